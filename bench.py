@@ -32,7 +32,9 @@ host memory.  Both transfers are INSIDE the timed region; `value` = input bytes 
           TDC_BENCH_BACKEND=gloo rehearses the N > 1 path with several ranks on ONE GPU (collectives on CPU tensors).
 
 After the timed steps ONE more step runs with per-kernel HIP-event timing switched on (untimed) -- the roofline object and
-the per-kernel table come from it.  Prints ONE JSON line (rank 0).  PyTorch is used for torch.distributed and the
+the per-kernel table come from it.  --dump-outputs DIR writes the stream of the last timed step (N > 1: rank 0's block container) as
+float32 / float64 .npy files under DIR before that (dump_stream: whole up to 8 MiB, else a seeded sample; at most ~50 MB), so that the
+outputs of two builds can be compared: with the same arguments the input text is the same in every run.  Prints ONE JSON line (rank 0).  PyTorch is used for torch.distributed and the
 multi-GPU staging buffers only.
 """
 import argparse
@@ -65,8 +67,43 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra figures (256 MiB English, 10^9 B DNA)")
     ap.add_argument("--dna-sample", type=int, default=1 << 25, help="bytes of DNA text the oracle compresses for the configs[2] check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the stream of the last timed step (N > 1: rank 0's block container) as DIR/<name>.npy")
     ap.add_argument("--cpu-result", default=None, help=argparse.SUPPRESS)      # (N > 1 self-launch: the parent's CPU baseline, a JSON file)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# ---- --dump-outputs: what the timed path handed its caller, as .npy files a second build's run can be compared with ---------------
+DUMP_FULL_MAX = 1 << 23         # streams up to 8 MiB are written whole (32 MB as float32)
+DUMP_SAMPLE = 1 << 22           # a longer stream: this many positions drawn with a fixed seed, + their indices (16 + 32 MB)
+DUMP_EDGE = 1 << 16             # first / last bytes of the stream (the head holds the code table), always written whole
+DUMP_SEED = 20240601
+
+
+def dump_stream(dirname, stream):
+    """stream: the uint8 bytes the timed path returned.  Writes float32 / float64 .npy files, at most ~50 MB in all:
+    stream_length, stream_byte_histogram (byte counts of the whole stream), stream_head / stream_tail (DUMP_EDGE bytes each), and
+    stream -- the whole stream if it has at most DUMP_FULL_MAX bytes, else DUMP_SAMPLE bytes at the positions in stream_index
+    (sorted, drawn from numpy's default_rng(DUMP_SEED) over the stream's length: equal streams give equal samples)."""
+    import numpy as np
+    s = np.ascontiguousarray(stream, dtype=np.uint8).reshape(-1)
+    os.makedirs(dirname, exist_ok=True)
+    out = {"stream_length": np.array([s.size], dtype=np.float64),
+           "stream_byte_histogram": np.bincount(s, minlength=256).astype(np.float64),
+           "stream_head": s[:DUMP_EDGE].astype(np.float32),
+           "stream_tail": s[-DUMP_EDGE:].astype(np.float32) if s.size else np.zeros(0, dtype=np.float32)}
+    if s.size <= DUMP_FULL_MAX:
+        out["stream"] = s.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, s.size, DUMP_SAMPLE, dtype=np.int64))
+        out["stream"] = s[idx].astype(np.float32)
+        out["stream_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(out)
 
 
 # ---- CPU baseline: runs BEFORE this process touches the GPU (child processes are plain CPU programs) -------------------------
@@ -187,6 +224,8 @@ def launch_ranks(args):
            "--threshold", str(args.threshold), "--gen", args.gen, "--no-cpu-baseline"]
     if args.no_extra:
         cmd.append("--no-extra")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if cpu_file:
         cmd += ["--cpu-result", cpu_file]
     env = dict(os.environ)
@@ -431,6 +470,14 @@ def main():
     else:
         step, exchange = (step_shared, "shared host memory") if shared is not None else (step_gather, "rccl gather to rank 0")
     dt, dev_ms, (out_len, st, sizes) = timed(step)
+    dumped = None
+    if args.dump_outputs and rank == 0:                 # untimed, before anything else reuses the buffers of the last timed step
+        if world == 1:
+            dumped = dump_stream(args.dump_outputs, h_out.a[:out_len])
+        elif shared is not None:
+            dumped = dump_stream(args.dump_outputs, shared.a[:payload_offsets(sizes)[1]])
+        else:
+            dumped = dump_stream(args.dump_outputs, h_container[:payload_offsets(sizes)[1]].numpy())
     ranks_seen = world
     if world > 1:
         bitmap = torch.tensor([1 << rank], dtype=torch.int64, device=coll_device)
@@ -518,6 +565,8 @@ def main():
                                "algorithmic_GBs": round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1) if p["ms"] > 0 else None}
                         for name, p in prof.items() if p["launches"]},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world == 1 and args.gen == "english" and args.threshold == 2 and N == 2_000_000_000:
             # byte for byte the oracle's stream of the metric's text: size + SHA-256 against the committed full-size golden
             line["stream_matches_golden"] = matches_golden("english_2e9", h_out.a[:out_len])
