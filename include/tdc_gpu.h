@@ -11,7 +11,8 @@
  *     occurs nowhere else (ds/SADivSufSort.hpp:20-25, ds/TextDS.hpp:132-138).  n < 2^31 (32-bit len_t, def.hpp:103).
  *   - every function returns 0 on success or a negative tdc_gpu_status; tdc_gpu_strerror() explains it.
  *   - host output buffers returned through `uint8_t** out` are malloc'd by the library: free with tdc_gpu_free().
- *   - a context owns one HIP stream and one device arena on one GPU; it is not thread-safe, use one per thread.
+ *   - a context owns three HIP streams (compute, copy, low-priority side work) and one device arena on one GPU; every call
+ *     returns with all three streams idle.  A context is not thread-safe, use one per thread.
  *     Every call switches the calling thread to the context's device and restores the previous current device on return.
  *     The library NEVER falls back to a CPU path: without a usable GPU every compute call fails with TDC_GPU_ERR_HIP.
  */

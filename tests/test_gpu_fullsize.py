@@ -102,11 +102,12 @@ def test_metric_config_2e9_end_to_end(gpu_ctx):
             assert sha256(h_back.a) == sha256(h_text.a)
         finally:
             h_back.free()
-        # a buffer that is too small is refused with the required size, nothing is written past it
-        tiny = np.concatenate([h_text.a[:1 << 22], np.zeros(1, dtype=np.uint8)])
+        # a buffer that is too small is refused with the required size, nothing is written past it (a text of 2^26 + 1 bytes: the
+        # refused call has run the chunked upload, the level-2 digits and the forked run kernels on the side streams)
+        prefix = np.concatenate([h_text.a[:1 << 26], np.zeros(1, dtype=np.uint8)])
         small = np.full(4096, 0xA5, dtype=np.uint8)
         with pytest.raises(T.TdcGpuError) as e:
-            gpu_ctx.lcpcomp_compress_into(tiny, len(tiny), small[:1024], 2, 1)
+            gpu_ctx.lcpcomp_compress_into(prefix, len(prefix), small[:1024], 2, 1)
         assert bool((small[1024:] == 0xA5).all())
         assert e.value.status == -5
         # bit-exact against the oracle's compressor on a prefix text (the generator's shorter outputs are prefixes)

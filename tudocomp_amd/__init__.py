@@ -170,7 +170,7 @@ def host_unregister(a):
 
 
 class Context:
-    """One GPU, one HIP stream, one device arena (tdc_gpu_ctx)."""
+    """One GPU, three HIP streams, one device arena (tdc_gpu_ctx)."""
 
     def __init__(self, device=0, options=None):
         """options: {name: value} applied through tdc_gpu_ctx_set_option ("wsort_min" or "TDC_GPU_WSORT_MIN": the same option) --

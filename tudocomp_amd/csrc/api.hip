@@ -51,6 +51,18 @@ struct HostBuf {
     HostBuf& operator=(const HostBuf&) = delete;
 };
 
+// waits for every stream of the context; the first error, if any
+hipError_t sync_streams(Ctx& c) {
+    hipError_t first = hipSuccess;
+    for (hipStream_t s : {c.stream, c.copy_stream, c.aux_stream}) {
+        const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
+
+// Every call that enqueues device work goes through here, and returns with every stream of its context idle: nothing of it
+// still reads the caller's buffers or writes into the arena the next call reuses, whichever way it ended.
 template <typename F>
 int guarded(tdc_gpu_ctx* ctx, F&& f) {
     if (!ctx) return TDC_GPU_ERR_ARG;
@@ -58,9 +70,12 @@ int guarded(tdc_gpu_ctx* ctx, F&& f) {
     ctx->kept = nullptr; ctx->kept_len = 0;      // (every call may reuse the arena)
     ctx->c.hist_ptr = nullptr;                   // the cached byte histogram belongs to ONE call (same address, other text: stale)
     DeviceGuard dg(ctx->c.device);               // the caller's current device is restored on every exit path
+    const hipStream_t compute = ctx->c.stream;
+    auto drain = [&] { ctx->c.stream = compute; return sync_streams(ctx->c); };
     try {
         HIP_TRY(dg.enter());
-        f();
+        try { f(); } catch (...) { (void)drain(); throw; }
+        HIP_TRY(drain());
         if (ctx->c.d_err) {                      // device-side error word (e.g. a look-back that timed out)
             u32 e = 0;
             HIP_TRY(hipMemcpy(&e, ctx->c.d_err, sizeof(u32), hipMemcpyDeviceToHost));
@@ -161,13 +176,6 @@ struct DevArrays {
     ~DevArrays() { encode_early_free(early); }
 };
 
-// c.stream points at another stream for the lifetime of the object (the stage functions enqueue on c.stream)
-struct StreamSwap {
-    Ctx& c; hipStream_t saved;
-    StreamSwap(Ctx& ctx, hipStream_t other) : c(ctx), saved(ctx.stream) { c.stream = other; }
-    ~StreamSwap() { c.stream = saved; }
-};
-
 // Checks that the 0 byte occurs exactly once, at n - 1 (ds/TextDS.hpp:132-138).  The count comes from the byte histogram of the text,
 // which the suffix array needs anyway (one pass for both; a host-buffer call has accumulated it behind the upload already).
 void validate_device_text(Ctx& c, const u8* d_text, size_t n) {
@@ -236,7 +244,7 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
     A.fs.cls = c.arena.get<u8>(n + 64);                  // class bytes for the encoder (filled by build_owner)
     // the metric's path (lcpcomp(comp=arrays, coder=huff) with the encoder's first half inside the flatten stage: nothing reads the dense
     // flen[] array behind build_owner): the factor lengths travel as bytes until then
-    const bool early_planned = strategy == TDC_GPU_COMP_ARRAYS && flatten && enc_coder == 0 && d_text && c.enc_early && c.enc_rec && c.copy_stream && c.huff_ok &&
+    const bool early_planned = strategy == TDC_GPU_COMP_ARRAYS && flatten && enc_coder == 0 && d_text && c.enc_early && c.enc_rec && c.huff_ok &&
                                n >= (c.enc_early >= 2 ? (size_t)1 : ((size_t)1 << 20)) && threshold >= 2;
     if (early_planned && c.flen_bytes) A.fs.flen8 = c.arena.get<u8>(n + 64);
     A.fs.want_owner_rem = early_planned ? (u32)c.owner_rem : 0u;   // (behind build_owner only the flatten rounds read owner[] on this path: the encoder reads cls[] and the records)
@@ -251,25 +259,18 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
     // The first half of the Huffman encoder (gaps, literal histogram, code table, bits per tile and their scan: 4-5 ms of streaming
     // kernels and three host round trips at 2e9 B) reads positions, lengths and class bytes but no source, and the flatten rounds are
     // bound by the latency of their chains, not by bandwidth: it runs on the copy stream next to the first round.
-    const bool early = flatten && enc_coder == 0 && d_text && c.enc_early && c.copy_stream && c.huff_ok && n >= (c.enc_early >= 2 ? (size_t)1 : ((size_t)1 << 20)) &&
+    const bool early = flatten && enc_coder == 0 && d_text && c.enc_early && c.huff_ok && n >= (c.enc_early >= 2 ? (size_t)1 : ((size_t)1 << 20)) &&
                        A.fs.have_list && A.fs.have_cls && A.fs.flenl && A.fs.nfact > 0;
     if (!early) expand_flen8(c, n, A.fs);                  // (planned, but there is no factor list to run it on: everybody else reads the dense array)
     if (early) {
         A.early = encode_early_reserve(c, n, c.enc_rec ? A.fs.nfact : 0);
-        HIP_TRY(hipEventRecord(c.ev_copy[0], c.stream));                  // the factors are in place
+        c.wait_for(c.copy_stream, c.stream);                               // the factors are in place
         // one step per round (the host never waits for the copy stream while a round needs it), the rest when the rounds are over
-        bool waited = false;
-        try {
-            flatten_factors(c, n, A.fs, &fl, [&](int round) {
-                StreamSwap sw(c, c.copy_stream);
-                if (!waited) { HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_copy[0], 0)); waited = true; }
-                if (round == 1 || round == 2) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, false);
-                else if (round == 0) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, true);
-            }, c.enc_rec ? encode_early_rec(A.early) : nullptr);
-        } catch (...) {
-            (void)hipStreamSynchronize(c.copy_stream);         // nothing of this call stays behind on the second stream
-            throw;
-        }
+        flatten_factors(c, n, A.fs, &fl, [&](int round) {
+            StreamSwap sw(c, c.copy_stream);
+            if (round == 1 || round == 2) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, false);
+            else if (round == 0) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, true);
+        }, c.enc_rec ? encode_early_rec(A.early) : nullptr);
     } else if (flatten) {
         flatten_factors(c, n, A.fs, &fl);
     } else {
@@ -471,9 +472,10 @@ int tdc_gpu_ctx_create(int device, tdc_gpu_ctx** out) {
             int lo = 0, hi = 0;
             if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
             if (hipStreamCreateWithPriority(&ctx->c.aux_stream, hipStreamNonBlocking, lo) != hipSuccess) { ctx->c.aux_stream = nullptr; (void)hipGetLastError(); }
-            for (auto& e : ctx->c.ev_aux) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        for (auto& e : ctx->c.ev_copy) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ctx->c.ev_join, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ctx->c.ev_dig2, hipEventDisableTiming));
+        for (auto& e : ctx->c.ev_chunk) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ctx->c.pinned_size = 4096;
         HIP_TRY(hipHostMalloc(&ctx->c.pinned, ctx->c.pinned_size, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc((void**)&ctx->c.pinned_hdr, Ctx::PINNED_HDR, hipHostMallocDefault));
@@ -504,7 +506,7 @@ void tdc_gpu_ctx_destroy(tdc_gpu_ctx* ctx) {
     if (!ctx) return;
     DeviceGuard dg(ctx->c.device);
     (void)dg.enter();
-    if (ctx->c.stream) (void)hipStreamSynchronize(ctx->c.stream);
+    (void)sync_streams(ctx->c);
     if (ctx->c.arena.base) (void)hipFree(ctx->c.arena.base);
     if (ctx->c.pinned) (void)hipHostFree(ctx->c.pinned);
     if (ctx->c.pinned_hdr) (void)hipHostFree(ctx->c.pinned_hdr);
@@ -512,10 +514,10 @@ void tdc_gpu_ctx_destroy(tdc_gpu_ctx* ctx) {
     if (ctx->c.zc_host) (void)hipHostFree(ctx->c.zc_host);
     if (ctx->c.d_err) (void)hipFree(ctx->c.d_err);
     for (auto& e : ctx->c.ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->c.ev_copy) if (e) (void)hipEventDestroy(e);
-    if (ctx->c.copy_stream) { (void)hipStreamSynchronize(ctx->c.copy_stream); (void)hipStreamDestroy(ctx->c.copy_stream); }
-    if (ctx->c.aux_stream) { (void)hipStreamSynchronize(ctx->c.aux_stream); (void)hipStreamDestroy(ctx->c.aux_stream); }
-    for (auto& e : ctx->c.ev_aux) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->c.ev_chunk) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->c.ev_join, ctx->c.ev_dig2}) if (e) (void)hipEventDestroy(e);
+    if (ctx->c.copy_stream) (void)hipStreamDestroy(ctx->c.copy_stream);
+    if (ctx->c.aux_stream) (void)hipStreamDestroy(ctx->c.aux_stream);
     if (ctx->c.ev_pool) { for (int i = 0; i < ctx->c.ev_pool_size; ++i) if (ctx->c.ev_pool[i]) (void)hipEventDestroy(ctx->c.ev_pool[i]); free(ctx->c.ev_pool); }
     free(ctx->c.pend);
     if (ctx->c.stream) (void)hipStreamDestroy(ctx->c.stream);
@@ -637,17 +639,16 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
         if (escape_device(c, d_raw, n, d_text) != tn) throw HipError{hipErrorUnknown, "escape: length mismatch", (int)__LINE__};
     } else {
         d_text = c.arena.get<u8>(n + 64);
-        if (n >= ((size_t)1 << 26) && c.copy_stream) {
+        if (n >= ((size_t)1 << 26)) {
             // The upload in chunks on the copy stream.  Behind every chunk, on the compute stream: its byte histogram (sentinel check,
             // symbol codes) and -- texts that take the wide suffix sort -- level 1 of that sort for the chunk in front of it (a key reads
             // up to 64 bytes ahead), with the code map and the splitters taken from chunk 0 (prim.hpp WPre).  All copies are queued
             // first: the one host wait in between (the histogram of chunk 0) does not stall them.
             u32* d_hist = c.arena.get<u32>(256);
             HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * sizeof(u32), c.stream));
-            HIP_TRY(hipEventRecord(c.ev_copy[8], c.stream));                   // (the copy stream starts behind whatever the compute stream did before)
-            HIP_TRY(hipStreamWaitEvent(c.copy_stream, c.ev_copy[8], 0));
+            c.wait_for(c.copy_stream, c.stream);                                // (the copy stream starts behind whatever the compute stream did before)
             const bool try_pre = c.wsort_overlap && c.wpre && wsort_applicable(c, n);
-            const size_t CH = try_pre ? (size_t)c.upload_chunks : 8;      // (at most 24: ev_copy[16 ..])
+            const size_t CH = try_pre ? (size_t)c.upload_chunks : 8;
             // Chunk boundaries (multiples of 4096).  With level 1 behind the copies the last three chunks shrink geometrically (0.6, 0.36,
             // 0.22 of the others): level 1 of a chunk runs 1.7 x as fast as its copy, so each of them is done before the next, shorter copy
             // ends, and what is left behind the last copy is the level 1 of a fifth of a chunk.
@@ -672,7 +673,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
                 coff.push_back(n);
             }
             const size_t nch = coff.size() - 1;
-            if (nch > 24) throw HipError{hipErrorUnknown, "upload: more chunks than copy events (ev_copy[16 .. 39])", (int)__LINE__};
+            if (nch > Ctx::CHUNK_EVENTS) throw HipError{hipErrorUnknown, "upload: more chunks than chunk events", (int)__LINE__};
             size_t queued = 0;                                                  // copies handed to the copy stream so far
             auto queue_copies = [&](size_t upto) {                              // (a few chunks ahead of the compute stream's work, not all at once:
                 for (; queued < nch && queued < upto; ++queued) {               //  the runtime batches what it is given in one go)
@@ -681,7 +682,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
                     //  -- and a copy starts behind the 64 bytes its predecessor delivered: no byte is written twice while level 1 reads it)
                     const size_t off = coff[queued] + (queued ? 64 : 0), end = std::min(coff[queued + 1] + 64, n);
                     if (end > off) HIP_TRY(hipMemcpyAsync(d_text + off, text + off, end - off, hipMemcpyHostToDevice, c.copy_stream));
-                    HIP_TRY(hipEventRecord(c.ev_copy[16 + queued], c.copy_stream));
+                    HIP_TRY(hipEventRecord(c.ev_chunk[queued], c.copy_stream));
                     (void)hipStreamQuery(c.copy_stream);                        // (submit now)
                 }
             };
@@ -689,7 +690,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
             for (size_t q = 0; q < nch; ++q) {
                 const size_t off = coff[q], len = coff[q + 1] - off;
                 queue_copies(q + 4);
-                HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_copy[16 + q], 0));
+                HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_chunk[q], 0));
                 text_histogram_add(c, d_text + off, len, d_hist);
                 if (q == 0 && try_pre) {
                     u32 h0[256];
@@ -708,12 +709,12 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
     }
     const int e1 = ev.tick();
     u8* d_out = nullptr;
-    struct SinkGuard {       // on every exit path: no copy into the caller's buffer is still in flight, the sink is forgotten
+    struct SinkGuard {       // on every exit path the sink is forgotten (guarded() waits for a copy into it that is still in flight)
         Ctx& c;
-        ~SinkGuard() { if (c.d2h_done && c.copy_stream) (void)hipStreamSynchronize(c.copy_stream); c.d2h_host = nullptr; c.d2h_cap = 0; c.d2h_done = 0; }
+        ~SinkGuard() { c.d2h_host = nullptr; c.d2h_cap = 0; c.d2h_done = 0; }
     } sink_guard{c};
     c.d2h_host = ho.into; c.d2h_cap = ho.into ? ho.cap : 0; c.d2h_done = 0;      // the encoder may start the D2H while it still packs
-    struct PreGuard { Ctx& c; ~PreGuard() { if (c.wpre) { c.wpre->active = false; c.wpre->begun = false; } if (c.aux_stream) (void)hipStreamSynchronize(c.aux_stream); c.arena.release_top(); } } pre_guard{c};   // (the side stream is idle by now unless the call failed half-way)
+    struct PreGuard { Ctx& c; ~PreGuard() { if (c.wpre) { c.wpre->active = false; c.wpre->begun = false; } c.arena.release_top(); } } pre_guard{c};
     const size_t len = run_pipeline(c, d_text, tn, threshold, flatten, coder, &d_out, 0, stats, ev, comp);
     const int e2 = ev.tick();
     *ho.out_len = len;
@@ -725,10 +726,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
         if (len > ho.cap) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
         const size_t done = c.d2h_done <= len ? c.d2h_done : 0;
         HIP_TRY(hipMemcpyAsync(ho.into + done, d_out + done, len - done, hipMemcpyDeviceToHost, c.stream));
-        if (done) {                                                          // the front part travels on the copy stream
-            HIP_TRY(hipEventRecord(c.ev_copy[9], c.copy_stream));
-            HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_copy[9], 0));
-        }
+        if (done) c.wait_for(c.stream, c.copy_stream);                      // the front part travels on the copy stream
         const int e3 = ev.tick();
         if (stats) { ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_d2h, e2, e3); ev.span(&stats->ms_total, e0, e3); }
         ev.finish();

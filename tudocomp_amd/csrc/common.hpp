@@ -201,7 +201,7 @@ struct Ctx {
     //  tdc_gpu_ctx_set_option() writes -- api.hip, one table -- and the shipped library never looks at TDC_GPU_* variables unless
     //  TDC_GPU_DEBUG_KNOBS=1 asks tdc_gpu_ctx_create() to apply them through that same function)
     int upload_tail_n = 3, upload_tail_pct = 60;   // the last upload_tail_n chunks of the overlapped upload shrink by this factor each (0.6, 0.36, 0.22: what is left behind the last copy is the device work of a small chunk)
-    int upload_chunks = 16;        // chunks of the overlapped upload (4 .. 24: ev_copy[16 ..]; option upload_chunks)
+    int upload_chunks = 16;        // chunks of the overlapped upload (4 .. 24; option upload_chunks)
     int flatten_steps = 1;         // flatten: chain steps per factor in the first round (0: unlimited; measured: 1,2,4,.. 8.5 ms; unlimited 11.2 ms)
     int flatten_growth = 8;        // ... and the factor the budget grows by per round (measured at 256 MiB: x2 8.4 ms, x4 7.4 ms, x8 7.0 ms)
     int sa_init_syms = 0;          // classic suffix sort: cap on the symbols of the initial key (0: as many as 64 bits hold; tuning)
@@ -215,10 +215,13 @@ struct Ctx {
     u32 hist_cache[256] = {};
     const u8* hist_ptr = nullptr;
     size_t hist_n = 0;
+    // side streams: every call returns with them idle (api.hip guarded()), so their events are reused from call to call
     hipStream_t copy_stream = nullptr;
-    hipStream_t aux_stream = nullptr;  // low-priority side stream: work that fills idle device time behind the upload (wsort.hip wsort_pre_chunk)
-    hipEvent_t ev_aux[2] = {};
-    hipEvent_t ev_copy[40] = {};
+    hipStream_t aux_stream = nullptr;  // low-priority side stream: work that fills idle device time behind the upload (wsort.hip wsort_pre_chunk); may be null
+    hipEvent_t ev_join = nullptr;      // wait_for()
+    static constexpr size_t CHUNK_EVENTS = 32;
+    hipEvent_t ev_chunk[CHUNK_EVENTS] = {};   // chunked uploads: one event per chunk, recorded ahead and waited on later
+    hipEvent_t ev_dig2 = nullptr;      // the level-2 digits on the aux stream (wsort_pre_chunk -> wsort_pre_finish)
     struct WPre* wpre = nullptr;   // level 1 of the suffix sort done behind the upload (prim.hpp), owned by the API context
     u8* d2h_host = nullptr;        // destination (host) of the running call, or null
     size_t d2h_cap = 0;
@@ -241,6 +244,12 @@ struct Ctx {
         return npend++;
     }
     void prof_end(int idx) { if (idx >= 0) HIP_TRY(hipEventRecord(pend[idx].b, stream)); }
+    // `waiter` goes on once `signaller` has got through what is enqueued on it so far.  One event serves every such pair:
+    // hipStreamWaitEvent takes the event's state at the time of the call, so the event may be recorded again right away.
+    void wait_for(hipStream_t waiter, hipStream_t signaller) {
+        HIP_TRY(hipEventRecord(ev_join, signaller));
+        HIP_TRY(hipStreamWaitEvent(waiter, ev_join, 0));
+    }
     struct ProfScope {     // RAII: times everything enqueued on the stream between construction and destruction
         Ctx& c; int idx;
         ProfScope(Ctx& ctx, int cls, u64 bytes) : c(ctx), idx(ctx.prof_begin(cls, bytes)) {}
@@ -335,6 +344,13 @@ struct Ctx {
             HIP_TRY(hipStreamSynchronize(stream));
         }
     }
+};
+
+// c.stream points at another stream for the lifetime of the object (the stage functions enqueue on c.stream)
+struct StreamSwap {
+    Ctx& c; hipStream_t saved;
+    StreamSwap(Ctx& ctx, hipStream_t other) : c(ctx), saved(ctx.stream) { c.stream = other; }
+    ~StreamSwap() { c.stream = saved; }
 };
 
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())

@@ -744,21 +744,16 @@ static void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const
     u8* dst = decode_dest(out, n);
     tick("host buffer");
     constexpr size_t CH = (size_t)64 << 20;
-    if (c.copy_stream && n >= 2 * CH && !dlog && host_pinned(dst)) {
+    if (n >= 2 * CH && !dlog && host_pinned(dst)) {
         // the copy pass in chunks, every chunk downloaded on the second stream while the next one is copied (a chunk reads literal
-        // positions only, wherever they are: the chunks do not depend on one another)
-        struct Drain { Ctx& c; ~Drain() { (void)hipStreamSynchronize(c.copy_stream); } } drain{c};   // nothing of this call stays behind on the second stream
-        u32 k = 0;
-        for (size_t a = 0; a < n; a += CH, ++k) {
+        // positions only, wherever they are: the chunks do not depend on one another; the call waits for the last copy on its way out)
+        for (size_t a = 0; a < n; a += CH) {
             const size_t b = std::min(n, a + CH);
             ref_copy_kernel<<<cdiv(b - a, 256), 256, 0, s>>>(d_ref, a, b, d_text);
             LAUNCH_CHECK();
-            hipEvent_t ev = c.ev_copy[k & 31];
-            HIP_TRY(hipEventRecord(ev, s));
-            HIP_TRY(hipStreamWaitEvent(c.copy_stream, ev, 0));
+            c.wait_for(c.copy_stream, s);
             HIP_TRY(hipMemcpyAsync(dst + a, d_text + a, b - a, hipMemcpyDeviceToHost, c.copy_stream));
         }
-        HIP_TRY(hipStreamSynchronize(c.copy_stream));
         HIP_TRY(hipStreamSynchronize(s));
         return;
     }
@@ -807,24 +802,21 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
     struct Upload {
         Ctx& c; size_t chunk = 0, nchunks = 0, waited = 0;
         explicit Upload(Ctx& cc) : c(cc) {}
-        ~Upload() { if (nchunks) (void)hipStreamSynchronize(c.copy_stream); }    // (the caller's buffer is not read after the call returns)
         void need(size_t bytes, size_t len, hipStream_t s) {
             if (!nchunks) return;
             const size_t upto = std::min(nchunks, (std::min(bytes, len) + chunk - 1) / chunk);
-            for (; waited < upto; ++waited) HIP_TRY(hipStreamWaitEvent(s, c.ev_copy[waited], 0));
+            for (; waited < upto; ++waited) HIP_TRY(hipStreamWaitEvent(s, c.ev_chunk[waited], 0));
         }
     } up(c);
-    if (c.copy_stream && len >= ((size_t)64 << 20) && host_pinned(stream)) {
+    if (len >= ((size_t)64 << 20) && host_pinned(stream)) {
         up.chunk = std::max((size_t)32 << 20, (len + 31) / 32);
         up.chunk = (up.chunk + 4095) & ~(size_t)4095;
         up.nchunks = (len + up.chunk - 1) / up.chunk;
-        // (decompression has ev_copy[0 .. 31] to itself -- the compress path's slots 0, 8, 9, 16 .. 39 belong to calls that never overlap
-        //  this one, every path drains the copy stream before it returns --; the chunk size above keeps the count within them)
-        if (up.nchunks > 32) throw HipError{hipErrorUnknown, "decode: more upload chunks than copy events", (int)__LINE__};
+        if (up.nchunks > Ctx::CHUNK_EVENTS) throw HipError{hipErrorUnknown, "decode: more upload chunks than chunk events", (int)__LINE__};
         for (size_t k = 0; k < up.nchunks; ++k) {
             const size_t a = k * up.chunk, b = std::min(len, a + up.chunk);
             HIP_TRY(hipMemcpyAsync(d_stream + a, stream + a, b - a, hipMemcpyHostToDevice, c.copy_stream));
-            HIP_TRY(hipEventRecord(c.ev_copy[k], c.copy_stream));
+            HIP_TRY(hipEventRecord(c.ev_chunk[k], c.copy_stream));
         }
         (void)hipStreamQuery(c.copy_stream);                                                 // (submit now)
     } else {

@@ -648,7 +648,7 @@ static void encode_step_b(Ctx& c, const u8* text, size_t n, FactorSpace& fs, int
     if (E.tile_rank) exclusive_sum_u32(c, E.tile_rank, E.tile_rank, tiles, nullptr);
     // With a host destination (end-to-end entry point) the pack runs in PACK_CH chunks of tiles (second half): the bit offsets at
     // which the chunks end travel with the total
-    E.may_overlap = c.d2h_host && tiles >= 64 * PACK_CH && c.copy_stream;
+    E.may_overlap = c.d2h_host && tiles >= 64 * PACK_CH;
     pick_u64_kernel<<<1, 64, 0, s>>>(tile_bits, tiles, PACK_CH, E.d_tp + 1);
     LAUNCH_CHECK();
     E.seq_b = c.publish_async(E.d_tp, (1 + PACK_CH) * sizeof(u64), 2);
@@ -742,11 +742,9 @@ size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder
             if (overlap && q + 1 < CH) {
                 const size_t safe = (size_t)((base_bits + h_end[q]) / 64) * 8;          // bytes in front of the word the next chunk may still touch
                 if (safe > copied) {
-                    HIP_TRY(hipEventRecord(c.ev_copy[q], s));
-                    HIP_TRY(hipStreamWaitEvent(c.copy_stream, c.ev_copy[q], 0));
+                    c.wait_for(c.copy_stream, s);
                     HIP_TRY(hipMemcpyAsync(c.d2h_host + copied, d_out + copied, safe - copied, hipMemcpyDeviceToHost, c.copy_stream));
                     copied = safe;
-                    c.d2h_done = copied;                     // (an error further down must still wait for this copy: api.hip SinkGuard)
                 }
             }
         }

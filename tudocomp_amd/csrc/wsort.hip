@@ -1660,23 +1660,14 @@ int ws_sort_impl(Ctx& c, const WKeyGen* gen, u64* K1[2], u64* K2[2], u32* V[2], 
                 const u32* l0 = wave_list, *l1 = wave_list + cur_cap, *l2 = wave_list + 2 * cur_cap, *l3 = wave_list + 3 * cur_cap;
                 // The four kernels work on disjoint runs and each is a chain of dependent loads per wave with little work behind it (none of
                 // them fills the device): with the context's two other streams at hand they run side by side (option wsort_run_streams).
-                const bool fork = c.wsort_run_streams && c.copy_stream && c.aux_stream && (wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]) >= 4096;
+                const bool fork = c.wsort_run_streams && c.aux_stream && (wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]) >= 4096;
                 hipStream_t sl = fork ? c.copy_stream : s, sw = fork ? c.aux_stream : s;
-                if (fork) {
-                    HIP_TRY(hipEventRecord(c.ev_copy[10], s));
-                    HIP_TRY(hipStreamWaitEvent(sl, c.ev_copy[10], 0));
-                    HIP_TRY(hipStreamWaitEvent(sw, c.ev_copy[10], 0));
-                }
+                if (fork) { c.wait_for(sl, s); c.wait_for(sw, s); }
                 if (wave_cnt[3]) { ws_run_wave_kernel<1024, PAIRS><<<cdiv(wave_cnt[3], 4), 256, 0, s>>>(A, l3, wave_cnt[3]); LAUNCH_CHECK(); }
                 if (wave_cnt[2]) { ws_run_wave_kernel<256, PAIRS><<<cdiv(wave_cnt[2], 4), 256, 0, sw>>>(A, l2, wave_cnt[2]); LAUNCH_CHECK(); }
                 if (wave_cnt[0]) { ws_run_lane_kernel<32, PAIRS><<<cdiv(wave_cnt[0], 8), 256, 0, sl>>>(A, l0, wave_cnt[0]); LAUNCH_CHECK(); }
                 if (wave_cnt[1]) { ws_run_lane_kernel<64, PAIRS><<<cdiv(wave_cnt[1], 4), 256, 0, sl>>>(A, l1, wave_cnt[1]); LAUNCH_CHECK(); }
-                if (fork) {
-                    HIP_TRY(hipEventRecord(c.ev_copy[11], sl));
-                    HIP_TRY(hipEventRecord(c.ev_copy[12], sw));
-                    HIP_TRY(hipStreamWaitEvent(s, c.ev_copy[11], 0));
-                    HIP_TRY(hipStreamWaitEvent(s, c.ev_copy[12], 0));
-                }
+                if (fork) { c.wait_for(s, sl); c.wait_for(s, sw); }
                 st->wave_runs += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
                 wave_cnt[0] = wave_cnt[1] = wave_cnt[2] = wave_cnt[3] = 0;
             }
@@ -1929,10 +1920,8 @@ void wsort_pre_chunk(Ctx& c, WPre& P, u32 q) {
         // (on the context's low-priority side stream, behind this chunk's level 1: the chain copy -> level 1 -> next copy is not lengthened,
         //  the digits fill the device's idle time behind the upload.  Its tables are allocated where this chunk's level-1 scratch was and
         //  stay: the next chunk's scratch lies above them, the side stream only touches them once level 1 is through -- the event)
-        HIP_TRY(hipEventRecord(c.ev_aux[0], c.stream));
-        HIP_TRY(hipStreamWaitEvent(c.aux_stream, c.ev_aux[0], 0));
-        struct Swap { Ctx& c; hipStream_t saved; ~Swap() { c.stream = saved; } } swap{c, c.stream};
-        c.stream = c.aux_stream;
+        c.wait_for(c.aux_stream, c.stream);
+        StreamSwap swap(c, c.aux_stream);
         hipStream_t s = c.stream;
         // ---- round 6 (round 4's variant re-measured now that a chunk's level 1 takes 1.3 instead of 1.7 ms of its 2.2 ms copy): the
         //      level-2 DIGITS of this chunk's records behind the upload as well -- the chunk's F0 buckets are the segments, every bucket is
@@ -1966,14 +1955,14 @@ void wsort_pre_chunk(Ctx& c, WPre& P, u32 q) {
         else { if (last2) launch(std::integral_constant<int, 1>{}, std::true_type{}); else launch(std::integral_constant<int, 1>{}, std::false_type{}); }
         LAUNCH_CHECK();
         c.prof_end(pc);
-        HIP_TRY(hipEventRecord(c.ev_aux[1], c.aux_stream));
+        HIP_TRY(hipEventRecord(c.ev_dig2, c.aux_stream));
     }
 }
 
 void wsort_pre_finish(Ctx& c, WPre& P, const u32* hist_full) {
     P.active = false;
     if (!P.begun) return;
-    if (P.dig2) HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_aux[1], 0));     // (the level-2 digits of the last chunks)
+    if (P.dig2) HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_dig2, 0));     // (the level-2 digits of the last chunks)
     for (int i = 1; i < 256; ++i) {
         const bool in_map = (P.present[i >> 5] >> (i & 31)) & 1u;
         if ((hist_full[i] != 0) != in_map) return;            // a byte value chunk 0 did not show (or the reverse): the keys are worthless
