@@ -6,6 +6,8 @@ large alphabets, inputs containing 0x00 / 0xFF (escaping changes n) and planted 
 """
 import random
 
+import numpy as np
+
 
 def fib_word(k):
     a, b = b"b", b"a"
@@ -93,4 +95,61 @@ def random_small(count, seed):
         else:
             s = bytes(rng.choice([0, 255, 97, 98]) for _ in range(n))
         out.append(("r%d" % i, s))
+    return out
+
+
+# ---- generators of the alphabet / code-depth tests (tests/test_gpu_alphabets.py); numpy, deterministic for a seed -------------------
+
+def chain_counts(k, slack=0.05, extra=2):
+    """k counts 1, 1, ... in which every count exceeds, by a fraction `slack` and at least 1, the sum of all counts but its
+    predecessor plus `extra` (the weight of the few literals outside the chain: the sentinel, ...): Huffman merges them as a chain,
+    the rarest symbols get codes of about k - 1 bits.  (Fibonacci numbers leave a margin of exactly 1 and lose depth to any literal
+    the plan did not count.)"""
+    c = [1, 1][:k]
+    while len(c) < k:
+        rest = sum(c) - c[-1] + extra
+        c.append(max(c[-1], rest + 1 + int(rest * slack)))
+    return c
+
+
+def deep_code_text(target_longest, seed=1, slack=0.05, copy_len=48, seg=(120, 230)):
+    """Raw bytes (no 0x00 / 0xFF) whose lcpcomp literals have a chain-shaped histogram -- Huffman codes of `target_longest` bits at
+    thresholds 24..copy_len (the tests read the depth from the stream) -- and that still has factors: segments of `seg` shuffled
+    literals over the byte values 0x80.. with chain_counts(target_longest) occurrences (the sentinel and a 'z' are the extra two), each followed by a run of `copy_len` bytes 'z'.  No literal
+    byte occurs in a run, so a factor (threshold up to copy_len) covers a run and never a rare literal, and the runs add a literal
+    or two themselves; two segments plus a run stay below 512 bytes, the longest literal run the device parse takes (fdist_max)."""
+    rng = np.random.default_rng(seed)
+    counts = chain_counts(target_longest, slack)
+    lits = np.repeat(np.arange(0x80, 0x80 + len(counts), dtype=np.uint8), counts)
+    rng.shuffle(lits)
+    run = np.full(copy_len, ord("z"), dtype=np.uint8)
+    cuts = np.cumsum(rng.integers(seg[0], seg[1] + 1, size=len(lits) // seg[0] + 2))
+    cuts = cuts[cuts < len(lits)]
+    parts = []
+    for a, b in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(lits)]])):
+        parts.append(lits[a:b])
+        parts.append(run)
+    return np.concatenate(parts)
+
+
+def alphabet_text(n, sigma, dist="uniform", seed=1, escapes=False, zipf_s=1.1):
+    """n raw bytes over sigma - 1 byte values, so that the escaped, 0-terminated text has exactly `sigma` symbols counting the
+    sentinel.  dist: "uniform" or "zipf" (rank r drawn with weight 1 / r^zipf_s).  escapes=True puts 0x00 and 0xFF among the values
+    and leaves 0xFE out (the escaping writes 0x00 as FF FE and 0xFF as FF FF: the alphabet keeps its size, the text grows and
+    gains 0xFF literals); sigma = 256 needs it (255 values besides the sentinel)."""
+    rng = np.random.default_rng(seed)
+    k = sigma - 1
+    if escapes or k > 253:
+        assert k >= 2
+        vals = np.concatenate([[0x00, 0xFF], rng.permutation(np.arange(1, 0xFE))[:k - 2]]).astype(np.uint8)
+    else:
+        vals = rng.permutation(np.arange(1, 0xFE))[:k].astype(np.uint8)
+    rng.shuffle(vals)
+    if dist == "uniform":
+        idx = rng.integers(0, k, size=n)
+    else:
+        w = 1.0 / np.arange(1, k + 1) ** zipf_s
+        idx = rng.choice(k, size=n, p=w / w.sum())
+    out = vals[idx]
+    out[:k] = vals                                   # every value occurs
     return out

@@ -68,6 +68,29 @@ def test_host_huffman_table_matches_oracle_restatement():
         assert list(t["order"][:sigma]) == list(o.order[:sigma])
         assert list(t["len_of"]) == list(o.len_of)
         assert list(t["code_of"]) == list(o.code_of)
+    # chain-shaped counts (Fibonacci numbers, margins from corpus.chain_counts) up to the u32 limit: codes of up to 46 bits, code
+    # words wider than 32 bits, node weights that no longer fit in 32 bits
+    from tests import corpus
+    fib = [1, 1]
+    while fib[-1] + fib[-2] < 1 << 32:
+        fib.append(fib[-1] + fib[-2])
+    chains = [fib, fib[:40], corpus.chain_counts(34), corpus.chain_counts(36, 0.02)]
+    chains += [[min(x, (1 << 32) - 1) for x in corpus.chain_counts(k, 0.0, 0)] for k in (45, 50)]
+    longest_seen = 0
+    for it, counts in enumerate(chains):
+        C = np.zeros(256, dtype=np.uint32)
+        syms = rng.choice(256, size=len(counts) + 3, replace=False)
+        C[syms[:len(counts)]] = counts
+        if it % 2:
+            C[syms[len(counts):]] = [7, 1000, 123456]     # a few symbols off the chain
+        t = T.huffman_table(C)
+        o = O.huffman_table(C)
+        assert t["sigma"] == o.sigma and t["longest"] == o.longest, it
+        assert list(t["order"][:o.sigma]) == list(o.order[:o.sigma])
+        assert list(t["len_of"]) == list(o.len_of), it
+        assert list(t["code_of"]) == list(o.code_of), it
+        longest_seen = max(longest_seen, o.longest)
+    assert longest_seen >= 40, longest_seen
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -12,7 +12,7 @@ import pytest
 
 import tudocomp_amd as T
 from oracle import oracle as O
-from tests.util import sha256, load_json
+from tests.util import sha256, load_json, huff_header
 
 pytestmark = pytest.mark.gpu
 
@@ -31,48 +31,6 @@ def _assert_golden(name, stream, st=None):
                 assert st[k] == g[k], (name, k, st[k], g[k])
 
 
-class _Bits:
-    """MSB-first bit reader (io/BitIStream.hpp) for the stream header only."""
-
-    def __init__(self, data):
-        self.d, self.p = data, 0
-
-    def bit(self):
-        b = (int(self.d[self.p >> 3]) >> (7 - (self.p & 7))) & 1
-        self.p += 1
-        return b
-
-    def int(self, bits):
-        v = 0
-        for _ in range(bits):
-            v = (v << 1) | self.bit()
-        return v
-
-    def compressed_int(self, b=7):            # io/BitIStream.hpp read_compressed_int: b-bit groups, each preceded by a "more" bit
-        v, shift = 0, 0
-        while True:
-            more = self.bit()
-            v |= self.int(b) << shift
-            shift += b
-            if not more:
-                return v
-
-
-def _header(stream):
-    """(n, flen_min, flen_max, fdist_max) of a lcpcomp(coder=huff) stream (LZSSCoding.hpp:27-41 behind the Huffman table)."""
-    r = _Bits(stream)
-    if r.bit():                               # huffmantable_encode (HuffmanCoder.hpp:264-273)
-        longest = r.compressed_int()
-        for _ in range(longest):
-            r.compressed_int()
-        sigma = r.compressed_int()
-        for _ in range(sigma):
-            r.int(8)
-    n = r.int(32)
-    w = O.bits_for(n)
-    return n, r.int(w), r.int(w), r.int(w)
-
-
 def test_metric_config_2e9_end_to_end(gpu_ctx):
     N = 2_000_000_000
     n = N + 1
@@ -87,7 +45,8 @@ def test_metric_config_2e9_end_to_end(gpu_ctx):
         stream = h_out.a[:out_len]
         assert sha256(h_text.a[:N]) == FULL["english_2e9"]["text_sha256"]
         _assert_golden("english_2e9", stream, st)          # byte for byte (by hash) the oracle's stream of the same 2*10^9 B text
-        hn, fmin, fmax, dmax = _header(stream)
+        h = huff_header(stream)
+        hn, fmin, fmax, dmax = h["n"], h["flen_min"], h["flen_max"], h["fdist_max"]
         assert (hn, fmin, fmax, dmax) == (n, st["flen_min"], st["flen_max"], st["fdist_max"])
         assert fmin >= 2 and fmax <= st["maxlcp"]
         back = O.lcpcomp_huff_decompress(stream)

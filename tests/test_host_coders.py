@@ -45,6 +45,23 @@ def test_encoder_decoder_classes_match_oracle(tmp_path, coder):
             assert (tmp_path / "d").read_bytes() == text, (name, thr, coder)
 
 
+@pytest.mark.parametrize("target", [13, 24])
+def test_huffman_coder_classes_on_deep_codes(tmp_path, target):
+    """literals with chain-shaped counts (corpus.deep_code_text): codes longer than the Decoder's lookup take its canonical walk"""
+    from tests.util import huff_header
+    text = np.concatenate([corpus.deep_code_text(target, seed=target), np.zeros(1, dtype=np.uint8)]).tobytes()
+    f = _factors(text, 32)
+    want = O.encode_huff(text, f)[0]
+    assert huff_header(want)["longest"] == target
+    tri = np.stack([f["pos"], f["src"], f["len"]], axis=1).astype(np.uint32)
+    (tmp_path / "t").write_bytes(text)
+    (tmp_path / "f").write_bytes(tri.tobytes())
+    subprocess.check_call([TOOL, "encode", "huff", str(tmp_path / "t"), str(tmp_path / "f"), str(tmp_path / "o")])
+    assert (tmp_path / "o").read_bytes() == want
+    subprocess.check_call([TOOL, "decode", "huff", str(tmp_path / "o"), str(tmp_path / "d")])
+    assert (tmp_path / "d").read_bytes() == text
+
+
 def test_gamma_coder_classes_match_oracle(tmp_path):
     for name, data in SMALL:
         if not data or data[-1] >= 0x80:

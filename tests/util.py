@@ -52,3 +52,49 @@ def decode_sequence_case(k):
             p += tok[2]
     assert p == len(want)
     return want + b"\0", factors_struct(pos, src, length)
+
+
+class Bits:
+    """MSB-first bit reader (io/BitIStream.hpp) for stream headers."""
+
+    def __init__(self, data):
+        self.d, self.p = data, 0
+
+    def bit(self):
+        b = (int(self.d[self.p >> 3]) >> (7 - (self.p & 7))) & 1
+        self.p += 1
+        return b
+
+    def int(self, bits):
+        v = 0
+        for _ in range(bits):
+            v = (v << 1) | self.bit()
+        return v
+
+    def compressed_int(self, b=7):            # io/BitIStream.hpp read_compressed_int: b-bit groups, each preceded by a "more" bit
+        v, shift = 0, 0
+        while True:
+            more = self.bit()
+            v |= self.int(b) << shift
+            shift += b
+            if not more:
+                return v
+
+
+def huff_header(stream):
+    """The header of a lcpcomp(coder=huff) stream: the Huffman table (huffmantable_encode, HuffmanCoder.hpp:264-273) -- "longest"
+    (0 without a table), "numl" (codes per length), "sigma" (literal symbols) -- and the fields behind it (LZSSCoding.hpp:27-41):
+    "n", "flen_min", "flen_max", "fdist_max"."""
+    from oracle import oracle as O
+    r = Bits(stream)
+    h = {"longest": 0, "numl": [], "sigma": 0}
+    if r.bit():
+        h["longest"] = r.compressed_int()
+        h["numl"] = [r.compressed_int() for _ in range(h["longest"])]
+        h["sigma"] = r.compressed_int()
+        for _ in range(h["sigma"]):
+            r.int(8)
+    h["n"] = r.int(32)
+    w = O.bits_for(h["n"])
+    h["flen_min"], h["flen_max"], h["fdist_max"] = r.int(w), r.int(w), r.int(w)
+    return h
