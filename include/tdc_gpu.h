@@ -78,6 +78,9 @@ typedef struct {
     uint32_t eager_levels;      /* levels processed inside one-launch runs of small levels (factorize_eager.hip)           */
     uint32_t eager_phases;      /* such runs                                                                            */
     uint32_t sa_star_chains;    /* chains of the star step of the suffix array's doubling fall-back (0: the step was not taken) */
+    uint32_t probes;            /* skip-ahead probes over runs of erased levels (arrays, max_lcp)                              */
+    uint32_t max_push_targets;  /* most target levels the pushes of one level went to (arrays, max_lcp)                        */
+    uint64_t d2h_early;         /* tdc_gpu_lcpcomp_compress_into: stream bytes copied to `out` while the pack still ran            */
 } tdc_gpu_stats;
 
 /* ---- context -------------------------------------------------------------------------------------------- */

@@ -90,6 +90,8 @@ def lib():
         L.orc_lcpcomp_ascii_decompress.argtypes = [ctypes.c_void_p, sz, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]
         L.orc_lcpcomp_sle_compress.argtypes = [ctypes.c_void_p, sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint,
                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(Stats)]
+        L.orc_lcpcomp_compress_any.argtypes = [ctypes.c_void_p, sz, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                               ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(Stats)]
         L.orc_encode_sle.argtypes = [ctypes.c_void_p, sz, ctypes.c_void_p, sz, ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p),
                                      ctypes.POINTER(sz), ctypes.POINTER(Stats)]
         L.orc_lcpcomp_sle_decompress.argtypes = [ctypes.c_void_p, sz, ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]
@@ -209,6 +211,22 @@ def max_heap(sa, isa, lcp, threshold):
     L.orc_max_heap.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     z = L.orc_max_heap(sa.ctypes.data_as(ctypes.c_void_p), isa.ctypes.data_as(ctypes.c_void_p), lcp.ctypes.data_as(ctypes.c_void_p),
                        len(sa), threshold, ctypes.byref(out))
+    raw = _take(out, z * 12) if out.value else b""
+    return np.frombuffer(raw, dtype=FACTOR_DTYPE).copy()
+
+
+def plcp_peaks(sa, isa, plcp, threshold):
+    """PLCPPeaksStrategy factor list in emission order; plcp[n-1] must hold phi[n-1] as PLCPFromPhi leaves it (the strategy
+    reads plcp[i + 1] up to i = n - 2)."""
+    plcp = np.ascontiguousarray(plcp, dtype=np.uint32)
+    out = ctypes.c_void_p()
+    L = lib()
+    L.orc_plcp_peaks.restype = ctypes.c_size_t
+    L.orc_plcp_peaks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                 ctypes.POINTER(ctypes.c_void_p)]
+    z = L.orc_plcp_peaks(sa.ctypes.data_as(ctypes.c_void_p), isa.ctypes.data_as(ctypes.c_void_p),
+                         plcp.ctypes.data_as(ctypes.c_void_p), len(sa), threshold,
+                         ctypes.byref(out))
     raw = _take(out, z * 12) if out.value else b""
     return np.frombuffer(raw, dtype=FACTOR_DTYPE).copy()
 
@@ -334,6 +352,25 @@ def lcpcomp_sle_compress(text, threshold=5, flatten=1, kmer=3):
     rc = lib().orc_lcpcomp_sle_compress(p, len(a), threshold, flatten, kmer, ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
     if rc:
         raise RuntimeError("orc_lcpcomp_sle_compress rc=%d" % rc)
+    return _take(out, n.value), st.as_dict()
+
+
+ORACLE_CODERS = {"huff": 0, "arith": 1, "arithmetic": 1, "ascii": 2, "sle": 3}
+ORACLE_COMPS = {"arrays": 0, "plcppeaks": 1, "max_lcp": 2, "heap": 3}
+
+
+def lcpcomp_compress_any(text, threshold, flatten, coder, comp, kmer=3):
+    """lcpcomp(coder=..., comp=...) for every strategy x coder pair: coder in ORACLE_CODERS, comp in ORACLE_COMPS, kmer for
+    coder="sle" only.  Raises RuntimeError where the reference fails (the arithmetic coder's division by zero: rc -8)."""
+    L = lib()
+    a, p = _buf(text)
+    out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+    rc = L.orc_lcpcomp_compress_any(p, len(a), threshold, int(flatten), ORACLE_CODERS[coder], kmer, ORACLE_COMPS[comp],
+                                    ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+    if rc:
+        if out.value:
+            L.orc_free(out)
+        raise RuntimeError("orc_lcpcomp_compress_any(coder=%s, comp=%s) rc=%d" % (coder, comp, rc))
     return _take(out, n.value), st.as_dict()
 
 

@@ -1118,52 +1118,53 @@ int orc_encode_sle(const uint8_t* text, size_t n, const orc_factor* f, size_t z,
 /* LCPCompressor.hpp:100-138 */
 static int lcpcomp_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten, int coder,
                             uint8_t** out, size_t* out_len, orc_stats* stats);
-static int g_strategy = 0;      /* 0 = ArraysComp, 1 = PLCPPeaksStrategy, 2 = MaxLCPStrategy (set around one call; the oracle is single-threaded test code) */
+static int g_strategy = 0;      /* 0 = ArraysComp, 1 = PLCPPeaksStrategy, 2 = MaxLCPStrategy, 3 = MaxHeapStrategy (set around one call; the oracle is single-threaded test code) */
+/* lcpcomp(coder=C, comp=S): every strategy x coder pair.  coder as encode_stream (0 huff, 1 arithmetic, 2 ascii, 3 sle with
+ * `kmer` in 1..7, ignored by the other coders), strategy as g_strategy.  -2 for an unknown coder, strategy or kmer. */
+int orc_lcpcomp_compress_any(const uint8_t* text, size_t n, uint32_t threshold, int flatten, int coder, unsigned kmer, int strategy,
+                             uint8_t** out, size_t* out_len, orc_stats* stats) {
+    if (coder < 0 || coder > 3 || strategy < 0 || strategy > 3) return -2;
+    if (coder == 3 && (kmer < 1 || kmer > 7)) return -2;
+    if (coder == 3) g_sle_k = kmer;
+    g_strategy = strategy;
+    const int rc = lcpcomp_compress(text, n, threshold, flatten, coder, out, out_len, stats);
+    g_strategy = 0;
+    g_sle_k = 3;
+    return rc;
+}
 int orc_lcpcomp_peaks_huff_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                                     uint8_t** out, size_t* out_len, orc_stats* stats) {
-    g_strategy = 1;
-    const int rc = lcpcomp_compress(text, n, threshold, flatten, 0, out, out_len, stats);
-    g_strategy = 0;
-    return rc;
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 0, 3, 1, out, out_len, stats);
 }
 /* lcpcomp(coder=huff, comp=max_lcp) */
 int orc_lcpcomp_maxlcp_huff_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                                      uint8_t** out, size_t* out_len, orc_stats* stats) {
-    g_strategy = 2;
-    const int rc = lcpcomp_compress(text, n, threshold, flatten, 0, out, out_len, stats);
-    g_strategy = 0;
-    return rc;
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 0, 3, 2, out, out_len, stats);
 }
 /* lcpcomp(coder=huff, comp=heap): MaxHeapStrategy */
 int orc_lcpcomp_heap_huff_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                                    uint8_t** out, size_t* out_len, orc_stats* stats) {
-    g_strategy = 3;
-    const int rc = lcpcomp_compress(text, n, threshold, flatten, 0, out, out_len, stats);
-    g_strategy = 0;
-    return rc;
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 0, 3, 3, out, out_len, stats);
 }
 int orc_lcpcomp_huff_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                               uint8_t** out, size_t* out_len, orc_stats* stats) {
-    return lcpcomp_compress(text, n, threshold, flatten, 0, out, out_len, stats);
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 0, 3, 0, out, out_len, stats);
 }
 /* LCPCompressor<ArithmeticCoder, ArraysComp, ...>::compress (BASELINE.json configs[2]) */
 int orc_lcpcomp_arith_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                                uint8_t** out, size_t* out_len, orc_stats* stats) {
-    return lcpcomp_compress(text, n, threshold, flatten, 1, out, out_len, stats);
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 1, 3, 0, out, out_len, stats);
 }
 /* lcpcomp(coder=ascii): the human-readable form of the same token stream */
 int orc_lcpcomp_ascii_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten,
                                uint8_t** out, size_t* out_len, orc_stats* stats) {
-    return lcpcomp_compress(text, n, threshold, flatten, 2, out, out_len, stats);
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 2, 3, 0, out, out_len, stats);
 }
 /* lcpcomp(coder=sle(kmer)): the coder of the reference's published lcpcomp runs (etc/compare-suites/default.suite:5) */
 int orc_lcpcomp_sle_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten, unsigned kmer,
                              uint8_t** out, size_t* out_len, orc_stats* stats) {
     if (kmer < 1 || kmer > 7) return -2;
-    g_sle_k = kmer;
-    const int rc = lcpcomp_compress(text, n, threshold, flatten, 3, out, out_len, stats);
-    g_sle_k = 3;
-    return rc;
+    return orc_lcpcomp_compress_any(text, n, threshold, flatten, 3, kmer, 0, out, out_len, stats);
 }
 static int lcpcomp_compress(const uint8_t* text, size_t n, uint32_t threshold, int flatten, int coder,
                             uint8_t** out, size_t* out_len, orc_stats* stats) {

@@ -121,6 +121,11 @@ int orc_lcpcomp_sle_compress(const uint8_t* text, size_t n, uint32_t threshold, 
 int orc_encode_sle(const uint8_t* text, size_t n, const orc_factor* f, size_t z, unsigned kmer,
                    uint8_t** out, size_t* out_len, orc_stats* st);
 int orc_lcpcomp_sle_decompress(const uint8_t* in, size_t in_len, unsigned kmer, uint8_t** out, size_t* out_len);
+/* lcpcomp(coder=C, comp=S) for every pair: coder 0 huff, 1 arithmetic, 2 ascii, 3 sle (kmer in 1..7, ignored otherwise);
+ * strategy 0 arrays, 1 plcppeaks, 2 max_lcp, 3 heap.  The functions above are this one with a fixed pair.  -2 for an unknown
+ * coder, strategy or kmer; -8 where the arithmetic coder would divide by 0 (*out is then set and must be freed). */
+int orc_lcpcomp_compress_any(const uint8_t* text, size_t n, uint32_t threshold, int flatten, int coder, unsigned kmer, int strategy,
+                             uint8_t** out, size_t* out_len, orc_stats* stats);
 /* LCPCompressor.hpp:140-150 / decode_text_internal :23-76 with HuffmanCoder::Decoder.
  * Produces the (still escaped, 0-terminated) text. *out malloc'd. */
 int orc_lcpcomp_huff_decompress(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len);

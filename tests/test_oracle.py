@@ -1,4 +1,6 @@
 """CPU tests: pin the oracle against the reference's own known-answer vectors and recorded outputs."""
+import random
+
 import numpy as np
 import pytest
 
@@ -323,3 +325,89 @@ def test_oracle_reproduces_committed_stage_fixture():
     assert set(want) == {name for name, _, _ in mg.INPUTS}
     for name, data, thr in mg.INPUTS:
         assert mg.stages(data, thr) == want[name], name
+
+
+_PAIR_COMPS = ("arrays", "plcppeaks", "max_lcp", "heap")
+_PAIR_CODERS = (("huff", 3), ("arith", 3), ("ascii", 3), ("sle", 1), ("sle", 3), ("sle", 4), ("sle", 7))
+
+
+def _pair_texts():
+    import tudocomp_amd as T
+    texts = [(name, O.escape(data)) for name, data in corpus.small_corpus()]
+    texts += [("english100k", O.escape(T.gen_english(100_000, 11).tobytes())),
+              ("dna100k", O.escape(T.gen_dna(100_000, 12).tobytes())),
+              ("planted100k", O.escape(corpus.planted(100_000, 4, random.Random(13), replen=2000)))]
+    return texts
+
+
+def _composed(text, comp, coder, kmer, threshold, flatten):
+    """the same pair from the oracle's stages: suffix array, strategy, sort, flatten, encoder"""
+    sa = O.suffix_array(text)
+    isa, phi, plcp, maxlcp = O.isa_phi_plcp(text, sa)
+    lcp = O.lcp_array(sa, plcp)
+    if comp == "plcppeaks":
+        peaks = plcp.copy()
+        peaks[-1] = phi[-1]                      # what PLCPFromPhi leaves in plcp[n-1]
+        f = O.plcp_peaks(sa, isa, peaks, threshold)
+    elif comp == "max_lcp":
+        f = O.max_lcp(sa, isa, lcp, maxlcp, threshold)
+    elif comp == "heap":
+        f = O.max_heap(sa, isa, lcp, threshold)
+    else:
+        f = O.arrays_comp(sa, isa, lcp, maxlcp, threshold)
+    f = O.sort_factors(f)
+    if flatten:
+        f = O.flatten(f)[0]
+    if coder == "sle":
+        return O.encode_sle(text, f, kmer)[0]
+    return {"huff": O.encode_huff, "arith": O.encode_arith, "ascii": O.encode_ascii}[coder](text, f)[0]
+
+
+def test_lcpcomp_compress_any_matches_fixed_pair_entries():
+    """O.lcpcomp_compress_any against the fixed-pair entries (every strategy with huff, arrays with every coder) on the small
+    corpus and three 100 KB texts at both flatten settings; on the larger texts also against the stages composed by hand, for
+    every strategy x coder pair.  Where the arithmetic coder divides by zero, every entry raises."""
+    fixed = {("arrays", "huff"): O.lcpcomp_huff_compress, ("plcppeaks", "huff"): O.lcpcomp_peaks_huff_compress,
+             ("max_lcp", "huff"): O.lcpcomp_maxlcp_huff_compress, ("heap", "huff"): O.lcpcomp_heap_huff_compress,
+             ("arrays", "arith"): O.lcpcomp_arith_compress, ("arrays", "ascii"): O.lcpcomp_ascii_compress}
+    composed = 0
+    for name, text in _pair_texts():
+        for fl in (0, 1):
+            thr = 1 + (len(text) + fl) % 5
+            for (comp, coder), fn in fixed.items():
+                try:
+                    want = fn(text, thr, fl)[0]
+                except RuntimeError:
+                    assert coder == "arith", (name, comp, coder)
+                    with pytest.raises(RuntimeError):
+                        O.lcpcomp_compress_any(text, thr, fl, coder, comp)
+                    continue
+                assert O.lcpcomp_compress_any(text, thr, fl, coder, comp)[0] == want, (name, comp, coder, thr, fl)
+            for k in (1, 3, 4, 7):
+                want = O.lcpcomp_sle_compress(text, thr, fl, k)[0]
+                assert O.lcpcomp_compress_any(text, thr, fl, "sle", "arrays", kmer=k)[0] == want, (name, k, thr, fl)
+            if len(text) < 50_000:
+                continue
+            for comp in _PAIR_COMPS:
+                for coder, k in _PAIR_CODERS:
+                    got = O.lcpcomp_compress_any(text, thr, fl, coder, comp, kmer=k)[0]
+                    assert got == _composed(text, comp, coder, k, thr, fl), (name, comp, coder, k, thr, fl)
+                    composed += 1
+    assert composed == 3 * 2 * len(_PAIR_COMPS) * len(_PAIR_CODERS)
+
+
+def test_lcpcomp_compress_any_rejects_what_the_reference_rejects():
+    """The arithmetic coder divides by zero when the sentinel is the only literal: every strategy raises, the other coders
+    do not; unknown names and kmer values outside 1..7 are refused."""
+    for comp in _PAIR_COMPS:
+        with pytest.raises(RuntimeError):
+            O.lcpcomp_compress_any(b"\0", 1, 1, "arith", comp)
+        for coder in ("huff", "ascii", "sle"):
+            assert O.lcpcomp_compress_any(b"\0", 1, 1, coder, comp)[0]
+    with pytest.raises(RuntimeError):
+        O.lcpcomp_arith_compress(b"\0", 1, 1)
+    for k in (0, 8):
+        with pytest.raises(RuntimeError):
+            O.lcpcomp_compress_any(b"abcabc\0", 2, 1, "sle", "arrays", kmer=k)
+    with pytest.raises(KeyError):
+        O.lcpcomp_compress_any(b"abcabc\0", 2, 1, "gamma", "arrays")

@@ -280,6 +280,7 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
     if (st) {
         st->factors = fz.factors; st->entries = fz.entries; st->pushes = fz.pushes;
         st->levels = fz.levels; st->mis_rounds = fz.rounds; st->small_levels = fz.small_levels; st->purges = fz.purges; st->window_pass = fz.window_pass; st->window_lcut = fz.window_lcut; st->eager_levels = fz.eager_levels; st->eager_phases = fz.eager_phases;
+        st->probes = fz.probes; st->max_push_targets = fz.max_push_targets;
         st->num_flattened = fl.num_flattened; st->max_depth_lb = fl.max_depth_lb; st->flatten_rounds = fl.rounds;
         if (ev) { ev->span(&st->ms_factorize, e0, e1); ev->span(&st->ms_flatten, e1, e2); }
     }
@@ -725,6 +726,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
     } else if (ho.into) {
         if (len > ho.cap) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
         const size_t done = c.d2h_done <= len ? c.d2h_done : 0;
+        if (stats) stats->d2h_early = done;
         HIP_TRY(hipMemcpyAsync(ho.into + done, d_out + done, len - done, hipMemcpyDeviceToHost, c.stream));
         if (done) c.wait_for(c.stream, c.copy_stream);                      // the front part travels on the copy stream
         const int e3 = ev.tick();

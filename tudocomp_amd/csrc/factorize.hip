@@ -1670,6 +1670,7 @@ void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi,
                         const u32 npush = h_sc.npush, nseg = h_sc.nseg;
                         if (npush) {
                             if (nseg > seg_cap) throw HipError{hipErrorUnknown, "factorize: too many push targets in one level", (int)__LINE__};
+                            st->max_push_targets = std::max(st->max_push_targets, nseg);
                             if (nseg <= SEG_INLINE) std::copy(h_sc.segs, h_sc.segs + nseg, h_segs.begin());
                             else if (cur_f.zc && nseg <= SMALL_M_SLIM)
                                 memcpy(h_segs.data(), c.zc_host + (size_t)(1 + cur_f.slot) * Ctx::ZC_WORDS + Ctx::ZC_SEG_OFF, (size_t)nseg * sizeof(PushSeg));   // published next to the scalars
@@ -1819,6 +1820,7 @@ void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi,
             c.read_n((const u32*)d_sc, (u32*)&h_sc, sizeof(LevelScalars) / sizeof(u32));   // scalars + inline segments: one sync
             const u32 nseg = h_sc.nseg;
             if (nseg > seg_cap) throw HipError{hipErrorUnknown, "factorize: too many push targets in one level", (int)__LINE__};
+            st->max_push_targets = std::max(st->max_push_targets, nseg);
             if (nseg <= SEG_INLINE) std::copy(h_sc.segs, h_sc.segs + nseg, h_segs.begin());
             else c.read_n(d_segs, h_segs.data(), nseg);
             std::sort(h_segs.begin(), h_segs.begin() + nseg, [](const PushSeg& a, const PushSeg& b) { return a.start < b.start; });
@@ -2257,6 +2259,7 @@ void factorize_max_lcp(Ctx& c, size_t n, u32* isa, const u32* phi, u32* plcp, u3
             c.read_n((const u32*)d_sc, (u32*)&h_sc, sizeof(LevelScalars) / sizeof(u32));
             const u32 nseg = h_sc.nseg;
             if (nseg > seg_cap) throw HipError{hipErrorUnknown, "max_lcp: too many push targets in one level", (int)__LINE__};
+            st->max_push_targets = std::max(st->max_push_targets, nseg);
             if (h_segs.size() < nseg) h_segs.resize(nseg);
             if (nseg > SEG_INLINE) c.read_n(d_segs, h_segs.data(), nseg);
             else for (u32 j = 0; j < nseg; ++j) h_segs[j] = h_sc.segs[j];

@@ -93,6 +93,7 @@ struct FactorizeStats { u64 factors = 0; u32 maxlcp = 0; u32 levels = 0; u32 rou
                         u32 window_pass = 0; /* 0 not used, 1 low levels done window-local, 2 window pass failed -> global loop */
                         u32 window_lcut = 0; /* highest level of the last window pass */
                         u32 probes = 0; /* skip-ahead probes over runs of erased levels */
+                        u32 max_push_targets = 0; /* most push-target levels of one level */
                         u32 eager_levels = 0, eager_phases = 0; /* levels inside one-launch runs of small levels (factorize_eager.hip), runs */ };
 
 // a8: compressors/lcpcomp/compress/ArraysComp.hpp:36-117 in position space.
