@@ -5,10 +5,15 @@ A "step" is one pass of the hot path over one batch of synthetic text: pinned ho
 ISA/Phi/PLCP -> ArraysComp factorization -> flatten -> host Huffman table -> bit-pack -> D2H -> compressed bytes in pinned
 host memory.  Both transfers are INSIDE the timed region; `value` = input bytes / wall time.
 
+A plain run does only what the headline needs: set up, W untimed + K timed steps, --dump-outputs, the JSON line.  Besides `value` and
+`ms_per_step` the line holds what the timed steps report themselves: "hbm_resident" = the same steps without the two transfers (device
+time of the same calls), "pipeline", "stages_ms" and "stats" of the last timed step.  --full adds everything else listed below: the CPU
+baseline, the extras, the comparisons with the oracle's streams, the profiled step (roofline + per-kernel table) and, for N > 1, the
+second exchange and the container check.  --no-cpu-baseline / --no-extra leave parts of that out again.
+
   N = 1 : the configuration the metric is quoted on: 2*10^9 B English-like text (SURVEY.md 8d generator, seed 42),
           threshold 2, flatten 1, through the product's entry point tdc_gpu_lcpcomp_compress_into.
-          Extra keys (never `value`): "hbm_resident" = the same steps without the two transfers (device time of the
-          same calls), "configs1_256MiB" = BASELINE.json configs[1] (256 MiB) through the same entry point,
+          Extra keys with --full (never `value`): "configs1_256MiB" = BASELINE.json configs[1] (256 MiB) through the same entry point,
           "configs2_dna_1e9" = BASELINE.json configs[2] (10^9 B DNA, LCPCompressor + ArithmeticCoder, threshold 5) through
           the same entry point, its stream checked against the CPU oracle on a 32 MiB DNA sample,
           "configs3_lz78" = BASELINE.json configs[3] on a 32 MiB sample (host-bound: the LZ78 parse runs on the host),
@@ -17,8 +22,9 @@ host memory.  Both transfers are INSIDE the timed region; `value` = input bytes 
           same full-size text (tests/golden/oracle_fullsize.json).
   N > 1 : BASELINE.json configs[4]: one process per GPU (torch.distributed, backend nccl = RCCL); every rank compresses
           its own 2*10^9 B shard (seed 42 + rank: weak scaling) exactly as in the N = 1 case (pinned host text, upload
-          overlapped with the first partition level) and keeps the stream on its GPU.  BOTH ways of putting the block
-          container together are timed, K steps each, in the same run:
+          overlapped with the first partition level) and keeps the stream on its GPU.  With --full BOTH ways of putting the block
+          container together are timed, K steps each, in the same run, and "container_ok" says whether the
+          container of the last step holds every rank's stream:
             "shared host memory" -- all-gather of the stream sizes, every rank downloads its stream to its offset of ONE
                 container that all ranks map (POSIX shared memory, page-locked): eight shards over eight host links at once;
             "rccl gather to rank 0" -- the collective north_star names: all-gather of the sizes, ONE group of point-to-point
@@ -27,12 +33,12 @@ host memory.  Both transfers are INSIDE the timed region; `value` = input bytes 
           as "rccl_gather": {"ms_per_step", "value"}; where the shared segment cannot be set up the RCCL gather is `value`.
           value = bytes of all ranks / max-over-ranks time.
           Started WITHOUT torchrun's environment (`python bench.py --gpus N`), the process launches its own N ranks: it runs the
-          CPU baseline, then starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (it has
-          not touched the GPU and never exec()s), relays rank 0's JSON line and the exit code.
+          CPU baseline (--full), then starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (it
+          has not touched the GPU and never exec()s), relays rank 0's JSON line and the exit code.
           TDC_BENCH_BACKEND=gloo rehearses the N > 1 path with several ranks on ONE GPU (collectives on CPU tensors).
 
-After the timed steps ONE more step runs with per-kernel HIP-event timing switched on (untimed) -- the roofline object and
-the per-kernel table come from it.  --dump-outputs DIR writes the stream of the last timed step (N > 1: rank 0's block container) as
+With --full, after the timed steps ONE more step runs with per-kernel HIP-event timing switched on (untimed) -- the roofline object
+and the per-kernel table come from it.  --dump-outputs DIR writes the stream of the last timed step (N > 1: rank 0's block container) as
 float32 / float64 .npy files under DIR before that (dump_stream: whole up to 8 MiB, else a seeded sample; at most ~50 MB), so that the
 outputs of two builds can be compared: with the same arguments the input text is the same in every run.  Prints ONE JSON line (rank 0).  PyTorch is used for torch.distributed and the
 multi-GPU staging buffers only.
@@ -62,11 +68,14 @@ def parse_args():
     ap.add_argument("--size", type=int, default=2_000_000_000, help="input bytes per GPU (default 2*10^9: the metric's text / one shard of configs[4])")
     ap.add_argument("--threshold", type=int, default=2)
     ap.add_argument("--gen", default="english", choices=["english", "dna"])
-    ap.add_argument("--cpu-sample", type=int, default=1 << 26, help="bytes of the workload the single-core CPU baseline is timed on")
-    ap.add_argument("--cpu-multi-sample", type=int, default=1 << 25, help="bytes per process of the multi-core CPU figure")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra figures (256 MiB English, 10^9 B DNA)")
-    ap.add_argument("--dna-sample", type=int, default=1 << 25, help="bytes of DNA text the oracle compresses for the configs[2] check")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baseline, extra figures, streams against the "
+                         "oracle, profiled step (roofline, kernel table), N > 1: the RCCL gather beside the shared container")
+    ap.add_argument("--cpu-sample", type=int, default=1 << 26, help="bytes of the workload the single-core CPU baseline is timed on (--full)")
+    ap.add_argument("--cpu-multi-sample", type=int, default=1 << 25, help="bytes per process of the multi-core CPU figure (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra figures (256 MiB English, 10^9 B DNA, ...)")
+    ap.add_argument("--dna-sample", type=int, default=1 << 25, help="bytes of DNA text the oracle compresses for the configs[2] check (--full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the stream of the last timed step (N > 1: rank 0's block container) as DIR/<name>.npy")
     ap.add_argument("--cpu-result", default=None, help=argparse.SUPPRESS)      # (N > 1 self-launch: the parent's CPU baseline, a JSON file)
@@ -203,13 +212,43 @@ def matches_golden(name, stream_view):
     return bool(len(stream_view) == g["size"] and hashlib.sha256(stream_view).hexdigest() == g["sha256"])
 
 
+def roofline(prof, st_prof, N):
+    """the roofline object of the profiled step (--full): the kernel class with the largest summed time against the HBM peak; its HBM
+    traffic per launch from the committed PMC summary of the same workload, where there is one"""
+    DOMINANT = max(prof, key=lambda name: prof[name]["ms"]) if prof else None
+    k = prof.get(DOMINANT, {"ms": 0.0, "launches": 0, "bytes": 0})
+    if not k["launches"]:
+        return None
+    achieved = k["bytes"] / (k["ms"] * 1e-3) / 1e9
+    traffic, traffic_src = None, None
+    pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
+    if os.path.exists(pmc):
+        try:
+            j = json.load(open(pmc))
+            ent = j.get("kernels", {}).get(DOMINANT) if j.get("workload_bytes") == N else None
+            if ent is None and j.get("workload_bytes") == N and j.get("kernel") == DOMINANT:
+                ent = j
+            if ent is not None:
+                traffic = ent.get("hbm_bytes_per_launch")
+                traffic_src = "static: %s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this workload, not measured in this run)" % j.get("source", "profiles/pmc_summary.json")
+        except Exception:
+            traffic = None
+    return {"bound": "hbm", "kernel": DOMINANT, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+            "launches_per_step": k["launches"],
+            "avg_launch_ms": round(k["ms"] / k["launches"], 4),
+            "algorithmic_bytes_per_launch": round(k["bytes"] / k["launches"]),
+            "share_of_device_time": round(k["ms"] / st_prof["ms_total"], 3) if st_prof["ms_total"] else None,
+            "timing": "HIP events on the library's stream around every launch, one profiled step after the timed region"}
+
+
 def launch_ranks(args):
-    """`python bench.py --gpus N` without torchrun's environment: this process -- which has NOT touched the GPU -- runs the CPU baseline and
-    starts the N ranks as a fresh child process (never exec), then relays rank 0's JSON line and the child's exit code."""
+    """`python bench.py --gpus N` without torchrun's environment: this process -- which has NOT touched the GPU -- runs the CPU baseline
+    (--full) and starts the N ranks as a fresh child process (never exec), then relays rank 0's JSON line and the child's exit code."""
     import socket
     import tempfile
     cpu_file = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         seed0 = 42 if args.gen == "english" else 7
         cpu_res, cpu_ref, dna_ref = cpu_baseline(args, seed0)
         fd, cpu_file = tempfile.mkstemp(prefix="tdc_bench_cpu_", suffix=".json")
@@ -222,6 +261,8 @@ def launch_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--size", str(args.size),
            "--threshold", str(args.threshold), "--gen", args.gen, "--no-cpu-baseline"]
+    if args.full:
+        cmd.append("--full")
     if args.no_extra:
         cmd.append("--no-extra")
     if args.dump_outputs:
@@ -296,7 +337,7 @@ def main():
                 cpu_res, cpu_ref, dna_ref = j["cpu_res"], j["cpu_ref"], j["dna_ref"]
             except (OSError, ValueError, KeyError):
                 cpu_res = None
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             cpu_res, cpu_ref, dna_ref = cpu_baseline(args, seed0)     # before any GPU initialisation in this process
 
     import hashlib
@@ -368,18 +409,20 @@ def main():
         if not shared_ok and shared is not None:
             shared.close(T.host_unregister)
             shared = None
-        # (2) staging for the RCCL gather to rank 0: the kept stream is copied into a torch tensor the collective can send
-        ok = True
-        try:
-            if backend == "nccl":
-                d_out = torch.empty(out_cap // 2, dtype=torch.uint8, device=device)
-            else:                                         # gloo rehearsal: the "gather" runs on CPU tensors
-                h_stage = torch.empty(out_cap // 2, dtype=torch.uint8)
-            if rank == 0:
-                h_container = torch.empty(cont_cap, dtype=torch.uint8).pin_memory()
-        except Exception:
-            ok = False
-        gather_ok = all_ok(ok) and not os.environ.get("TDC_BENCH_NO_RCCL_GATHER")
+        # (2) staging for the RCCL gather to rank 0: the kept stream is copied into a torch tensor the collective can send.  Needed where
+        #     the gather is `value` (no shared container, or TDC_BENCH_RCCL_GATHER) or is timed beside it (--full); the same on every rank.
+        if args.full or not shared_ok or os.environ.get("TDC_BENCH_RCCL_GATHER"):
+            ok = True
+            try:
+                if backend == "nccl":
+                    d_out = torch.empty(out_cap // 2, dtype=torch.uint8, device=device)
+                else:                                     # gloo rehearsal: the "gather" runs on CPU tensors
+                    h_stage = torch.empty(out_cap // 2, dtype=torch.uint8)
+                if rank == 0:
+                    h_container = torch.empty(cont_cap, dtype=torch.uint8).pin_memory()
+            except Exception:
+                ok = False
+            gather_ok = all_ok(ok) and not os.environ.get("TDC_BENCH_NO_RCCL_GATHER")
         if os.environ.get("TDC_BENCH_RCCL_GATHER") and gather_ok and shared is not None:     # (the gather as `value`: tests)
             shared.close(T.host_unregister)
             shared = None
@@ -483,6 +526,7 @@ def main():
         bitmap = torch.tensor([1 << rank], dtype=torch.int64, device=coll_device)
         dist.all_reduce(bitmap, op=dist.ReduceOp.SUM)
         ranks_seen = bin(int(bitmap.item())).count("1")
+    if world > 1 and args.full:
         if shared is not None:
             container_ok = check_container(out_len, sizes, lambda: shared.blob(sizes))
             if gather_ok:                                 # the collective north_star names, timed in the same run
@@ -495,41 +539,18 @@ def main():
         else:
             container_ok = check_container(out_len, sizes, lambda: bytes(h_container[:payload_offsets(sizes)[1]].numpy()))
 
-    # ---- one more step with per-kernel timing (untimed): roofline + kernel table ----------------------------------------------
-    ctx.set_profiling(True)
-    ctx.reset_profile()
-    _, st_prof, _ = step()
-    prof = ctx.kernel_profile()
-    ctx.set_profiling(False)
+    prof = st_prof = None
+    if args.full:
+        # ---- one more step with per-kernel timing (untimed): roofline + kernel table ------------------------------------------
+        ctx.set_profiling(True)
+        ctx.reset_profile()
+        _, st_prof, _ = step()
+        prof = ctx.kernel_profile()
+        ctx.set_profiling(False)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = world * N / 1e6 / (dt / args.steps)
-        DOMINANT = max(prof, key=lambda name: prof[name]["ms"]) if prof else None
-        k = prof.get(DOMINANT, {"ms": 0.0, "launches": 0, "bytes": 0})
-        roof = None
-        if k["launches"]:
-            achieved = k["bytes"] / (k["ms"] * 1e-3) / 1e9
-            traffic, traffic_src = None, None
-            pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
-            if os.path.exists(pmc):
-                try:
-                    j = json.load(open(pmc))
-                    ent = j.get("kernels", {}).get(DOMINANT) if j.get("workload_bytes") == N else None
-                    if ent is None and j.get("workload_bytes") == N and j.get("kernel") == DOMINANT:
-                        ent = j
-                    if ent is not None:
-                        traffic = ent.get("hbm_bytes_per_launch")
-                        traffic_src = "static: %s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this workload, not measured in this run)" % j.get("source", "profiles/pmc_summary.json")
-                except Exception:
-                    traffic = None
-            roof = {"bound": "hbm", "kernel": DOMINANT, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "launches_per_step": k["launches"],
-                    "avg_launch_ms": round(k["ms"] / k["launches"], 4),
-                    "algorithmic_bytes_per_launch": round(k["bytes"] / k["launches"]),
-                    "share_of_device_time": round(k["ms"] / st_prof["ms_total"], 3) if st_prof["ms_total"] else None,
-                    "timing": "HIP events on the library's stream around every launch, one profiled step after the timed region"}
         c_ratio = out_len / N
         z = st["factors"]
         b_alg = 44 + c_ratio + 48 * z / N
@@ -554,20 +575,21 @@ def main():
             "dtype": "u32", "data": "synthetic",
             "config": {"workload": workload, "bytes_per_gpu": N,
                        "parallelism": ("independent shards x%d, %s" % (world, exchange)) if world > 1 else "single GPU"},
-            "roofline": roof,
             "hbm_resident": {"value": round(N / 1e6 / (kern_ms * 1e-3), 2), "unit": "MB/s", "ms_per_step": round(kern_ms, 3),
                              "note": "same steps, device time without the H2D / D2H transfers (per GPU)"},
             "pipeline": {"B_alg_bytes_per_input_byte": round(b_alg, 2), "achieved_GBs": round(b_alg * N / (kern_ms * 1e-3) / 1e9, 1),
                          "frac_of_hbm_peak": round(b_alg * N / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
             "stages_ms": {k2[3:]: round(v, 2) for k2, v in st.items() if k2.startswith("ms_")},
             "stats": {k2: st[k2] for k2 in STAT_KEYS},
-            "kernels": {name: {"ms_per_step": round(p["ms"], 3), "launches_per_step": p["launches"],
-                               "algorithmic_GBs": round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1) if p["ms"] > 0 else None}
-                        for name, p in prof.items() if p["launches"]},
         }
+        if prof is not None:
+            line["roofline"] = roofline(prof, st_prof, N)
+            line["kernels"] = {name: {"ms_per_step": round(p["ms"], 3), "launches_per_step": p["launches"],
+                                      "algorithmic_GBs": round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1) if p["ms"] > 0 else None}
+                               for name, p in prof.items() if p["launches"]}
         if dumped is not None:
             line["dumped_outputs"] = dumped
-        if world == 1 and args.gen == "english" and args.threshold == 2 and N == 2_000_000_000:
+        if args.full and world == 1 and args.gen == "english" and args.threshold == 2 and N == 2_000_000_000:
             # byte for byte the oracle's stream of the metric's text: size + SHA-256 against the committed full-size golden
             line["stream_matches_golden"] = matches_golden("english_2e9", h_out.a[:out_len])
         if world > 1:
@@ -587,7 +609,7 @@ def main():
             gpu_prefix, _ = ctx.lcpcomp_compress(sample, args.threshold, 1)
             cpu_res["bit_exact_vs_gpu_on_sample"] = bool(len(gpu_prefix) == want_len and hashlib.sha256(gpu_prefix).hexdigest() == want_sha)
             line["cpu_baseline"] = cpu_res
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             # the stream of the timed steps back to the text (tdc_gpu_lcpcomp_decompress_into, stream and text in pinned host
             # memory: H2D of the stream, device parse, references, D2H of the text); the result is compared with the input text
             try:
@@ -606,7 +628,7 @@ def main():
                 h_stream.free(); h_back.free()
             except Exception as e:                       # (an extra never costs the line: e.g. no page-locked memory left for its two buffers)
                 line["decompress"] = {"error": str(e)}
-        if world == 1 and not args.no_extra and N > (1 << 28):
+        if world == 1 and args.full and not args.no_extra and N > (1 << 28):
             m = 1 << 28
             h_text.a[m] = 0                               # the first 256 MiB of the generator's output ARE its 256 MiB text
             ts = []
@@ -620,7 +642,7 @@ def main():
                                        "note": "BASELINE configs[1] through the same end-to-end entry point, 3 steps after 1 warm-up"}
             if args.gen == "english" and args.threshold == 2:
                 line["configs1_256MiB"]["stream_matches_golden"] = matches_golden("english_256MiB", h_out.a[:ol2])
-        if world == 1 and not args.no_extra and args.gen == "english" and N > (1 << 30):
+        if world == 1 and args.full and not args.no_extra and args.gen == "english" and N > (1 << 30):
             # BASELINE.json configs[2]: 10^9 B DNA (sigma = 4), LCPCompressor + ArithmeticCoder, threshold 5 (the compressor's default)
             md = 1_000_000_000
             T.gen_dna(md, 7, out=h_text.a)

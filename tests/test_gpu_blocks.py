@@ -160,15 +160,15 @@ def test_blocks_container_of_several_megabytes(gpu_ctx):
 
 
 def test_bench_launches_its_own_ranks_two_rank_rehearsal(gpu_ctx):
-    """`python bench.py --gpus 2` WITHOUT torchrun's environment: the parent runs the CPU baseline and starts the two ranks as a child
-    process (torch.distributed.run); both ranks share this box's one GPU, the collectives run on the gloo backend.  The line must carry
-    both exchange variants (shared host memory = value, the gather to rank 0 beside it), the roofline object and the CPU baseline."""
+    """`python bench.py --gpus 2 --full` WITHOUT torchrun's environment: the parent runs the CPU baseline and starts the two ranks as a
+    child process (torch.distributed.run); both ranks share this box's one GPU, the collectives run on the gloo backend.  The line must
+    carry both exchange variants (shared host memory = value, the gather to rank 0 beside it), the roofline object and the CPU baseline."""
     import json
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["TDC_BENCH_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", str(1 << 24), "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", str(1 << 22), "--cpu-multi-sample", str(1 << 20), "--no-extra"],
+                        "--full", "--cpu-sample", str(1 << 22), "--cpu-multi-sample", str(1 << 20), "--no-extra"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

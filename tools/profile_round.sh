@@ -8,7 +8,7 @@ TAG=${1:-x}
 R=$PWD
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
-python3 bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $OUT/stats_bench.json 2> $OUT/stats.err
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra > /dev/null 2> $OUT/pmc_fetch.err
