@@ -248,6 +248,23 @@ int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, siz
  * general marking also for streams of short tokens -- tests), 0 if on the host. */
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx);
 
+/* ---- LZ78Compressor::decompress (compressors/LZ78Compressor.hpp:142-160 -> lz78::Decompressor :16-37, EliasGammaCoder::Decoder
+ * coders/EliasGammaCoder.hpp:31-42) for streams of tdc_gpu_lz78_compress or the reference's lz78(coder=gamma).  Parsed ON THE DEVICE
+ * (where the pair that starts at a bit position ends is evaluated for every bit position, the real pair starts
+ * are the orbit of bit 0), phrase lengths by pointer jumping over the parent ids, the text by the reference resolver of the lcpcomp
+ * decoder.  The reference walks every phrase's parent chain one byte at a time instead.  coder must be TDC_GPU_CODER_GAMMA
+ * (else TDC_GPU_ERR_UNSUPPORTED).  *out (malloc'd, free with tdc_gpu_free) receives the text; the empty stream decodes to 0 bytes.
+ * phrases / rounds (nullable): number of (id, char) pairs / pointer-jumping rounds (phrase lengths + text references).
+ * Malformed input -- a pair cut off by the end of the stream, an id field wider than 32 bits, a char field wider than 64 bits, the
+ * k-th pair (0-based) naming a phrase id > k --: TDC_GPU_ERR_ARG.  A text of more than 2^32 - 2 bytes: TDC_GPU_ERR_TOO_LARGE (found
+ * before anything of the text's size is allocated). */
+int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                            uint64_t* phrases, uint32_t* rounds);
+/* The same into the CALLER's buffer `out` of out_cap bytes (pinned host memory -- tdc_gpu_host_alloc -- receives the text at the host
+ * link's rate).  TDC_GPU_ERR_OOM if the text does not fit; *out_len then holds the required size. */
+int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, uint64_t* phrases, uint32_t* rounds);
+
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,
                         const uint32_t* len, size_t z, uint8_t** out, size_t* out_len);

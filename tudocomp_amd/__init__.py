@@ -370,6 +370,31 @@ class Context:
                                                             ctypes.byref(f), ctypes.byref(r)))
         return n.value, {"factors": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
 
+    def lz78_decompress(self, stream, coder=CODER_GAMMA):
+        """LZ78Compressor<EliasGammaCoder>::decompress, parsed on the device: returns the text and {"phrases", "rounds"}."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_lz78_decompress(self._h, _ptr(a), len(a), coder, ctypes.byref(p), ctypes.byref(n),
+                                                    ctypes.byref(f), ctypes.byref(r)))
+        return self._take(p, n.value), {"phrases": f.value, "rounds": r.value}
+
+    def lz78_decompress_into(self, stream, out, coder=CODER_GAMMA):
+        """lz78_decompress into a caller-owned buffer (a PinnedBuffer or a writable uint8 array; `stream` may be a PinnedBuffer too):
+        returns (text length, {"phrases", "rounds"}).  A buffer that is too small raises TdcGpuError (status -5) whose `required`
+        is the text length."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n = ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.tdc_gpu_lz78_decompress_into(self._h, _ptr(a), len(a), coder, _ptr(oa), oa.size, ctypes.byref(n),
+                                                  ctypes.byref(f), ctypes.byref(r))
+        if rc:
+            err = TdcGpuError(rc, self._L.tdc_gpu_last_error(self._h).decode())
+            err.required = n.value if rc == -5 else None
+            raise err
+        return n.value, {"phrases": f.value, "rounds": r.value}
+
     def blocks_decompress(self, blob, coder=CODER_HUFF):
         """inverse of blocks_compress on this context's device: the concatenated raw bytes"""
         a = _u8(blob)
@@ -465,6 +490,11 @@ class LZ78Compressor:
         out, st = self.ctx.lz78_compress(data)
         self.last_stats = st
         return out
+
+    def decompress(self, stream):
+        """LZ78Compressor::decompress (:142-160): the stream is parsed and the phrases are expanded on the device."""
+        text, _ = self.ctx.lz78_decompress(stream)
+        return text
 
 
 class LZSSLCPCompressor:

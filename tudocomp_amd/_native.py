@@ -27,6 +27,7 @@ SYMBOLS = [
     "tdc_gpu_ctx_set_option", "tdc_gpu_option_count", "tdc_gpu_option_name", "tdc_escape", "tdc_unescape", "tdc_lz78_factors", "tdc_huffman_table", "tdc_huffman_selfcheck", "tdc_gpu_blocks_count", "tdc_gpu_blocks_compress", "tdc_gpu_blocks_decompress", "tdc_gpu_device_count", "tdc_gen_english", "tdc_gen_dna",
     "tdc_gpu_arena_bytes", "tdc_gpu_device_memory",
     "tdc_gpu_lcpcomp_compress_keep", "tdc_gpu_stream_fetch", "tdc_gpu_stream_fetch_dev", "tdc_gpu_host_register", "tdc_gpu_host_unregister",
+    "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
 ]
 
 
@@ -114,6 +115,8 @@ def load():
     L.tdc_gpu_flatten.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.tdc_gpu_encode_huff.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]
     L.tdc_gpu_lcpcomp_decompress.argtypes = [vp, vp, sz, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lz78_decompress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lz78_decompress_into.argtypes = [vp, vp, sz, i32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lcpcomp_decompress_coder.argtypes = [vp, vp, sz, ctypes.c_int, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_encode_arith.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]
     L.tdc_gpu_encode_ascii.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]

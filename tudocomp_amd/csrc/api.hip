@@ -1111,6 +1111,51 @@ int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, siz
     });
 }
 
+namespace {
+void lz78_decompress_common(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, DecodeOut& o, size_t* out_len, uint64_t* phrases,
+                            uint32_t* rounds) {
+    if (coder != TDC_GPU_CODER_GAMMA) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lz78: only coder=gamma is built"};
+    if ((!stream && len) || !out_len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    DecodeStats ds;
+    size_t n = 0, need = 0;
+    try { n = decode_lz78_gamma(ctx->c, stream, len, o, &need, &ds); }
+    catch (const StreamFormatError& e) { free(o.owned); o.owned = nullptr; throw ArgError{TDC_GPU_ERR_ARG, e.what}; }
+    catch (const DecodeTooLarge&) { free(o.owned); o.owned = nullptr; throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lz78: the stream decodes to more than 2^32 - 2 bytes"}; }
+    catch (const HipError& e) {
+        free(o.owned); o.owned = nullptr;
+        if (e.e == hipErrorOutOfMemory && o.into && need > o.cap) {
+            *out_len = need;
+            throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+        }
+        throw;
+    }
+    catch (...) { free(o.owned); o.owned = nullptr; throw; }
+    *out_len = n;
+    if (phrases) *phrases = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+}
+}  // namespace
+
+int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                            uint64_t* phrases, uint32_t* rounds) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+        DecodeOut o;
+        lz78_decompress_common(ctx, stream, len, coder, o, out_len, phrases, rounds);
+        *out = o.owned;
+    });
+}
+
+int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, uint64_t* phrases, uint32_t* rounds) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        DecodeOut o;
+        o.into = out; o.cap = out_cap;
+        lz78_decompress_common(ctx, stream, len, coder, o, out_len, phrases, rounds);
+    });
+}
+
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx) { return ctx ? ctx->last_decode_device : 0; }
 
 static int encode_entry(tdc_gpu_ctx* ctx, int coder, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,

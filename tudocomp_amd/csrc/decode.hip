@@ -14,6 +14,7 @@
 // format: LZSSLCPCompressor.hpp:125-130).
 #include "stages.hpp"
 #include "prim.hpp"
+#include "decode.hpp"
 
 #include <chrono>
 #include <new>
@@ -27,52 +28,16 @@ namespace {
 
 typedef StreamFormatError StreamError;
 
-// MSB-first reader over the reference's bit stream incl. its terminator rule (io/BitIStream.hpp:27-63, :191-193):
-// the low 3 bits of the last byte give the number of valid bits of the final data byte (6 and 7 live in an extra byte).
-struct FastBits {
-    const u8* p;
-    size_t nbytes;
-    u64 total = 0, pos = 0;
-    FastBits(const u8* in, size_t n) : p(in), nbytes(n) {
-        if (n == 0) return;
-        const unsigned fb = in[n - 1] & 7u;
-        if (fb >= 6) { if (n < 2) throw StreamError{"truncated stream"}; total = 8ull * (n - 2) + fb; }
-        else total = 8ull * (n - 1) + fb;
-    }
-    bool eof() const { return pos >= total; }
-    // next 57 bits, left-aligned in the result's top bits (zeros beyond the end, like BitIStream::read_bit at eof)
-    u64 peek() const {
-        const size_t byte = (size_t)(pos >> 3);
-        u64 w = 0;
-        if (byte + 8 <= nbytes) { u64 t; memcpy(&t, p + byte, 8); w = __builtin_bswap64(t); }
-        else for (size_t i = 0; i < 8; ++i) w = (w << 8) | (byte + i < nbytes ? p[byte + i] : 0);
-        w <<= (pos & 7);
-        if (pos + 57 > total) {                               // mask the bits behind the end of the stream
-            const u64 valid = total > pos ? total - pos : 0;
-            w = valid == 0 ? 0 : (w & (~0ull << (64 - valid)));
-        }
-        return w;
-    }
-    u64 read(unsigned bits) {                                 // bits <= 57
-        if (bits == 0) return 0;
-        const u64 v = peek() >> (64 - bits);
-        pos += bits;
-        return v;
-    }
-    u64 read_compressed_int() {                               // io/BitIStream.hpp:174-188, 7-bit groups
-        u64 v = 0; unsigned i = 0; bool more;
-        do { more = read(1) != 0; v |= read(7) << (7 * i++); } while (more && i < 10);
-        return v;
-    }
-};
-
+// G work-items per factor (G divides the workgroup size, so a thread keeps its sub-lane over the grid-stride loop)
 __global__ void ref_scatter_kernel(const u32* __restrict__ pos, const u32* __restrict__ src, const u32* __restrict__ len, size_t z,
                                    int G, u32* __restrict__ ref) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const size_t items = z * (size_t)G, stride = (size_t)gridDim.x * blockDim.x;
     const u32 sub = threadIdx.x % G;
-    if (i >= z) return;
-    const u32 p = pos[i], s = src[i], l = len[i];
-    for (u32 j = sub; j < l; j += G) ref[p + j] = s + j;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < items; t += stride) {
+        const size_t i = t / G;
+        const u32 p = pos[i], s = src[i], l = len[i];
+        for (u32 j = sub; j < l; j += G) ref[p + j] = s + j;
+    }
 }
 
 // one round of in-place pointer jumping: a position follows its chain for up to HOPS references and stops early at a literal
@@ -138,10 +103,11 @@ __global__ __launch_bounds__(256) void ref_jump_done_kernel(u32* ref, size_t n, 
 }
 
 __global__ void ref_copy_kernel(const u32* __restrict__ ref, size_t a, size_t n, u8* text) {      // positions [a, n)
-    const size_t p = a + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const u32 q = ref[p];
-    if (q != NONE32) text[p] = text[q];          // q is a literal position: never written by this kernel
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = a + (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        const u32 q = ref[p];
+        if (q != NONE32) text[p] = text[q];      // q is a literal position: never written by this kernel
+    }
 }
 
 constexpr unsigned LUT_BITS = 12;
@@ -171,36 +137,6 @@ static_assert(sizeof(DevTab) % 4 == 0, "copied word by word");
 struct ParseParams { u64 total, n, flen_min; u32 W, lbits, dbits, fdist_max; };
 constexpr u64 DEC_MAX_RUN = 512;            // longest literal run (fdist_max) the device parse takes
 constexpr u32 DEC_TILE = 32768;             // bit positions per workgroup of the next() pass
-constexpr size_t DEC_SEG = (size_t)1 << 30; // bit positions per segment of the chain marking
-
-// 64 stream bits from absolute bit position x on (MSB first), zeros behind `total` (BitIStream reads zeros at eof).  `words` are the
-// stream's 32-bit words, byte-swapped so that bit 31 of word k is stream bit 32 k; word index kb is words[0].
-struct BitWin {
-    const u32* words; u64 kb; u64 total;
-    __device__ __forceinline__ u64 peek(u64 x) const {
-        if (x >= total) return 0ull;
-        const u64 k = (x >> 5) - kb;
-        const u32 sh = (u32)x & 31u;
-        const u64 hi = ((u64)words[k] << 32) | words[k + 1];
-        u64 w = sh ? (hi << sh) | (u64)(words[k + 2] >> (32 - sh)) : hi;
-        if (x + 64 > total) w &= ~0ull << (64 - (total - x));
-        return w;
-    }
-};
-// the same over the stream in global memory (bytes; the buffer is padded with 16 zero bytes)
-struct BitWinG {
-    const u32* s32; u64 total;
-    __device__ __forceinline__ u64 peek(u64 x) const {
-        if (x >= total) return 0ull;
-        const u64 k = x >> 5;
-        const u32 sh = (u32)x & 31u;
-        const u32 a = __builtin_bswap32(s32[k]), b = __builtin_bswap32(s32[k + 1]), c = __builtin_bswap32(s32[k + 2]);
-        const u64 hi = ((u64)a << 32) | b;
-        u64 w = sh ? (hi << sh) | (u64)(c >> (32 - sh)) : hi;
-        if (x + 64 > total) w &= ~0ull << (64 - (total - x));
-        return w;
-    }
-};
 
 // huffman_decode (HuffmanCoder.hpp:377-397) on a 64-bit window: code length (0: no code of the table) and symbol
 __device__ __forceinline__ u32 dec_code(const DevTab* T, u64 w, u32& sym) {
@@ -689,7 +625,7 @@ static bool host_pinned(const void* p) {
 
 // where the decoded text goes: the caller's buffer, or a buffer allocated here (2 MiB aligned, transparent huge pages asked for: a
 // 256 MiB text otherwise pays 65 536 page faults in front of the download) that the caller releases with free()
-static u8* decode_dest(DecodeOut& o, size_t n) {
+u8* decode_dest(DecodeOut& o, size_t n) {
     if (o.into) {
         if (n > o.cap) throw HipError{hipErrorOutOfMemory, "decompress: output buffer too small", (int)__LINE__};
         return o.into;
@@ -707,7 +643,7 @@ static u8* decode_dest(DecodeOut& o, size_t n) {
 
 // Resolves the reference forest of n text positions on the device (d_text holds the literals at their positions, the factor list is
 // on the device as well) and downloads the text.
-static void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
+void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
                                  u32* d_changed, DecodeOut& out, DecodeStats* st) {
     hipStream_t s = c.stream;
     const bool dlog = c.dec_log != 0;
@@ -721,7 +657,7 @@ static void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const
     };
     fill_u32(c, d_ref, n, NONE32);
     const int G = (z * 64 > n) ? 8 : 64;
-    ref_scatter_kernel<<<cdiv(z * G, 256), 256, 0, s>>>(d_pos, d_src, d_len, z, G, d_ref);
+    ref_scatter_kernel<<<dec_grid(z * G), 256, 0, s>>>(d_pos, d_src, d_len, z, G, d_ref);
     LAUNCH_CHECK();
     tick("fill + reference scatter");
     unsigned g = cdiv(n, 256 * 8); if (g > 16384) g = 16384;
@@ -749,7 +685,7 @@ static void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const
         // positions only, wherever they are: the chunks do not depend on one another; the call waits for the last copy on its way out)
         for (size_t a = 0; a < n; a += CH) {
             const size_t b = std::min(n, a + CH);
-            ref_copy_kernel<<<cdiv(b - a, 256), 256, 0, s>>>(d_ref, a, b, d_text);
+            ref_copy_kernel<<<dec_grid(b - a), 256, 0, s>>>(d_ref, a, b, d_text);
             LAUNCH_CHECK();
             c.wait_for(c.copy_stream, s);
             HIP_TRY(hipMemcpyAsync(dst + a, d_text + a, b - a, hipMemcpyDeviceToHost, c.copy_stream));
@@ -757,7 +693,7 @@ static void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const
         HIP_TRY(hipStreamSynchronize(s));
         return;
     }
-    ref_copy_kernel<<<cdiv(n, 256), 256, 0, s>>>(d_ref, 0, n, d_text);
+    ref_copy_kernel<<<dec_grid(n), 256, 0, s>>>(d_ref, 0, n, d_text);
     LAUNCH_CHECK();
     tick("copy pass");
     HIP_TRY(hipMemcpyAsync(dst, d_text, n, hipMemcpyDeviceToHost, s));

@@ -1,0 +1,97 @@
+// decode.hpp -- pieces of the lcpcomp decoder (decode.hip) that the LZ78 decoder (lz78_decode.hip) shares: the MSB-first bit
+// readers with the reference's terminator rule, and the device reference resolver behind both parses.
+#pragma once
+#include "stages.hpp"
+
+#include <algorithm>
+
+namespace tdc {
+
+constexpr size_t DEC_SEG = (size_t)1 << 30; // bit positions per segment of the chain marking (option dec_seg overrides it)
+
+// Workgroups (of 256 threads) of a one-dimensional launch over `items` work-items, for kernels that loop with a grid stride: at most
+// DEC_MAX_BLOCKS, so that the dispatch grid (work-items, a 32-bit field) stays below 2^32 for every size the decoders take -- texts of up
+// to 2^32 - 2 bytes, factor lists of up to 64 work-items per factor.  Launches that fit keep their one-item-per-thread shape.
+constexpr unsigned DEC_MAX_BLOCKS = (1u << 24) - 1;
+static_assert((unsigned long long)DEC_MAX_BLOCKS * 256ull < (1ull << 32), "dispatch grid must stay below 2^32 work-items");
+inline unsigned dec_grid(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, DEC_MAX_BLOCKS); }
+
+// MSB-first reader over the reference's bit stream incl. its terminator rule (io/BitIStream.hpp:27-63, :191-193):
+// the low 3 bits of the last byte give the number of valid bits of the final data byte (6 and 7 live in an extra byte).
+struct FastBits {
+    const u8* p;
+    size_t nbytes;
+    u64 total = 0, pos = 0;
+    FastBits(const u8* in, size_t n) : p(in), nbytes(n) {
+        if (n == 0) return;
+        const unsigned fb = in[n - 1] & 7u;
+        if (fb >= 6) { if (n < 2) throw StreamFormatError{"truncated stream"}; total = 8ull * (n - 2) + fb; }
+        else total = 8ull * (n - 1) + fb;
+    }
+    bool eof() const { return pos >= total; }
+    // next 57 bits, left-aligned in the result's top bits (zeros beyond the end, like BitIStream::read_bit at eof)
+    u64 peek() const {
+        const size_t byte = (size_t)(pos >> 3);
+        u64 w = 0;
+        if (byte + 8 <= nbytes) { u64 t; memcpy(&t, p + byte, 8); w = __builtin_bswap64(t); }
+        else for (size_t i = 0; i < 8; ++i) w = (w << 8) | (byte + i < nbytes ? p[byte + i] : 0);
+        w <<= (pos & 7);
+        if (pos + 57 > total) {                               // mask the bits behind the end of the stream
+            const u64 valid = total > pos ? total - pos : 0;
+            w = valid == 0 ? 0 : (w & (~0ull << (64 - valid)));
+        }
+        return w;
+    }
+    u64 read(unsigned bits) {                                 // bits <= 57
+        if (bits == 0) return 0;
+        const u64 v = peek() >> (64 - bits);
+        pos += bits;
+        return v;
+    }
+    u64 read_compressed_int() {                               // io/BitIStream.hpp:174-188, 7-bit groups
+        u64 v = 0; unsigned i = 0; bool more;
+        do { more = read(1) != 0; v |= read(7) << (7 * i++); } while (more && i < 10);
+        return v;
+    }
+};
+
+// 64 stream bits from absolute bit position x on (MSB first), zeros behind `total` (BitIStream reads zeros at eof).  `words` are the
+// stream's 32-bit words, byte-swapped so that bit 31 of word k is stream bit 32 k; word index kb is words[0].
+struct BitWin {
+    const u32* words; u64 kb; u64 total;
+    __device__ __forceinline__ u64 peek(u64 x) const {
+        if (x >= total) return 0ull;
+        const u64 k = (x >> 5) - kb;
+        const u32 sh = (u32)x & 31u;
+        const u64 hi = ((u64)words[k] << 32) | words[k + 1];
+        u64 w = sh ? (hi << sh) | (u64)(words[k + 2] >> (32 - sh)) : hi;
+        if (x + 64 > total) w &= ~0ull << (64 - (total - x));
+        return w;
+    }
+};
+// the same over the stream in global memory (bytes; the buffer is padded with 16 zero bytes)
+struct BitWinG {
+    const u32* s32; u64 total;
+    __device__ __forceinline__ u64 peek(u64 x) const {
+        if (x >= total) return 0ull;
+        const u64 k = x >> 5;
+        const u32 sh = (u32)x & 31u;
+        const u32 a = __builtin_bswap32(s32[k]), b = __builtin_bswap32(s32[k + 1]), c = __builtin_bswap32(s32[k + 2]);
+        const u64 hi = ((u64)a << 32) | b;
+        u64 w = sh ? (hi << sh) | (u64)(c >> (32 - sh)) : hi;
+        if (x + 64 > total) w &= ~0ull << (64 - (total - x));
+        return w;
+    }
+};
+
+// where a decoded text of n bytes goes: out.into if set (HipError hipErrorOutOfMemory if n > out.cap), else a buffer allocated here
+// (out.owned; the caller releases it with free())
+u8* decode_dest(DecodeOut& o, size_t n);
+// Resolves the reference forest of n text positions on the device and downloads the text into decode_dest(out, n).  d_text (n + 64
+// bytes) holds the literals at their positions; the factor list (d_pos, d_src, d_len: z entries, length 0 allowed) copies
+// text[d_src[i] + j] to d_pos[i] + j, j < d_len[i], every source in front of its target.  d_ref: n entries of scratch, d_changed: one
+// word.  st->rounds receives the number of pointer-jumping rounds.  n < 2^32 - 1 (positions and NONE32 share the u32 range).
+void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
+                          u32* d_changed, DecodeOut& out, DecodeStats* st);
+
+}  // namespace tdc

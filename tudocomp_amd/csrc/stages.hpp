@@ -178,6 +178,11 @@ struct StreamFormatError { const char* what; };          // malformed input
 struct DecodeOut { u8* into = nullptr; size_t cap = 0; u8* owned = nullptr; };
 // the same for streams written with another coder: 0 = HuffmanCoder, 2 = ASCIICoder, 3 | kmer << 8 = SLECoder
 size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, DecodeOut& out, DecodeStats* st);
+// LZ78Compressor::decompress (compressors/LZ78Compressor.hpp:142-160) for coder=gamma, parsed on the device (lz78_decode.hip).
+// Returns the text length; *need (nullable) receives it as soon as it is known -- also when out.into is too small (HipError
+// hipErrorOutOfMemory).  Malformed input: StreamFormatError; a text of more than 2^32 - 2 bytes: DecodeTooLarge.
+struct DecodeTooLarge { u64 n; };
+size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, DecodeOut& out, size_t* need, DecodeStats* st);
 // a17: compressors/LZ78Compressor.hpp:64-140 -- sequential parse on the host; returns the number of (id, char) pairs
 size_t lz78_parse_host(const u8* in, size_t n, std::vector<u32>& ids, std::vector<u8>& chars, bool* leftover_is_high);
 // a16: coders/EliasGammaCoder.hpp:26-29 + io/BitOStream.hpp:105-129 on the device; returns the stream length

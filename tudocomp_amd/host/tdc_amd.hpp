@@ -422,9 +422,20 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
-    // LZ78Compressor::decompress (:142-160) with EliasGammaCoder::Decoder: pairs until BitIStream eof
+    // LZ78Compressor::decompress (:142-160) with EliasGammaCoder::Decoder: pairs until BitIStream eof.
+    // dec=gpu (an addition, as for lcpcomp): the stream is parsed and the phrases are expanded on the device (tdc_gpu_lz78_decompress);
+    // the stream itself is the same either way.
     void decompress(Input& input, Output& output) override {
         const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_lz78_decompress(m_ctx->h, in.data(), in.size(), TDC_GPU_CODER_GAMMA, &out, &out_len, nullptr, nullptr);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
         EliasGammaCoder::Decoder decoder(std::make_shared<BitIStream>(in.data(), in.size()));
         std::vector<uint32_t> parent(1, 0);
         std::vector<uint8_t> chr(1, 0);
@@ -462,7 +473,8 @@ inline std::vector<std::string> registered_algorithms() {
              "lcpcomp(coder=..., comp=heap, ...)                                          [MI355X, sequential replay of the reference's heap: a parity row, about a minute per MiB -- inputs of a few hundred KiB at most]",
              "lcpcomp(coder=arithmetic, comp=arrays, threshold=5, flatten=1)              [MI355X, compress only]",
              "lzss_lcp(coder=huff, threshold=3)                                           [MI355X, libtdc_gpu.so]",
-             "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]" };
+             "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]",
+             "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]" };
 }
 
 inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuContext> ctx = nullptr, int device = 0) {
@@ -470,7 +482,7 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
     Selection s;
     s.id_string = id;
     if (av.name == "lz78") {
-        auto z = std::make_unique<LZ78Compressor>(parse_algorithm_id(id, {"coder", "lz78trie"}), std::move(ctx));
+        auto z = std::make_unique<LZ78Compressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dec"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;
