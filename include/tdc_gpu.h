@@ -229,7 +229,8 @@ int tdc_gpu_flatten(tdc_gpu_ctx* ctx, size_t n, const uint32_t* pos, uint32_t* s
  * coders/HuffmanCoder.hpp:572-612); lzss_lcp(coder=huff) streams have the same format (LZSSLCPCompressor.hpp:125-130).
  * Streams of 1 MiB and more whose longest literal run is at most 512 are parsed ON THE DEVICE (rounds 4-5, DESIGN.md section 5: where
  * the token that starts at a bit position ends is evaluated for every bit position, the real token starts are the orbit of the
- * first one); smaller streams, longer literal runs and the SLE / ASCII coders take the host parse.  The references -- what ScanDec /
+ * first one) -- coder=huff and coder=sle (every kmer; rankings of up to 1024 entries, which is all the encoder writes) alike;
+ * smaller streams, longer literal runs and the ASCII coder take the host parse.  The references -- what ScanDec /
  * CompactDec spend their time on (lcpcomp/decompress/ScanDec.hpp:146-247) -- are resolved on the device by pointer jumping.
  * *out (malloc'd, free with tdc_gpu_free) receives the escaped, 0-terminated text exactly as compress() was given it.
  * factors / rounds (nullable): number of factors in the stream / pointer-jumping rounds.  Malformed input: TDC_GPU_ERR_ARG. */
@@ -243,9 +244,9 @@ int tdc_gpu_lcpcomp_decompress_coder(tdc_gpu_ctx* ctx, const uint8_t* stream, si
  * link's rate; the malloc'd variants pay for the page faults of a fresh buffer).  TDC_GPU_ERR_OOM if the text does not fit. */
 int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                     size_t* out_len, uint64_t* factors, uint32_t* rounds);
-/* 1 if the last tdc_gpu_lcpcomp_decompress / _decompress_coder / _decompress_into call on this context succeeded and parsed the token stream on the device (coder=huff streams
- * of 1 MiB and more whose longest literal run is at most 512; env TDC_GPU_DEC_PARSE = 0 never / 2 every size; TDC_GPU_DEC_LEAN = 0: the
- * general marking also for streams of short tokens -- tests), 0 if on the host. */
+/* 1 if the last tdc_gpu_lcpcomp_decompress / _decompress_coder / _decompress_into call on this context succeeded and parsed the token
+ * stream on the device (coder=huff and coder=sle streams of 1 MiB and more whose longest literal run is at most 512; option dec_parse =
+ * 0 never / 2 every size; option dec_lean = 0: the general marking also for streams of short tokens -- tests), 0 if on the host. */
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx);
 
 /* ---- LZ78Compressor::decompress (compressors/LZ78Compressor.hpp:142-160 -> lz78::Decompressor :16-37, EliasGammaCoder::Decoder

@@ -1,5 +1,6 @@
 """Decompression timing: tdc_gpu_lcpcomp_decompress on the stream of a synthetic text, token stream parsed on the
-host (TDC_GPU_DEC_PARSE=0) vs on the device (default).  Usage: python3 tools/decode_bench.py [english|dna] [N] [threshold]"""
+host (TDC_GPU_DEC_PARSE=0) vs on the device (default).
+Usage: python3 tools/decode_bench.py [english|dna] [N] [threshold] [huff|sle|sleK]      (sle = the reference's default kmer 3)"""
 import os; os.environ.setdefault("TDC_GPU_DEBUG_KNOBS", "1")   # (development tool: the TDC_GPU_* variables below are applied -- include/tdc_gpu.h, options)
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,11 +10,15 @@ import tudocomp_amd as T
 gen = sys.argv[1] if len(sys.argv) > 1 else "english"
 N = int(float(sys.argv[2])) if len(sys.argv) > 2 else 1 << 28
 thr = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+cname = sys.argv[4] if len(sys.argv) > 4 else "huff"
+if cname != "huff" and not (cname[:3] == "sle" and cname[3:] in ("", "1", "2", "3", "4", "5", "6", "7")):
+    sys.exit("coder must be huff, sle or sle1 .. sle7")
+coder = T.CODER_HUFF if cname == "huff" else T.CODER_SLE | (int(cname[3:] or 0) << 8)
 data = T.gen_english(N, 42) if gen == "english" else T.gen_dna(N, 7)
 text = np.concatenate([data, np.zeros(1, dtype=np.uint8)])
 with T.Context(0) as ctx:
-    stream, cst = ctx.lcpcomp_compress(text, thr, 1)
-print("%s %d B, threshold %d: stream %d B, %d factors, fdist_max %d" % (gen, N, thr, len(stream), cst["factors"], cst["fdist_max"]), flush=True)
+    stream, cst = ctx.lcpcomp_compress(text, thr, 1, coder)
+print("%s %d B, threshold %d, coder %s: stream %d B, %d factors, fdist_max %d" % (gen, N, thr, cname, len(stream), cst["factors"], cst["fdist_max"]), flush=True)
 want = text.tobytes()
 for mode in ("0", "1"):
     os.environ["TDC_GPU_DEC_PARSE"] = mode
@@ -24,11 +29,11 @@ for mode in ("0", "1"):
         for i in range(4):                         # the C ABI call alone (the binding's copy into a Python bytes object is not the library's time)
             p, n = ctypes.c_void_p(), ctypes.c_size_t()
             t0 = time.perf_counter()
-            rc = ctx._L.tdc_gpu_lcpcomp_decompress_coder(ctx._h, a.ctypes.data_as(ctypes.c_void_p), len(a), T.CODER_HUFF, ctypes.byref(p), ctypes.byref(n), None, None)
+            rc = ctx._L.tdc_gpu_lcpcomp_decompress_coder(ctx._h, a.ctypes.data_as(ctypes.c_void_p), len(a), coder, ctypes.byref(p), ctypes.byref(n), None, None)
             ts.append(time.perf_counter() - t0)
             assert rc == 0
             ctx._L.tdc_gpu_free(p)
-        back, st = ctx.lcpcomp_decompress(stream)
+        back, st = ctx.lcpcomp_decompress(stream, coder)
         ok = back == want
         del back
         t = min(ts[1:])
@@ -43,7 +48,7 @@ with T.Context(0) as ctx:
     ts = []
     for i in range(5):
         t0 = time.perf_counter()
-        n, st = ctx.lcpcomp_decompress_into(h_in, h_out)
+        n, st = ctx.lcpcomp_decompress_into(h_in, h_out, coder)
         ts.append(time.perf_counter() - t0)
     ok = n == N + 1 and h_out.a[:n].tobytes() == want
     t = min(ts[1:])

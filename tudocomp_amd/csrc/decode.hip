@@ -17,8 +17,10 @@
 #include "decode.hpp"
 
 #include <chrono>
+#include <memory>
 #include <new>
 #include <stdlib.h>
+#include <type_traits>
 #include <sys/mman.h>
 #include <vector>
 
@@ -153,32 +155,107 @@ __device__ __forceinline__ u32 dec_code(const DevTab* T, u64 w, u32& sym) {
     return length + 1;
 }
 
-// The token that starts at bit x.  Returns 0: literals + factor, 1: literals, then the stream ends (:83-91), < 0: no token.
+// SLE code tables (coders/SLECoder.hpp:301-453), the counterpart of DevTab: per rank of the extended alphabet how many literals the
+// entry stands for (top byte: 1, or k for a k-mer) and its bytes in text order (byte j in bits 8 j ..).  The encoder writes at most
+// 2^(8+2) ranks (:126-143); streams with a longer ranking keep the host parse.
+constexpr u32 SLE_DEV_RANKS = 1024;
+struct SleTab {
+    u32 sigma, sigma_bits, k, pad;
+    u64 ent[SLE_DEV_RANKS];
+};
+
+// one literal code of the rank classes (:368-404): bits used, the rank (>= sigma: no code)
+__device__ __forceinline__ u32 sle_code(const SleTab* T, u64 w, u32& rank) {
+    const u32 sb = T->sigma_bits;                                                // >= 1
+    if (sb < 4) { rank = (u32)(w >> (64 - sb)); return sb; }
+    if (sb < 6) {
+        if (w >> 63) { rank = (u32)((w << 1) >> (64 - sb)); return 1 + sb; }
+        rank = (u32)((w << 1) >> 62); return 3;
+    }
+    if (sb == 6) {
+        const u32 cls = (u32)(w >> 62);
+        const u64 b = w << 2;
+        if (cls == 0) { rank = (u32)(b >> 61); return 5; }
+        if (cls == 1) { rank = 8 + (u32)(b >> 61); return 5; }
+        if (cls == 2) { rank = 16 + (u32)(b >> 60); return 6; }
+        rank = (u32)(b >> (64 - 6)); return 8;
+    }
+    const u32 cls = (u32)(w >> 61);
+    const u64 b = w << 3;
+    if (cls < 4) { rank = 4 * cls + (u32)(b >> 62); return 5; }
+    if (cls < 7) { rank = 16 + 8 * (cls - 4) + (u32)(b >> 61); return 6; }
+    rank = (u32)(b >> (64 - sb)); return 3 + sb;
+}
+
+// What differs between the coders, one overload per table type:
+//   dec_run:   the r literals of a run from bit y on (false: no token).  `open`: the run ended inside a k-mer.  SLE only -- the
+//              Huffman run, one code per literal, stands in dec_token itself (its instances keep the code they had before SLE)
+//   dec_len:   the factor's length field in the left-aligned bits v behind its source: bits used, value
+//   dec_ends:  does a token have to end inside the stream?  The Huffman parse refuses one that does not; the SLE parse reads zeros
+//              behind the end like the host parser (FastBits) and leaves the verdict to the length check.
+// A code yields 1 or k literals; a k-mer that would run past the r-th literal is cut there (its other bytes are dropped: the k-mer
+// read state does not survive the next field, :419-450), as in the host parser's `while (num--)` loop.
 template <typename Win, typename Lit>
-__device__ __forceinline__ int dec_token(const Win& bw, u64 x, const ParseParams& P, const DevTab* T, Lit&& lit, u64& next, u32& r, u32& src, u32& len) {
+__device__ __forceinline__ bool dec_run(const SleTab* T, const Win& bw, u64& y, u32 r, Lit&& lit, bool& open) {
+    u32 i = 0;
+    while (i < r) {
+        u32 rank;
+        y += sle_code(T, bw.peek(y), rank);
+        if (rank >= T->sigma) return false;
+        const u64 e = T->ent[rank];
+        const u32 c = (u32)(e >> 56), take = min(c, r - i);
+        for (u32 j = 0; j < take; ++j) lit(i + j, (u8)(e >> (8 * j)));
+        i += take;
+        open = take < c;
+    }
+    return true;
+}
+__device__ __forceinline__ u32 dec_len(const DevTab*, u64 v, u32 lbits, u32& val) { val = (u32)(v >> (64 - lbits)); return lbits; }
+__device__ __forceinline__ u32 dec_len(const SleTab*, u64 v, u32 lbits, u32& val) {      // MinDistributedRange, :425-444
+    if (lbits <= 5) { val = (u32)(v >> (64 - lbits)); return lbits; }
+    const u32 cls = (u32)(v >> 62);
+    const u64 b = v << 2;
+    if (cls == 0) { val = (u32)(b >> 61); return 5; }
+    if (cls == 1) { val = 8 + (u32)(b >> 61); return 5; }
+    if (cls == 2) { val = 16 + (u32)(b >> 60); return 6; }
+    val = (u32)(b >> (64 - lbits)); return 2 + lbits;
+}
+__device__ __forceinline__ constexpr bool dec_ends(const DevTab*) { return true; }
+__device__ __forceinline__ constexpr bool dec_ends(const SleTab*) { return false; }
+
+// The token that starts at bit x.  Returns 0: literals + factor, 1: literals, then the stream ends (:83-91), < 0: no token.
+// End of an SLE stream: SLECoder's eof() is false inside a k-mer (:358-366), so a last run that ends inside one is followed by a
+// factor all the same -- read from the zeros behind the end if need be.  The device does what the host parser does with the same
+// bytes: it reads that factor, and the stream stands or falls with the range and length checks.
+template <typename Tab, typename Win, typename Lit>
+__device__ __forceinline__ int dec_token(const Win& bw, u64 x, const ParseParams& P, const Tab* T, Lit&& lit, u64& next, u32& r, u32& src, u32& len) {
     r = 0; src = 0; len = 0; next = x;
     if (x >= P.total) return -1;
     u64 w = bw.peek(x);
     u64 y = x + 1;
+    bool open = false;
     if (w >> 63) {
         r = (u32)((w << 1) >> (64 - P.dbits));
         y += P.dbits;
         if (r > P.fdist_max) return -2;
-        for (u32 i = 0; i < r; ++i) {
-            u32 sym = 0;
-            const u32 l = dec_code(T, bw.peek(y), sym);
-            if (!l) return -3;
-            lit(i, (u8)sym);
-            y += l;
-        }
-        if (y > P.total) return -4;
+        if constexpr (std::is_same<Tab, DevTab>::value) {
+            for (u32 i = 0; i < r; ++i) {
+                u32 sym = 0;
+                const u32 l = dec_code(T, bw.peek(y), sym);
+                if (!l) return -3;
+                lit(i, (u8)sym);
+                y += l;
+            }
+        } else if (!dec_run(T, bw, y, r, lit, open)) return -3;
+        if (dec_ends(T) && y > P.total) return -4;
     }
-    if (y >= P.total) { next = y; return 1; }
-    w = bw.peek(y);
+    if (!open && y >= P.total) { next = y; return 1; }
+    w = bw.peek(y);                                               // (W + the longest length field <= 31 + 33 bits: one window)
     src = (u32)(w >> (64 - P.W));
-    len = (u32)P.flen_min + (u32)((w << P.W) >> (64 - P.lbits));
-    y += P.W + P.lbits;
-    if (y > P.total) return -5;
+    u32 v;
+    y += P.W + dec_len(T, w << P.W, P.lbits, v);
+    len = (u32)P.flen_min + v;
+    if (dec_ends(T) && y > P.total) return -5;
     next = y;
     return 0;
 }
@@ -187,14 +264,20 @@ __device__ __forceinline__ void dec_tab_to_lds(const DevTab* g, DevTab* l) {
     const u32* a = (const u32*)g; u32* b = (u32*)l;
     for (u32 i = threadIdx.x; i < sizeof(DevTab) / 4; i += blockDim.x) b[i] = a[i];
 }
+__device__ __forceinline__ void dec_tab_to_lds(const SleTab* g, SleTab* l) {           // the ranks in use only
+    const u32* a = (const u32*)g; u32* b = (u32*)l;
+    const u32 words = 4 + 2 * min(g->sigma, SLE_DEV_RANKS);
+    for (u32 i = threadIdx.x; i < words; i += blockDim.x) b[i] = a[i];
+}
 
 // next() for the bit positions x_in .. x_in + m - 1 (array index = position - x_in; m = "leaves the segment"; no token: m as well --
 // the chain ends there and the count pass reports it)
-__global__ __launch_bounds__(256) void dec_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const DevTab* __restrict__ gT,
+template <typename Tab>
+__global__ __launch_bounds__(256) void dec_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const Tab* __restrict__ gT,
                                                         u32 nwords, u32* __restrict__ next) {
     extern __shared__ __attribute__((aligned(16))) u32 dyn[];
-    DevTab* T = (DevTab*)dyn;
-    u32* sw = dyn + sizeof(DevTab) / 4;
+    Tab* T = (Tab*)dyn;
+    u32* sw = dyn + sizeof(Tab) / 4;
     dec_tab_to_lds(gT, T);
     const u32 i0 = blockIdx.x * DEC_TILE;
     const u64 a0 = x_in + i0;
@@ -218,9 +301,10 @@ __global__ __launch_bounds__(256) void dec_next_kernel(const u32* __restrict__ s
 struct DecScalars { u64 exit_bit; u64 total_out; u32 exit_status; u32 err; };
 
 // the tokens of a segment: absolute bit position, text positions it produces (literals + factor length)
+template <typename Tab>
 __global__ __launch_bounds__(256) void dec_count_kernel(const u32* __restrict__ s32, u64 x_in, const u32* __restrict__ idx, u32 cnt, ParseParams P,
-                                                         const DevTab* __restrict__ gT, u64* __restrict__ tokx, u32* __restrict__ outc, DecScalars* __restrict__ sc) {
-    __shared__ DevTab T;
+                                                         const Tab* __restrict__ gT, u64* __restrict__ tokx, u32* __restrict__ outc, DecScalars* __restrict__ sc) {
+    __shared__ Tab T;
     dec_tab_to_lds(gT, &T);
     __syncthreads();
     const BitWinG bw{s32, P.total};
@@ -244,10 +328,11 @@ __global__ __launch_bounds__(256) void dec_count_kernel(const u32* __restrict__ 
 }
 
 // literal bytes to their text positions, the factor list (a token without factor gets length 0)
+template <typename Tab>
 __global__ __launch_bounds__(256) void dec_emit_kernel(const u32* __restrict__ s32, const u64* __restrict__ tokx, const u32* __restrict__ base, u32 z, ParseParams P,
-                                                        const DevTab* __restrict__ gT, u8* __restrict__ text, u32* __restrict__ fpos, u32* __restrict__ fsrc,
+                                                        const Tab* __restrict__ gT, u8* __restrict__ text, u32* __restrict__ fpos, u32* __restrict__ fsrc,
                                                         u32* __restrict__ flen, DecScalars* __restrict__ sc) {
-    __shared__ DevTab T;
+    __shared__ Tab T;
     dec_tab_to_lds(gT, &T);
     __syncthreads();
     const BitWinG bw{s32, P.total};
@@ -280,11 +365,12 @@ constexpr u32 DL_CH = 16384;                // bit positions per workgroup of th
 constexpr u32 DL_LA_MAX = 1024;             // longest token (bits) the lean path takes
 constexpr u16 DL_NONE = 0xFFFFu;
 
-__global__ __launch_bounds__(256) void dec_lean_exit_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const DevTab* __restrict__ gT,
+template <typename Tab>
+__global__ __launch_bounds__(256) void dec_lean_exit_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const Tab* __restrict__ gT,
                                                              u32 nwords, u32 LA, u16* __restrict__ exit1) {
     extern __shared__ __attribute__((aligned(16))) u32 dyn[];
-    DevTab* T = (DevTab*)dyn;
-    u32* sw = dyn + sizeof(DevTab) / 4;
+    Tab* T = (Tab*)dyn;
+    u32* sw = dyn + sizeof(Tab) / 4;
     u16* nxl = (u16*)(sw + nwords);                            // next(x) - x of the workgroup's positions; 0: the chain ends at x
     dec_tab_to_lds(gT, T);
     const u32 i0 = blockIdx.x * DL_CH;
@@ -353,12 +439,12 @@ __global__ void dec_lean_tiles_kernel(const u16* __restrict__ exit1, const u16* 
 }
 // the tokens of every tile, walked from the tile's entry: EMIT = false counts them (tokens, text positions they produce), EMIT = true
 // writes the literal bytes and the factor list (tok0 / out0: what the earlier segments hold; tbase_*: exclusive sums over the tiles)
-template <bool EMIT>
-__global__ __launch_bounds__(256) void dec_lean_walk_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const DevTab* __restrict__ gT,
+template <typename Tab, bool EMIT>
+__global__ __launch_bounds__(256) void dec_lean_walk_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const Tab* __restrict__ gT,
                                                              const u16* __restrict__ tile_entry, u32 ntiles, u32* __restrict__ tcount, u32* __restrict__ tout,
                                                              u64 tok0, u64 out0, u8* __restrict__ text, u32* __restrict__ fpos, u32* __restrict__ fsrc,
                                                              u32* __restrict__ flen, DecScalars* __restrict__ sc) {
-    __shared__ DevTab T;
+    __shared__ Tab T;
     dec_tab_to_lds(gT, &T);
     __syncthreads();
     const BitWinG bw{s32, P.total};
@@ -414,7 +500,18 @@ __global__ __launch_bounds__(256) void dec_lean_walk_kernel(const u32* __restric
 
 // Header of a lcpcomp(coder=huff) stream: HuffmanCoder::Decoder ctor (HuffmanCoder.hpp:581-597) + huffmantable_decode (:278-290),
 // then the four fields of decode_text_internal (LCPCompressor.hpp:23-76).  Shared by the host parse and the device parse.
-struct HuffHeader {
+struct LzssFields {                                            // decode_text_internal (LCPCompressor.hpp:23-76)
+    u64 n = 0, flen_min = 0, flen_max = 0, fdist_max = 0;
+    unsigned W = 0, lbits = 0, dbits = 0;
+};
+static void parse_lzss_fields(FastBits& bs, LzssFields& F) {
+    F.n = bs.read(32);
+    F.W = bits_for(F.n);
+    F.flen_min = bs.read(F.W); F.flen_max = bs.read(F.W); F.fdist_max = bs.read(F.W);
+    F.lbits = bits_for(F.flen_max - F.flen_min); F.dbits = bits_for(F.fdist_max);
+    if (F.n == 0 || F.n >= 0x7FFFFFFFull) throw StreamError{"text length out of range"};     // a text always holds its sentinel
+}
+struct HuffHeader : LzssFields {
     bool have_table = false;
     u8 order[256];
     u64 firstcode[64];
@@ -423,8 +520,6 @@ struct HuffHeader {
     u8 numl[64] = {0};
     size_t sigma = 0;
     std::vector<unsigned short> lut;                          // (symbol << 4) | code length, 0 = longer than LUT_BITS / invalid
-    u64 n = 0, flen_min = 0, flen_max = 0, fdist_max = 0;
-    unsigned W = 0, lbits = 0, dbits = 0;
 };
 static void parse_huff_header(FastBits& bs, size_t len, HuffHeader& H) {
     H.have_table = bs.read(1) != 0;
@@ -450,12 +545,7 @@ static void parse_huff_header(FastBits& bs, size_t len, HuffHeader& H) {
                 for (size_t x = 0; x < ((size_t)1 << (LUT_BITS - l)); ++x) H.lut[base + x] = e;
             }
     }
-    // decode_text_internal (LCPCompressor.hpp:23-76)
-    H.n = bs.read(32);
-    H.W = bits_for(H.n);
-    H.flen_min = bs.read(H.W); H.flen_max = bs.read(H.W); H.fdist_max = bs.read(H.W);
-    H.lbits = bits_for(H.flen_max - H.flen_min); H.dbits = bits_for(H.fdist_max);
-    if (H.n == 0 || H.n >= 0x7FFFFFFFull) throw StreamError{"text length out of range"};     // a text always holds its sentinel
+    parse_lzss_fields(bs, H);
     {   // plausibility (a corrupt header would otherwise ask for gigabytes): a literal costs at least one bit, a factor at least W
         // bits and covers at most flen_max positions
         const u64 bits = (u64)len * 8;
@@ -506,16 +596,31 @@ static u64 parse_lzss_huff_stream(FastBits& bs, const HuffHeader& H, std::vector
     return n;
 }
 
-// The same token stream written with SLECoder (coders/SLECoder.hpp:301-453: ranking header, rank class codes, k-mer symbols
-// expand to k literals, MinDistributedRange for the factor length).
-static u64 parse_lzss_sle_stream(const u8* in, size_t len, unsigned k, std::vector<u8>& text, std::vector<u32>& fpos,
+// Header of a lcpcomp(coder=sle) stream: SLECoder::Decoder ctor (coders/SLECoder.hpp:325-340: the inverse ranking of the extended
+// alphabet, a byte or a k-mer tagged 0xFF in its top byte), then the fields of decode_text_internal.  Shared by both parses.
+struct SleHeader : LzssFields {
+    unsigned k = 3, sb = 0;
+    size_t sigma = 0;
+    std::vector<u64> inv;
+};
+static void parse_sle_header(FastBits& bs, unsigned k, SleHeader& H) {
+    H.k = k;
+    H.sigma = (size_t)bs.read_compressed_int();
+    if (H.sigma == 0 || H.sigma > 4096) throw StreamError{"corrupt SLE ranking"};
+    H.sb = bits_for(H.sigma - 1);
+    H.inv.resize(H.sigma);
+    for (size_t r = 0; r < H.sigma; ++r) H.inv[r] = bs.read_compressed_int();
+    parse_lzss_fields(bs, H);
+}
+
+// Host parse of the same token stream written with SLECoder (:301-453: rank class codes, k-mer symbols expand to k literals,
+// MinDistributedRange for the factor length).
+static u64 parse_lzss_sle_stream(FastBits& bs, const SleHeader& H, std::vector<u8>& text, std::vector<u32>& fpos,
                                  std::vector<u32>& fsrc, std::vector<u32>& flen) {
-    FastBits bs(in, len);
-    const size_t sigma = (size_t)bs.read_compressed_int();                  // Decoder ctor :325-340
-    if (sigma == 0 || sigma > 4096) throw StreamError{"corrupt SLE ranking"};
-    const unsigned sb = bits_for(sigma - 1);
-    std::vector<u64> inv(sigma);
-    for (size_t r = 0; r < sigma; ++r) inv[r] = bs.read_compressed_int();
+    const size_t sigma = H.sigma;
+    const unsigned sb = H.sb, k = H.k, W = H.W, lbits = H.lbits, dbits = H.dbits;
+    const u64 n = H.n, flen_min = H.flen_min;
+    const std::vector<u64>& inv = H.inv;
     auto read_rank = [&]() -> u64 {                                           // :367-397
         if (sb < 4) return bs.read(sb);
         if (sb < 6) return bs.read(1) ? bs.read(sb) : bs.read(2);
@@ -532,11 +637,6 @@ static u64 parse_lzss_sle_stream(const u8* in, size_t len, unsigned k, std::vect
         if (cls < 7) return 16 + 8 * (cls - 4) + bs.read(3);
         return bs.read(sb);
     };
-    const u64 n = bs.read(32);
-    const unsigned W = bits_for(n);
-    const u64 flen_min = bs.read(W), flen_max = bs.read(W), fdist_max = bs.read(W);
-    const unsigned lbits = bits_for(flen_max - flen_min), dbits = bits_for(fdist_max);
-    if (n == 0 || n >= 0x7FFFFFFFull) throw StreamError{"text length out of range"};
     text.assign((size_t)n, 0);
     u8 kmer[8]; size_t kread = (size_t)-1;
     u64 p = 0;
@@ -701,18 +801,57 @@ void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d
     tick("download");
 }
 
-// lcpcomp(coder=huff) with the token stream parsed on the device.  Returns false if this stream keeps the host parse (long literal
-// runs); throws StreamFormatError for malformed input.
-static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const HuffHeader& H, u64 x0, u64 total, DecodeOut& out,
-                                    DecodeStats* st) {
+// What the device parse needs to know of a coder: its table and the widths of its variable fields.
+template <typename Tab> struct DevCoder {
+    Tab tab;                                  // as the kernels read it
+    u64 code_max = 0;                         // longest literal code (bits)
+    u64 lenf_min = 0, lenf_max = 0;           // shortest / longest length field of a factor (bits)
+};
+static void dev_coder(const HuffHeader& H, DevCoder<DevTab>& D) {
+    DevTab* t = &D.tab;
+    memset(t, 0, sizeof(DevTab));
+    t->have_table = H.have_table ? 1u : 0u; t->longest = H.longest; t->sigma = (u32)H.sigma;
+    if (H.have_table) {
+        memcpy(t->lut, H.lut.data(), sizeof(t->lut));
+        for (unsigned i = 0; i < 64; ++i) { t->firstcode[i] = i < H.longest ? H.firstcode[i] : 0; t->prefix_sum[i] = i < H.longest ? (u32)H.prefix_sum[i] : 0; t->numl[i] = H.numl[i]; }
+        memcpy(t->order, H.order, 256);
+    }
+    D.code_max = H.have_table ? H.longest : 8;
+    D.lenf_min = D.lenf_max = H.lbits;
+}
+// (false: the ranking does not fit the device table)
+static bool dev_coder(const SleHeader& H, DevCoder<SleTab>& D) {
+    if (H.sigma > SLE_DEV_RANKS || H.k < 1 || H.k > 7) return false;
+    SleTab* t = &D.tab;
+    memset(t, 0, sizeof(SleTab));
+    t->sigma = (u32)H.sigma; t->sigma_bits = H.sb; t->k = H.k;
+    for (size_t r = 0; r < H.sigma; ++r) {
+        const u64 x = H.inv[r];
+        if ((x >> 56) == 0xFF) {                                                 // a k-mer, first byte most significant
+            u64 e = (u64)H.k << 56;
+            for (unsigned j = 0; j < H.k; ++j) e |= ((x >> (8 * (H.k - 1 - j))) & 0xFFull) << (8 * j);
+            t->ent[r] = e;
+        } else t->ent[r] = (1ull << 56) | (x & 0xFFull);
+    }
+    const unsigned sb = H.sb;                                                    // rank classes, SLECoder.hpp:368-404
+    D.code_max = sb < 4 ? sb : sb < 6 ? 1 + sb : sb == 6 ? 8 : 3 + sb;
+    D.lenf_min = H.lbits <= 5 ? H.lbits : 5;                                     // MinDistributedRange, :425-444
+    D.lenf_max = H.lbits <= 5 ? H.lbits : 2 + H.lbits;
+    return true;
+}
+
+// lcpcomp(coder=huff | sle) with the token stream parsed on the device.  Returns false if this stream keeps the host parse (long
+// literal runs); throws StreamFormatError for malformed input.
+template <typename Tab>
+static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssFields& H, const DevCoder<Tab>& D, u64 x0, u64 total,
+                               DecodeOut& out, DecodeStats* st) {
     if (H.fdist_max > DEC_MAX_RUN) return false;
-    const u64 code_max = H.have_table ? H.longest : 8;
-    const u64 la_bits = 1 + H.dbits + H.fdist_max * code_max + H.W + H.lbits;          // the longest token a candidate may read
+    const u64 la_bits = 1 + H.dbits + H.fdist_max * D.code_max + H.W + D.lenf_max;     // the longest token a candidate may read
     const u32 nwords = (u32)((DEC_TILE + la_bits + 31) / 32 + 4);
-    const size_t lds = sizeof(DevTab) + (size_t)nwords * 4;
+    const size_t lds = sizeof(Tab) + (size_t)nwords * 4;
     if (lds > 60 * 1024) return false;
     const size_t n = (size_t)H.n;
-    const u64 min_tok = 1 + H.W + H.lbits;
+    const u64 min_tok = 1 + H.W + D.lenf_min;
     const size_t zmax = (size_t)((total - x0) / min_tok + 2);
     const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;                    // (tests shrink the segments)
     const size_t seg = (size_t)std::min<u64>(seg_bits, total - x0 + 1);
@@ -729,7 +868,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
     if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, "decode: the caller's buffer is too small for the text", (int)__LINE__};   // (known from the header: before any device work)
     // (the device parse needs ~17 bytes of arena per stream bit of a segment on top of 5 n + 28 zmax; the host parse needs 5 n + 12 z: if
     //  the device cannot provide the former, the host parse takes the stream instead of the call failing)
-    try { c.ensure_arena(len + 64 + n * 5 + n / 8 + zmax * 28 + seg * 17 + sizeof(DevTab) + ((size_t)16 << 20)); }
+    try { c.ensure_arena(len + 64 + n * 5 + n / 8 + zmax * 28 + seg * 17 + sizeof(Tab) + ((size_t)16 << 20)); }
     catch (const HipError& e) { if (e.e != hipErrorOutOfMemory) throw; (void)hipGetLastError(); return false; }
     const size_t mark0 = c.arena.mark();
     u8* d_stream = c.arena.get<u8>(len + 64);
@@ -760,19 +899,9 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
     }
     HIP_TRY(hipMemsetAsync(d_stream + len, 0, 64, s));
     const u32* s32 = (const u32*)d_stream;                                              // (arena allocations are 256-byte aligned)
-    DevTab* d_tab = (DevTab*)c.arena.alloc(sizeof(DevTab));
-    {
-        std::vector<u8> hb(sizeof(DevTab), 0);
-        DevTab* t = (DevTab*)hb.data();
-        t->have_table = H.have_table ? 1u : 0u; t->longest = H.longest; t->sigma = (u32)H.sigma;
-        if (H.have_table) {
-            memcpy(t->lut, H.lut.data(), sizeof(t->lut));
-            for (unsigned i = 0; i < 64; ++i) { t->firstcode[i] = i < H.longest ? H.firstcode[i] : 0; t->prefix_sum[i] = i < H.longest ? (u32)H.prefix_sum[i] : 0; t->numl[i] = H.numl[i]; }
-            memcpy(t->order, H.order, 256);
-        }
-        HIP_TRY(hipMemcpyAsync(d_tab, hb.data(), sizeof(DevTab), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));                                               // (hb leaves scope)
-    }
+    Tab* d_tab = (Tab*)c.arena.alloc(sizeof(Tab));
+    HIP_TRY(hipMemcpyAsync(d_tab, &D.tab, sizeof(Tab), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     const ParseParams P{ total, H.n, H.flen_min, H.W, H.lbits, H.dbits, (u32)H.fdist_max };
     if (la_bits <= DL_LA_MAX && c.dec_lean) {
         // ---- lean marking (short tokens): per segment exits per tile entry -> groups -> tile entries -> count walk -> scans -> emit walk
@@ -785,7 +914,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
         HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(DecScalars), s));
         HIP_TRY(hipMemsetAsync(d_text, 0, n, s));
         const u32 nw_l = (u32)((DL_CH + la_bits + 31) / 32 + 4);
-        const size_t lds_l = sizeof(DevTab) + (size_t)nw_l * 4 + (size_t)DL_CH * 2;
+        const size_t lds_l = sizeof(Tab) + (size_t)nw_l * 4 + (size_t)DL_CH * 2;
         size_t z = 0;
         u64 x_in = x0, out0 = 0;
         u32 last_status = 0;
@@ -800,7 +929,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
             u32* tcount = c.arena.get<u32>(ntiles), *tout = c.arena.get<u32>(ntiles);
             up.need((size_t)((x_in + m + la_bits) / 8 + 64), len, s);
             tick("upload + tables");
-            dec_lean_exit_kernel<<<cdiv(m, DL_CH), 256, lds_l, s>>>(s32, x_in, m, P, d_tab, nw_l, LA, exit1);
+            dec_lean_exit_kernel<Tab><<<cdiv(m, DL_CH), 256, lds_l, s>>>(s32, x_in, m, P, d_tab, nw_l, LA, exit1);
             LAUNCH_CHECK();
             tick("next() + tile exits");
             dec_lean_exit2_kernel<<<cdiv((size_t)ngroups * LA, 256), 256, 0, s>>>(exit1, ntiles, ngroups, LA, exit2);
@@ -811,7 +940,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
             LAUNCH_CHECK();
             tick("group + tile entries");
             const unsigned gw = std::min<u32>(cdiv(ntiles, 256), 4096u);
-            dec_lean_walk_kernel<false><<<gw, 256, 0, s>>>(s32, x_in, m, P, d_tab, tentry, ntiles, tcount, tout, 0, 0, nullptr, nullptr, nullptr, nullptr, d_sc);
+            dec_lean_walk_kernel<Tab, false><<<gw, 256, 0, s>>>(s32, x_in, m, P, d_tab, tentry, ntiles, tcount, tout, 0, 0, nullptr, nullptr, nullptr, nullptr, d_sc);
             LAUNCH_CHECK();
             exclusive_sum_u32(c, tcount, tcount, ntiles, d_cnt);
             const u32 cnt = c.read(d_cnt);
@@ -821,7 +950,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
             if (cnt == 0 || z + cnt > zmax) throw StreamFormatError{"corrupt stream: token chain"};
             if (h.err || h.exit_status == 2) throw StreamFormatError{"corrupt stream: malformed token"};
             if (h.total_out > H.n) throw StreamFormatError{"corrupt stream: length mismatch"};   // (64-bit total over all segments so far: no 32-bit sum below it can have wrapped)
-            dec_lean_walk_kernel<true><<<gw, 256, 0, s>>>(s32, x_in, m, P, d_tab, tentry, ntiles, tcount, tout, (u64)z, out0, d_text, d_pos, d_src, d_len, d_sc);
+            dec_lean_walk_kernel<Tab, true><<<gw, 256, 0, s>>>(s32, x_in, m, P, d_tab, tentry, ntiles, tcount, tout, (u64)z, out0, d_text, d_pos, d_src, d_len, d_sc);
             LAUNCH_CHECK();
             tick("emit walk");
             c.arena.release(mk);
@@ -858,7 +987,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
         u8* mark = c.arena.get<u8>(m);
         up.need((size_t)((x_in + m + la_bits) / 8 + 64), len, s);
         tick("upload + tables");
-        dec_next_kernel<<<cdiv(m, DEC_TILE), 256, lds, s>>>(s32, x_in, m, P, d_tab, nwords, next);
+        dec_next_kernel<Tab><<<cdiv(m, DEC_TILE), 256, lds, s>>>(s32, x_in, m, P, d_tab, nwords, next);
         LAUNCH_CHECK();
         tick("next() of every bit");
         mark_orbit_u32(c, next, m, mark, e1, e2);
@@ -868,7 +997,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
         const u32 cnt = c.read(d_cnt);
         tick("token list");
         if (cnt == 0 || z + cnt > zmax) throw StreamFormatError{"corrupt stream: token chain"};
-        dec_count_kernel<<<std::min<u32>(cdiv(cnt, 256), 4096u), 256, 0, s>>>(s32, x_in, idx, cnt, P, d_tab, tokx + z, outc + z, d_sc);
+        dec_count_kernel<Tab><<<std::min<u32>(cdiv(cnt, 256), 4096u), 256, 0, s>>>(s32, x_in, idx, cnt, P, d_tab, tokx + z, outc + z, d_sc);
         LAUNCH_CHECK();
         const DecScalars h = c.read(d_sc);
         tick("count pass");
@@ -891,7 +1020,7 @@ static bool decode_lzss_huff_device(Ctx& c, const u8* stream, size_t len, const 
     u8* d_text = c.arena.get<u8>(n + 64);
     u32* d_ref = c.arena.get<u32>(n);
     HIP_TRY(hipMemsetAsync(d_text, 0, n, s));
-    dec_emit_kernel<<<std::min<u32>(cdiv(z, 256), 4096u), 256, 0, s>>>(s32, tokx, base, (u32)z, P, d_tab, d_text, d_pos, d_src, d_len, d_sc);
+    dec_emit_kernel<Tab><<<std::min<u32>(cdiv(z, 256), 4096u), 256, 0, s>>>(s32, tokx, base, (u32)z, P, d_tab, d_text, d_pos, d_src, d_len, d_sc);
     LAUNCH_CHECK();
     const DecScalars h = c.read(d_sc);
     tick("scan + emit pass");
@@ -912,17 +1041,37 @@ size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, DecodeOut& o
     std::vector<u8> text;                                    // (host parse only: the literals at their text positions)
     std::vector<u32> fpos, fsrc, flen;
     u64 n;
-    if ((coder & 0xFF) == 3) n = parse_lzss_sle_stream(stream, len, (unsigned)(coder >> 8) ? (unsigned)(coder >> 8) : 3u, text, fpos, fsrc, flen);
-    else if (coder == 2) n = parse_lzss_ascii_stream(stream, len, text, fpos, fsrc, flen);
+    // the token stream itself: on the device (option dec_parse: 1 = streams of 1 MiB and more, 2 = every stream, 0 = never), else on
+    // the host -- as well for the streams the device parse declines
+    auto on_device = [&](const FastBits& bs) { return bs.pos < bs.total && c.dec_parse && (c.dec_parse >= 2 || len >= ((size_t)1 << 20)); };
+    if ((coder & 0xFF) == 3) {
+        FastBits bs(stream, len);
+        SleHeader H;
+        parse_sle_header(bs, (unsigned)(coder >> 8) ? (unsigned)(coder >> 8) : 3u, H);
+        if (on_device(bs)) {
+            // (this header has no plausibility check of its own: a text length the stream cannot hold -- a code gives at most k
+            //  literals, a factor costs at least W bits -- is left to the host parse and its verdict)
+            const u64 bits = (u64)len * 8;
+            std::unique_ptr<DevCoder<SleTab>> D(new DevCoder<SleTab>);
+            if (H.n <= bits * H.k + (bits / H.W + 1) * (H.flen_max ? H.flen_max : 1) && dev_coder(H, *D) &&
+                decode_lzss_device(c, stream, len, H, *D, bs.pos, bs.total, out, st)) {
+                st->device_parse = 1;
+                return (size_t)H.n;
+            }
+        }
+        n = parse_lzss_sle_stream(bs, H, text, fpos, fsrc, flen);
+    } else if (coder == 2) n = parse_lzss_ascii_stream(stream, len, text, fpos, fsrc, flen);
     else {
         FastBits bs(stream, len);
         HuffHeader H;
         parse_huff_header(bs, len, H);
-        // the token stream itself: on the device (streams of 1 MiB and more; TDC_GPU_DEC_PARSE = 0 never / 2 always: tests), else on the host
-        if (bs.pos < bs.total && c.dec_parse && (c.dec_parse >= 2 || len >= ((size_t)1 << 20)) &&
-            decode_lzss_huff_device(c, stream, len, H, bs.pos, bs.total, out, st)) {
-            st->device_parse = 1;
-            return (size_t)H.n;
+        if (on_device(bs)) {
+            std::unique_ptr<DevCoder<DevTab>> D(new DevCoder<DevTab>);
+            dev_coder(H, *D);
+            if (decode_lzss_device(c, stream, len, H, *D, bs.pos, bs.total, out, st)) {
+                st->device_parse = 1;
+                return (size_t)H.n;
+            }
         }
         n = parse_lzss_huff_stream(bs, H, text, fpos, fsrc, flen);
     }

@@ -357,8 +357,9 @@ public:
         const bool on_device = m_opts.get("dec", "scan") == "gpu";
         if (!on_device && m_coder == TDC_GPU_CODER_ASCII) { lzss_ascii_decode(input, output); return; }
         if (!on_device && (m_coder & 0xFF) == TDC_GPU_CODER_SLE) { lzss_sle_decode(input, output, m_kmer); return; }
-        // dec=gpu (an addition to the reference's decoder strategies scan / compact / ..., LCPCompressor.hpp:88): the stream is
-        // parsed on the host, the references are resolved on the device (tdc_gpu_lcpcomp_decompress)
+        // dec=gpu (an addition to the reference's decoder strategies scan / compact / ..., LCPCompressor.hpp:88): huff and
+        // sle streams of 1 MiB and more are parsed on the device, the others on the host; the references are resolved on the device
+        // (tdc_gpu_lcpcomp_decompress_coder)
         if (m_opts.get("dec", "scan") == "gpu") {
             if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
             const bytes& in = input.raw();
