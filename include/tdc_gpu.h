@@ -266,6 +266,29 @@ int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len,
 int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                  size_t* out_len, uint64_t* phrases, uint32_t* rounds);
 
+/* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
+ * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG
+ * for an inner 0, TDC_GPU_ERR_TOO_LARGE).  out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0): n bytes, no header.  The suffix array is the one
+ * tdc_gpu_suffix_array builds; the transform is one gather over it, downloaded chunk by chunk behind the gather into page-locked memory.
+ * stats (nullable): n, out_len, ms_h2d, ms_sa, ms_encode (the gather), ms_d2h, ms_total and the sa_* fields. */
+int tdc_gpu_bwt_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t** out, size_t* out_len, tdc_gpu_stats* stats);
+/* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small. */
+int tdc_gpu_bwt_compress_into(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t* out, size_t out_cap, size_t* out_len,
+                              tdc_gpu_stats* stats);
+/* Inverse (decode_bwt, ds/bwt.hpp:77-98, with the complete C table -- DESIGN.md section 5.2): LF by a stable counting rank, then list ranking
+ * of its one cycle from sampled heads on the device; the reference walks LF one byte at a time.  *out (malloc'd, tdc_gpu_free) receives the
+ * escaped, 0-terminated text exactly as compress() was given it; a buffer of at most one byte decodes to nothing.  rounds (nullable):
+ * pointer-jumping rounds over the heads.  A buffer of two bytes or more that is no transform -- not exactly one 0 byte, or an LF mapping that
+ * is not one cycle --: TDC_GPU_ERR_ARG, nothing written to the destination.  len >= 2^31 - 1: TDC_GPU_ERR_TOO_LARGE. */
+int tdc_gpu_bwt_decompress(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t** out, size_t* out_len, uint32_t* rounds);
+int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t* out, size_t out_cap, size_t* out_len,
+                                uint32_t* rounds);
+/* tests: the inverse with its two parameters exposed (0 = the library's choice): sample = expected rows between two list heads, max_steps =
+ * most steps a walk takes in one launch.  out: len bytes; lf (nullable): len entries, the LF table; heads / launches (nullable): list heads
+ * in the end, launches of the first walk. */
+int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
+                              uint32_t* lf, uint64_t* heads, uint32_t* launches);
+
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,
                         const uint32_t* len, size_t z, uint8_t** out, size_t* out_len);

@@ -395,6 +395,59 @@ class Context:
             raise err
         return n.value, {"phrases": f.value, "rounds": r.value}
 
+    # ---- bwt ---------------------------------------------------------------------------------------------
+    def _raise_required(self, rc, n):
+        err = TdcGpuError(rc, self._L.tdc_gpu_last_error(self._h).decode())
+        err.required = n if rc == -5 else None
+        raise err
+
+    def bwt_compress(self, text):
+        """BWTCompressor::compress: text is the escaped + 0-terminated view.  Returns (the transform, stats dict)."""
+        a = text.a if isinstance(text, PinnedBuffer) else _u8(text)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_bwt_compress(self._h, _ptr(a), len(a), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)))
+        return self._take(out, n.value), st.as_dict()
+
+    def bwt_compress_into(self, text, n, out):
+        """bwt_compress of the first n bytes of `text` into a caller-owned buffer (PinnedBuffer or writable uint8 array): returns
+        (length, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is n."""
+        ta = text.a if isinstance(text, PinnedBuffer) else _u8(text)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_bwt_compress_into(self._h, _ptr(ta), n, _ptr(oa), oa.size, ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
+
+    def bwt_decompress(self, bwt):
+        """BWTCompressor::decompress on the device: returns the escaped, 0-terminated text and {"rounds"}."""
+        a = bwt.a if isinstance(bwt, PinnedBuffer) else _u8(bwt)
+        p, n, r = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_bwt_decompress(self._h, _ptr(a), len(a), ctypes.byref(p), ctypes.byref(n), ctypes.byref(r)))
+        return self._take(p, n.value), {"rounds": r.value}
+
+    def bwt_decompress_into(self, bwt, out, n=None):
+        """bwt_decompress of the first n bytes of `bwt` (default: all of it) into a caller-owned buffer: returns (text length, {"rounds"}).
+        A buffer that is too small raises TdcGpuError (status -5) whose `required` is the text length."""
+        a = bwt.a if isinstance(bwt, PinnedBuffer) else _u8(bwt)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, r = ctypes.c_size_t(), ctypes.c_uint32()
+        rc = self._L.tdc_gpu_bwt_decompress_into(self._h, _ptr(a), len(a) if n is None else n, _ptr(oa), oa.size, ctypes.byref(ol), ctypes.byref(r))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, {"rounds": r.value}
+
+    def bwt_inverse_stage(self, bwt, sample=0, max_steps=0, want_lf=True):
+        """the inverse with its parameters exposed (0 = the library's choice): sample = expected rows between two list heads, max_steps =
+        most steps of a walk per launch.  Returns (text, {"lf", "heads", "launches"})."""
+        a = _u8(bwt)
+        out = np.empty(len(a), dtype=np.uint8)
+        lf = np.empty(len(a), dtype=np.uint32) if want_lf else None
+        h, ln = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_bwt_inverse_stage(self._h, _ptr(a), len(a), int(sample), int(max_steps), _ptr(out),
+                                                      _ptr(lf) if want_lf else None, ctypes.byref(h), ctypes.byref(ln)))
+        return (out.tobytes() if len(a) > 1 else b""), {"lf": lf, "heads": h.value, "launches": ln.value}
+
     def blocks_decompress(self, blob, coder=CODER_HUFF):
         """inverse of blocks_compress on this context's device: the concatenated raw bytes"""
         a = _u8(blob)
@@ -475,6 +528,24 @@ class LCPCompressor:
             raise RuntimeError("lcpcomp(coder=arithmetic) streams cannot be decoded (neither can the reference)")
         text, _ = self.ctx.lcpcomp_decompress(stream, self.coder)
         return unescape(text)
+
+
+class BWTCompressor:
+    """Mirror of tdc::BWTCompressor (compressors/BWTCompressor.hpp:14-67): the Burrows-Wheeler transform of the input wrapped with the
+    compressor's input restrictions (escape {0}, null-terminate); decompress() inverts it on the device and removes them again."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.last_stats = None
+
+    def compress(self, data):
+        out, st = self.ctx.bwt_compress(escape(data))
+        self.last_stats = st
+        return out
+
+    def decompress(self, stream):
+        text, _ = self.ctx.bwt_decompress(stream)
+        return unescape(text) if text else b""
 
 
 class LZ78Compressor:

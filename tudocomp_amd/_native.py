@@ -28,6 +28,7 @@ SYMBOLS = [
     "tdc_gpu_arena_bytes", "tdc_gpu_device_memory",
     "tdc_gpu_lcpcomp_compress_keep", "tdc_gpu_stream_fetch", "tdc_gpu_stream_fetch_dev", "tdc_gpu_host_register", "tdc_gpu_host_unregister",
     "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
+    "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
 ]
 
 
@@ -117,6 +118,11 @@ def load():
     L.tdc_gpu_lcpcomp_decompress.argtypes = [vp, vp, sz, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lz78_decompress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lz78_decompress_into.argtypes = [vp, vp, sz, i32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_bwt_compress.argtypes = [vp, vp, sz, pvp, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_bwt_compress_into.argtypes = [vp, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_bwt_decompress.argtypes = [vp, vp, sz, pvp, psz, ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_bwt_decompress_into.argtypes = [vp, vp, sz, vp, sz, psz, ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_bwt_inverse_stage.argtypes = [vp, vp, sz, u32, u32, vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lcpcomp_decompress_coder.argtypes = [vp, vp, sz, ctypes.c_int, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_encode_arith.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]
     L.tdc_gpu_encode_ascii.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]

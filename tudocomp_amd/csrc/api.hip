@@ -363,6 +363,7 @@ const OptionDef OPTIONS[] = {
     { "dec_parse",        [](Ctx& c, long v) { c.dec_parse = clampi(v, 0, 2); } },
     { "dec_done",         [](Ctx& c, long v) { c.dec_done = v != 0; } },
     { "dec_log",          [](Ctx& c, long v) { c.dec_log = v != 0; } },
+    { "bwt_log",          [](Ctx& c, long v) { c.bwt_log = v != 0; } },
     { "window_force_fail",[](Ctx& c, long v) { c.window_force_fail = v ? 1 : 0; } },
     { "window_large",     [](Ctx& c, long v) { c.window_large_lists = v ? 1 : 0; } },
     { "window_src",       [](Ctx& c, long v) { c.window_src = v ? 1 : 0; } },
@@ -600,6 +601,83 @@ int tdc_gpu_lcpcomp_compress_dev(tdc_gpu_ctx* ctx, const void* d_text, size_t n,
 }
 
 namespace {
+// The text of a host-buffer call on its way to the device (n + 64 bytes from the arena).  Texts of 64 MiB and more travel in chunks on the
+// copy stream with device work behind every chunk; the caller releases the top of the arena and the WPre state when its suffix array
+// is done (PreGuard).
+u8* upload_text(Ctx& c, const uint8_t* text, size_t n) {
+    u8* d_text = c.arena.get<u8>(n + 64);
+    if (n >= ((size_t)1 << 26)) {
+        // The upload in chunks on the copy stream.  Behind every chunk, on the compute stream: its byte histogram (sentinel check,
+        // symbol codes) and -- texts that take the wide suffix sort -- level 1 of that sort for the chunk in front of it (a key reads
+        // up to 64 bytes ahead), with the code map and the splitters taken from chunk 0 (prim.hpp WPre).  All copies are queued
+        // first: the one host wait in between (the histogram of chunk 0) does not stall them.
+        u32* d_hist = c.arena.get<u32>(256);
+        HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * sizeof(u32), c.stream));
+        c.wait_for(c.copy_stream, c.stream);                                // (the copy stream starts behind whatever the compute stream did before)
+        const bool try_pre = c.wsort_overlap && c.wpre && wsort_applicable(c, n);
+        const size_t CH = try_pre ? (size_t)c.upload_chunks : 8;
+        // Chunk boundaries (multiples of 4096).  With level 1 behind the copies the last three chunks shrink geometrically (0.6, 0.36,
+        // 0.22 of the others): level 1 of a chunk runs 1.7 x as fast as its copy, so each of them is done before the next, shorter copy
+        // ends, and what is left behind the last copy is the level 1 of a fifth of a chunk.
+        std::vector<size_t> coff;
+        {
+            std::vector<double> w(CH, 1.0);
+            if (try_pre) {                                   // (the last chunks shrink geometrically: options upload_tail_n / upload_tail_pct)
+                const size_t T = std::min<size_t>((size_t)c.upload_tail_n, CH - 1);
+                double f = 1.0;
+                for (size_t k = 0; k < T; ++k) { f *= (double)c.upload_tail_pct / 100.0; w[CH - T + k] = f; }
+            }
+            double tot = 0; for (double x : w) tot += x;
+            coff.push_back(0);
+            double acc = 0;
+            for (size_t k = 0; k + 1 < CH; ++k) {
+                acc += w[k];
+                size_t o = ((size_t)((double)n * (acc / tot)) + 4095) & ~(size_t)4095;
+                if (o <= coff.back()) o = coff.back() + 4096;
+                if (o >= n) break;
+                coff.push_back(o);
+            }
+            coff.push_back(n);
+        }
+        const size_t nch = coff.size() - 1;
+        if (nch > Ctx::CHUNK_EVENTS) throw HipError{hipErrorUnknown, "upload: more chunks than chunk events", (int)__LINE__};
+        size_t queued = 0;                                                  // copies handed to the copy stream so far
+        auto queue_copies = [&](size_t upto) {                              // (a few chunks ahead of the compute stream's work, not all at once:
+            for (; queued < nch && queued < upto; ++queued) {               //  the runtime batches what it is given in one go)
+                // (a copy takes the first 64 bytes of the next chunk along -- a key reads that far ahead --, so level 1 of a chunk
+                //  can start as soon as the chunk itself is there: behind the last copy one chunk's level 1 is left, not two)
+                //  -- and a copy starts behind the 64 bytes its predecessor delivered: no byte is written twice while level 1 reads it)
+                const size_t off = coff[queued] + (queued ? 64 : 0), end = std::min(coff[queued + 1] + 64, n);
+                if (end > off) HIP_TRY(hipMemcpyAsync(d_text + off, text + off, end - off, hipMemcpyHostToDevice, c.copy_stream));
+                HIP_TRY(hipEventRecord(c.ev_chunk[queued], c.copy_stream));
+                (void)hipStreamQuery(c.copy_stream);                        // (submit now)
+            }
+        };
+        bool pre_on = false;
+        for (size_t q = 0; q < nch; ++q) {
+            const size_t off = coff[q], len = coff[q + 1] - off;
+            queue_copies(q + 4);
+            HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_chunk[q], 0));
+            text_histogram_add(c, d_text + off, len, d_hist);
+            if (q == 0 && try_pre) {
+                u32 h0[256];
+                c.read_n(d_hist, h0, 256);                                 // (waits for chunk 0 only; chunks 1 .. 3 are on their way)
+                pre_on = wsort_pre_begin(c, *c.wpre, d_text, n, coff.data(), (u32)nch, h0);
+                if (!pre_on) c.arena.release_top();
+            }
+            if (pre_on) wsort_pre_chunk(c, *c.wpre, (u32)q);
+        }
+        text_histogram_finish(c, d_text, n, d_hist);
+        if (pre_on) {
+            wsort_pre_finish(c, *c.wpre, c.hist_cache);
+            if (!c.wpre->active) c.arena.release_top();                      // chunk 0 did not show every byte value: the classic order of things
+        }
+    } else HIP_TRY(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c.stream));
+    return d_text;
+}
+// on every exit path of a call that ran upload_text(): level 1 of the suffix sort done behind the upload is forgotten
+struct PreGuard { Ctx& c; ~PreGuard() { if (c.wpre) { c.wpre->active = false; c.wpre->begun = false; } c.arena.release_top(); } };
+
 // Host buffers in, host buffer out: H2D, (escape,) the whole pipeline, D2H.  The output goes either into a malloc'd buffer
 // (*ho.out) or into the caller's buffer ho.into of ho.cap bytes; copies from / to pinned memory (tdc_gpu_host_alloc) run at
 // PCIe speed, pageable memory is staged by the runtime.
@@ -639,74 +717,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
         d_text = c.arena.get<u8>(tn + 64);
         if (escape_device(c, d_raw, n, d_text) != tn) throw HipError{hipErrorUnknown, "escape: length mismatch", (int)__LINE__};
     } else {
-        d_text = c.arena.get<u8>(n + 64);
-        if (n >= ((size_t)1 << 26)) {
-            // The upload in chunks on the copy stream.  Behind every chunk, on the compute stream: its byte histogram (sentinel check,
-            // symbol codes) and -- texts that take the wide suffix sort -- level 1 of that sort for the chunk in front of it (a key reads
-            // up to 64 bytes ahead), with the code map and the splitters taken from chunk 0 (prim.hpp WPre).  All copies are queued
-            // first: the one host wait in between (the histogram of chunk 0) does not stall them.
-            u32* d_hist = c.arena.get<u32>(256);
-            HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * sizeof(u32), c.stream));
-            c.wait_for(c.copy_stream, c.stream);                                // (the copy stream starts behind whatever the compute stream did before)
-            const bool try_pre = c.wsort_overlap && c.wpre && wsort_applicable(c, n);
-            const size_t CH = try_pre ? (size_t)c.upload_chunks : 8;
-            // Chunk boundaries (multiples of 4096).  With level 1 behind the copies the last three chunks shrink geometrically (0.6, 0.36,
-            // 0.22 of the others): level 1 of a chunk runs 1.7 x as fast as its copy, so each of them is done before the next, shorter copy
-            // ends, and what is left behind the last copy is the level 1 of a fifth of a chunk.
-            std::vector<size_t> coff;
-            {
-                std::vector<double> w(CH, 1.0);
-                if (try_pre) {                                   // (the last chunks shrink geometrically: options upload_tail_n / upload_tail_pct)
-                    const size_t T = std::min<size_t>((size_t)c.upload_tail_n, CH - 1);
-                    double f = 1.0;
-                    for (size_t k = 0; k < T; ++k) { f *= (double)c.upload_tail_pct / 100.0; w[CH - T + k] = f; }
-                }
-                double tot = 0; for (double x : w) tot += x;
-                coff.push_back(0);
-                double acc = 0;
-                for (size_t k = 0; k + 1 < CH; ++k) {
-                    acc += w[k];
-                    size_t o = ((size_t)((double)n * (acc / tot)) + 4095) & ~(size_t)4095;
-                    if (o <= coff.back()) o = coff.back() + 4096;
-                    if (o >= n) break;
-                    coff.push_back(o);
-                }
-                coff.push_back(n);
-            }
-            const size_t nch = coff.size() - 1;
-            if (nch > Ctx::CHUNK_EVENTS) throw HipError{hipErrorUnknown, "upload: more chunks than chunk events", (int)__LINE__};
-            size_t queued = 0;                                                  // copies handed to the copy stream so far
-            auto queue_copies = [&](size_t upto) {                              // (a few chunks ahead of the compute stream's work, not all at once:
-                for (; queued < nch && queued < upto; ++queued) {               //  the runtime batches what it is given in one go)
-                    // (a copy takes the first 64 bytes of the next chunk along -- a key reads that far ahead --, so level 1 of a chunk
-                    //  can start as soon as the chunk itself is there: behind the last copy one chunk's level 1 is left, not two)
-                    //  -- and a copy starts behind the 64 bytes its predecessor delivered: no byte is written twice while level 1 reads it)
-                    const size_t off = coff[queued] + (queued ? 64 : 0), end = std::min(coff[queued + 1] + 64, n);
-                    if (end > off) HIP_TRY(hipMemcpyAsync(d_text + off, text + off, end - off, hipMemcpyHostToDevice, c.copy_stream));
-                    HIP_TRY(hipEventRecord(c.ev_chunk[queued], c.copy_stream));
-                    (void)hipStreamQuery(c.copy_stream);                        // (submit now)
-                }
-            };
-            bool pre_on = false;
-            for (size_t q = 0; q < nch; ++q) {
-                const size_t off = coff[q], len = coff[q + 1] - off;
-                queue_copies(q + 4);
-                HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_chunk[q], 0));
-                text_histogram_add(c, d_text + off, len, d_hist);
-                if (q == 0 && try_pre) {
-                    u32 h0[256];
-                    c.read_n(d_hist, h0, 256);                                 // (waits for chunk 0 only; chunks 1 .. 3 are on their way)
-                    pre_on = wsort_pre_begin(c, *c.wpre, d_text, n, coff.data(), (u32)nch, h0);
-                    if (!pre_on) c.arena.release_top();
-                }
-                if (pre_on) wsort_pre_chunk(c, *c.wpre, (u32)q);
-            }
-            text_histogram_finish(c, d_text, n, d_hist);
-            if (pre_on) {
-                wsort_pre_finish(c, *c.wpre, c.hist_cache);
-                if (!c.wpre->active) c.arena.release_top();                      // chunk 0 did not show every byte value: the classic order of things
-            }
-        } else HIP_TRY(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c.stream));
+        d_text = upload_text(c, text, n);
     }
     const int e1 = ev.tick();
     u8* d_out = nullptr;
@@ -715,7 +726,7 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
         ~SinkGuard() { c.d2h_host = nullptr; c.d2h_cap = 0; c.d2h_done = 0; }
     } sink_guard{c};
     c.d2h_host = ho.into; c.d2h_cap = ho.into ? ho.cap : 0; c.d2h_done = 0;      // the encoder may start the D2H while it still packs
-    struct PreGuard { Ctx& c; ~PreGuard() { if (c.wpre) { c.wpre->active = false; c.wpre->begun = false; } c.arena.release_top(); } } pre_guard{c};
+    PreGuard pre_guard{c};
     const size_t len = run_pipeline(c, d_text, tn, threshold, flatten, coder, &d_out, 0, stats, ev, comp);
     const int e2 = ev.tick();
     *ho.out_len = len;
@@ -1153,6 +1164,119 @@ int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t
         DecodeOut o;
         o.into = out; o.cap = out_cap;
         lz78_decompress_common(ctx, stream, len, coder, o, out_len, phrases, rounds);
+    });
+}
+
+// ---- bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------------------------------------------------
+namespace {
+void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, HostOut ho, tdc_gpu_stats* stats) {
+    if (!ho.out_len || (!ho.out && !ho.into)) throw ArgError{TDC_GPU_ERR_ARG, "out/out_len is NULL"};
+    check_text_args(text, n);
+    if (text[n - 1] != 0) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "text does not end with a 0 sentinel"};
+    *ho.out_len = n;
+    if (ho.into && ho.cap < n) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    reserve_arena(c, arena_need(c, n));
+    Events ev(c);
+    const int e0 = ev.tick();
+    PreGuard pre_guard{c};
+    u8* d_text = upload_text(c, text, n);
+    const int e1 = ev.tick();
+    validate_device_text(c, d_text, n);
+    // the suffix array as tdc_gpu_suffix_array builds it; with the sink of the wide path the inverse suffix array is not materialised
+    u32* d_sa = c.arena.get<u32>(n);
+    u32* d_isa = c.arena.get<u32>(n);
+    SAStats ss;
+    SAExtra ex;
+    ex.lcp8 = c.arena.get<u8>(n + 64);
+    const int e2 = ev.tick();
+    build_suffix_array(c, d_text, n, d_sa, d_isa, &ss, &ex);
+    const int e3 = ev.tick();
+    u8* d_out = (u8*)d_isa;                                  // (the ranks are not needed: the transform takes their place)
+    HostBuf h(ho.into ? 1 : n);
+    u8* dst = ho.into ? ho.into : h.as<u8>();
+    const bool sent = bwt_gather(c, d_text, d_sa, n, d_out, dst);
+    const int e4 = ev.tick();
+    if (!sent) HIP_TRY(hipMemcpyAsync(dst, d_out, n, hipMemcpyDeviceToHost, c.stream));
+    const int e5 = ev.tick();
+    if (stats) {
+        stats->n = n; stats->out_len = n;
+        stats->sa_rounds = ss.rounds; stats->sa_init_syms = ss.init_syms; stats->sa_sorted_elems = ss.sorted_elems;
+        stats->sa_key_words = ss.wide_kw; stats->sa_text_rounds = ss.text_rounds; stats->sa_mode = (uint32_t)ex.mode; stats->sa_overlapped = ss.overlapped;
+        stats->sa_star_chains = (uint32_t)std::min<u64>(ss.star_chains, 0xFFFFFFFFull);
+        stats->arena_bytes = c.arena.high;
+        // ms_encode: the gather (with a page-locked destination the downloads of its chunks run inside it, and ms_d2h is what is left: nothing)
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_sa, e2, e3); ev.span(&stats->ms_encode, e3, e4); ev.span(&stats->ms_d2h, e4, e5);
+        ev.span(&stats->ms_total, e0, e5);
+    }
+    ev.finish();
+    if (!ho.into) *ho.out = h.release<uint8_t>();
+}
+
+void bwt_decompress_common(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, DecodeOut& o, size_t* out_len,
+                           uint32_t* host_lf, BwtInvStats* bs) {
+    if ((!bwt && len) || !out_len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (len >= 0x7FFFFFFFull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "bwt: the buffer must be shorter than 2^31 - 1 bytes (32-bit len_t)"};
+    if (o.into && len > 1 && o.cap < len) {
+        *out_len = len;
+        throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+    }
+    size_t n = 0;
+    try { n = bwt_inverse(ctx->c, bwt, len, sample, max_steps, o, host_lf, bs); }
+    catch (const StreamFormatError& e) { free(o.owned); o.owned = nullptr; throw ArgError{TDC_GPU_ERR_ARG, e.what}; }
+    catch (const DecodeTooLarge&) { free(o.owned); o.owned = nullptr; throw ArgError{TDC_GPU_ERR_TOO_LARGE, "bwt: buffer too large"}; }
+    catch (...) { free(o.owned); o.owned = nullptr; throw; }
+    *out_len = n;
+}
+}  // namespace
+
+int tdc_gpu_bwt_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t** out, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { bwt_compress_host(ctx, text, n, HostOut{out, nullptr, 0, out_len}, stats); });
+}
+
+int tdc_gpu_bwt_compress_into(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t* out, size_t out_cap, size_t* out_len,
+                              tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        bwt_compress_host(ctx, text, n, HostOut{nullptr, out, out_cap, out_len}, stats);
+    });
+}
+
+int tdc_gpu_bwt_decompress(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t** out, size_t* out_len, uint32_t* rounds) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+        DecodeOut o;
+        BwtInvStats bs;
+        bwt_decompress_common(ctx, bwt, len, 0, 0, o, out_len, nullptr, rounds ? &bs : nullptr);
+        if (rounds) *rounds = bs.rounds;
+        *out = o.owned;
+    });
+}
+
+int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t* out, size_t out_cap, size_t* out_len,
+                                uint32_t* rounds) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        DecodeOut o;
+        o.into = out; o.cap = out_cap;
+        BwtInvStats bs;
+        bwt_decompress_common(ctx, bwt, len, 0, 0, o, out_len, nullptr, rounds ? &bs : nullptr);
+        if (rounds) *rounds = bs.rounds;
+    });
+}
+
+int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
+                              uint32_t* lf, uint64_t* heads, uint32_t* launches) {
+    return guarded(ctx, [&] {
+        if (!out && len > 1) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        DecodeOut o;
+        o.into = out; o.cap = len;
+        size_t n = 0;
+        BwtInvStats bs;
+        bwt_decompress_common(ctx, bwt, len, sample, max_steps, o, &n, lf, &bs);
+        if (heads) *heads = bs.heads;
+        if (launches) *launches = bs.launches;
     });
 }
 

@@ -188,4 +188,18 @@ size_t lz78_parse_host(const u8* in, size_t n, std::vector<u32>& ids, std::vecto
 // a16: coders/EliasGammaCoder.hpp:26-29 + io/BitOStream.hpp:105-129 on the device; returns the stream length
 size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap);
 
+// ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
+// forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform
+// goes afterwards.  True: it is on its way there already, chunk by chunk on the copy stream behind the gather (page-locked memory, texts
+// of 128 MiB and more), and c.stream waits for the last copy; false: the caller downloads d_out.
+bool bwt_gather(Ctx& c, const u8* d_text, const u32* d_sa, size_t n, u8* d_out, u8* host_dst);
+// inverse (decode_bwt with the complete C table): LF by a stable counting rank, then list ranking of its one cycle from sampled heads.
+// sample = expected rows per list, max_steps = most steps a walk takes per launch (0: BWT_SAMPLE, BWT_STEPS_PER_SAMPLE x sample).
+// `bwt` is a host buffer; the text goes to decode_dest(out, len); host_lf (nullable, len entries) receives the LF table.  Inputs of at
+// most one byte decode to nothing.  A buffer that is no transform (not exactly one 0 byte, LF not one cycle): StreamFormatError;
+// len >= 2^31 - 1: DecodeTooLarge; out.into too small: HipError hipErrorOutOfMemory -- each before anything is written to `out`.
+constexpr u32 BWT_SAMPLE = 256, BWT_STEPS_PER_SAMPLE = 4;
+struct BwtInvStats { u64 heads = 0; u32 launches = 0, rounds = 0, longest = 0, sample = 0, max_steps = 0; };
+size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, DecodeOut& out, u32* host_lf, BwtInvStats* st);
+
 }  // namespace tdc

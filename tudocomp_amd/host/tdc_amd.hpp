@@ -457,6 +457,57 @@ public:
     }
 };
 
+// tdc::BWTCompressor (compressors/BWTCompressor.hpp:14-67, ds/bwt.hpp): the Burrows-Wheeler transform of the escaped, 0-terminated view;
+// n bytes out, no header.
+class BWTCompressor : public Compressor {
+    AlgorithmValue m_opts;
+    std::shared_ptr<GpuContext> m_ctx;
+    int m_device = 0;
+public:
+    tdc_gpu_stats last_stats{};
+    void set_device(int d) { m_device = d; }
+    BWTCompressor(AlgorithmValue opts, std::shared_ptr<GpuContext> ctx) : m_opts(std::move(opts)), m_ctx(std::move(ctx)) {}   // (textds: accepted, ignored)
+    InputRestrictions input_restrictions() const override { return {true, true}; }   // uses_textds (BWTCompressor.hpp:23)
+    void compress(Input& input, Output& output) override {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const bytes view = input.as_view();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_bwt_compress(m_ctx->h, view.data(), view.size(), &out, &out_len, &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
+    }
+    // decode_bwt (ds/bwt.hpp:77-98): LF[i] = C[b[i]] + rank of b[i] among the equal bytes in front; n - 1 steps from row 0, then the 0.
+    // C is accumulated over ALL byte values here (the reference's loop stops in front of 255, which breaks texts that hold 0xFF --
+    // every escaped 0x00 or 0xFF byte).  Like the reference the host loop does not look at what it is given beyond staying inside the
+    // buffer.  dec=gpu: LF and the list ranking of its cycle on the device (tdc_gpu_bwt_decompress), which refuses what is no transform.
+    void decompress(Input& input, Output& output) override {
+        const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_bwt_decompress(m_ctx->h, in.data(), in.size(), &out, &out_len, nullptr);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
+        const size_t n = in.size();
+        if (n <= 1) return;
+        if (n >= 0x7FFFFFFFull) throw std::runtime_error("bwt: input too large (32-bit len_t)");
+        size_t C[257] = {0};
+        for (size_t i = 0; i < n; ++i) ++C[in[i] + 1];
+        for (int c = 0; c < 256; ++c) C[c + 1] += C[c];
+        std::vector<uint32_t> lf(n);
+        for (size_t i = 0; i < n; ++i) lf[i] = (uint32_t)C[in[i]]++;
+        bytes text(n);
+        size_t i = 0;
+        for (size_t j = 1; j < n; ++j) { text[n - 1 - j] = in[i]; i = lf[i]; }
+        text[n - 1] = 0;
+        output.write(text.data(), text.size());
+    }
+};
+
 // ---- registry (what is actually registered; Registry.hpp:204-231) ---------------------------------------------
 struct Selection {
     std::string id_string;
@@ -475,7 +526,9 @@ inline std::vector<std::string> registered_algorithms() {
              "lcpcomp(coder=arithmetic, comp=arrays, threshold=5, flatten=1)              [MI355X, compress only]",
              "lzss_lcp(coder=huff, threshold=3)                                           [MI355X, libtdc_gpu.so]",
              "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]",
-             "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]" };
+             "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]",
+             "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
+             "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]" };
 }
 
 inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuContext> ctx = nullptr, int device = 0) {
@@ -485,6 +538,13 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
     if (av.name == "lz78") {
         auto z = std::make_unique<LZ78Compressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dec"}), std::move(ctx));
         z->set_device(device);
+        s.compressor = std::move(z);
+        return s;
+    }
+    if (av.name == "bwt") {
+        auto z = std::make_unique<BWTCompressor>(parse_algorithm_id(id, {"textds", "dec"}), std::move(ctx));
+        z->set_device(device);
+        s.restrictions = z->input_restrictions();
         s.compressor = std::move(z);
         return s;
     }
