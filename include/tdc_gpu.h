@@ -81,6 +81,10 @@ typedef struct {
     uint32_t probes;            /* skip-ahead probes over runs of erased levels (arrays, max_lcp)                              */
     uint32_t max_push_targets;  /* most target levels the pushes of one level went to (arrays, max_lcp)                        */
     uint64_t d2h_early;         /* tdc_gpu_lcpcomp_compress_into: stream bytes copied to `out` while the pack still ran            */
+    uint32_t pipe_stages;       /* tdc_gpu_pipeline_compress: number of stages, ...                                                 */
+    uint32_t pipe_reserved;
+    uint64_t pipe_len[8];       /* ... the length in bytes behind stage i, ...                                                      */
+    float    pipe_ms[8];        /* ... and what stage i took (host clock around a synchronisation; only with option pipe_log)       */
 } tdc_gpu_stats;
 
 /* ---- context -------------------------------------------------------------------------------------------- */
@@ -288,6 +292,50 @@ int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len
  * in the end, launches of the first walk. */
 int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
                               uint32_t* lf, uint64_t* heads, uint32_t* launches);
+
+/* ---- rle, mtf, encode(huff) and chains of them behind bwt: the reference's `bwtzip = bwt:rle:mtf:encode(huff)`
+ * (etc/compare-suites/default.suite).  A pipeline is a sequence of 1 .. 8 stages; every stage's whole output is the
+ * next stage's input (tudocomp_driver/ChainCompressor.hpp: `a:b:c` = chain(chain(a, b), c)) and stays in device memory, only the last
+ * one is downloaded.  One stage alone is a valid pipeline: that is how the three single compressors are reached.
+ *   TDC_GPU_STAGE_BWT   BWTCompressor::compress (compressors/BWTCompressor.hpp:29-44).  Only as the FIRST stage: its input is the escaped,
+ *                       0-terminated view, with the contract and the error codes of tdc_gpu_bwt_compress.
+ *   TDC_GPU_STAGE_RLE   RunLengthEncoder::compress (compressors/RunLengthEncoder.hpp:15-32, util/vbyte.hpp:28-37), param = its option
+ *                       `offset`.  The reference's loop compares a signed char with istream::peek(): a run of k bytes below 0x80 becomes
+ *                       `c c vbyte(k - 2 + offset)`, bytes from 0x80 up never extend a run (every repeated one becomes `c vbyte(offset)`).
+ *                       On an input that ends in 0xFF 0xFF the reference does not terminate; this library emits what it emits for such bytes
+ *                       in mid-stream, which the reference's decoder decodes.
+ *   TDC_GPU_STAGE_MTF   MTFCompressor::compress (compressors/MTFCompressor.hpp:16-33): move-to-front ranks, list 0 .. 255 at the start.
+ *   TDC_GPU_STAGE_HUFF  LiteralEncoder<HuffmanCoder>::compress (compressors/LiteralEncoder.hpp:23-32): the algorithm `encode(huff)`.
+ * Inputs of up to 2^32 - 2 bytes (bwt: < 2^31 - 1); a stage whose output would be longer fails with TDC_GPU_ERR_TOO_LARGE before it writes.
+ * 0 or more than 8 stages, an unknown kind, bwt behind the first stage, an rle offset above 2^62: TDC_GPU_ERR_ARG. */
+enum { TDC_GPU_STAGE_BWT = 0, TDC_GPU_STAGE_RLE = 1, TDC_GPU_STAGE_MTF = 2, TDC_GPU_STAGE_HUFF = 3 };
+#define TDC_GPU_PIPELINE_MAX_STAGES 8
+typedef struct { int kind; uint64_t param; } tdc_gpu_stage;      /* param: rle offset, 0 for the other kinds */
+/* worst-case output length of the pipeline on n input bytes (what an _into buffer needs at most); 0 for an invalid pipeline or one
+ * whose worst case passes 2^32 - 2 bytes */
+size_t tdc_gpu_pipeline_bound(const tdc_gpu_stage* stages, int nstages, size_t n);
+/* stats (nullable): n, out_len, pipe_stages, pipe_len[], pipe_ms[] (option pipe_log), ms_total, arena_bytes, and for a leading bwt the
+ * fields tdc_gpu_bwt_compress fills. */
+int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t** out,
+                              size_t* out_len, tdc_gpu_stats* stats);
+/* into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small.  The download runs
+ * on the copy stream (page-locked memory -- tdc_gpu_host_alloc -- receives it at the host link's rate). */
+int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
+                                   size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
+/* Inverse, stage by stage from the last one: rle, mtf and encode(huff) are decoded by the host loops below, a leading bwt by
+ * tdc_gpu_bwt_decompress on the device (*out then holds the escaped, 0-terminated text).  Malformed input: TDC_GPU_ERR_ARG. */
+int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len, uint8_t** out,
+                                size_t* out_len);
+int tdc_gpu_pipeline_decompress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
+                                     uint8_t* out, size_t out_cap, size_t* out_len);
+/* The host decoders (no context, no GPU): rle_decode (RunLengthEncoder.hpp:36-50), MTFCompressor::decompress (MTFCompressor.hpp:35-43,
+ * 60-68), LiteralEncoder::decompress (LiteralEncoder.hpp:34-41 with HuffmanCoder::Decoder).  out == NULL: nothing is written and *out_len
+ * receives the decoded length.  Otherwise at most out_cap bytes are written; a text that does not fit is refused like malformed input
+ * (*out_len still receives its length).  TDC_GPU_ERR_ARG for: a vbyte that runs off the end of the input or is longer than ten bytes, a
+ * vbyte below `offset`, a Huffman header that is cut off or inconsistent, a code outside the table. */
+int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len);
+int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
+int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
 
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _native
-from ._native import Stats, LIB_PATH, SYMBOLS  # noqa: F401
+from ._native import Stats, Stage, LIB_PATH, SYMBOLS  # noqa: F401
 
 CODER_HUFF = 0
 CODER_GAMMA = 1
@@ -20,6 +20,10 @@ COMP_ARRAYS = 0
 COMP_PLCPPEAKS = 1
 COMP_MAXLCP = 2
 COMP_HEAP = 3
+STAGE_BWT = 0            # stages of a pipeline (tdc_gpu_stage.kind): a stage is a kind or (STAGE_RLE, offset)
+STAGE_RLE = 1
+STAGE_MTF = 2
+STAGE_HUFF = 3
 
 
 class TdcGpuError(RuntimeError):
@@ -111,6 +115,51 @@ def huffman_table(counts):
     if rc:
         raise TdcGpuError(rc)
     return {"sigma": sigma.value, "longest": longest.value, "order": order, "len_of": len_of, "code_of": code_of}
+
+
+def _stages(stages):
+    """[kind | (kind, param), ...] -> (tdc_gpu_stage array, count)"""
+    items = [(s, 0) if isinstance(s, int) else (int(s[0]), int(s[1])) for s in stages]
+    arr = (Stage * max(len(items), 1))()
+    for i, (k, p) in enumerate(items):
+        arr[i].kind, arr[i].param = k, p
+    return arr, len(items)
+
+
+def pipeline_bound(stages, n):
+    """worst-case output length of the pipeline on n bytes (0: invalid pipeline, or a worst case above 2^32 - 2 bytes)"""
+    arr, k = _stages(stages)
+    return _native.load().tdc_gpu_pipeline_bound(arr, k, n)
+
+
+def _host_decode(fn, data, *args):
+    """measure, then decode (the host decoders of the C ABI; no GPU)"""
+    L = _native.load()
+    a = _u8(data)
+    n = ctypes.c_size_t()
+    rc = getattr(L, fn)(_ptr(a) if len(a) else None, len(a), *args, None, 0, ctypes.byref(n))
+    if rc:
+        raise TdcGpuError(rc, fn)
+    out = np.empty(max(n.value, 1), dtype=np.uint8)
+    rc = getattr(L, fn)(_ptr(a) if len(a) else None, len(a), *args, _ptr(out), n.value, ctypes.byref(n))
+    if rc:
+        raise TdcGpuError(rc, fn)
+    return out[:n.value].tobytes()
+
+
+def rle_decode(data, offset=0):
+    """rle_decode (compressors/RunLengthEncoder.hpp:36-50) on the host"""
+    return _host_decode("tdc_rle_decode", data, ctypes.c_uint64(offset))
+
+
+def mtf_decode(data):
+    """MTFCompressor::decompress (compressors/MTFCompressor.hpp:35-43) on the host"""
+    return _host_decode("tdc_mtf_decode", data)
+
+
+def huff_decode_literals(data):
+    """LiteralEncoder<HuffmanCoder>::decompress (compressors/LiteralEncoder.hpp:34-41) on the host"""
+    return _host_decode("tdc_huff_decode_literals", data)
 
 
 def device_count():
@@ -448,6 +497,47 @@ class Context:
                                                       _ptr(lf) if want_lf else None, ctypes.byref(h), ctypes.byref(ln)))
         return (out.tobytes() if len(a) > 1 else b""), {"lf": lf, "heads": h.value, "launches": ln.value}
 
+    # ---- rle, mtf, encode(huff) and chains ------------------------------------------------------------------
+    def pipeline_compress(self, stages, data):
+        """stages: [STAGE_* | (STAGE_RLE, offset), ...], intermediates stay on the device.  A leading STAGE_BWT takes the escaped +
+        0-terminated view.  Returns (stream, stats dict with pipe_len / pipe_ms per stage)."""
+        arr, k = _stages(stages)
+        a = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_pipeline_compress(self._h, arr, k, _ptr(a) if len(a) else None, len(a), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)))
+        return self._take(out, n.value), st.as_dict()
+
+    def pipeline_compress_into(self, stages, data, n, out):
+        """pipeline_compress of the first n bytes of `data` into a caller-owned buffer (PinnedBuffer or writable uint8 array): returns
+        (length, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the stream length."""
+        arr, k = _stages(stages)
+        a = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_pipeline_compress_into(self._h, arr, k, _ptr(a), n, _ptr(oa), oa.size, ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
+
+    def pipeline_decompress(self, stages, stream):
+        """inverse of pipeline_compress: host loops for rle, mtf and encode(huff), the device inverse for a leading bwt"""
+        arr, k = _stages(stages)
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.tdc_gpu_pipeline_decompress(self._h, arr, k, _ptr(a) if len(a) else None, len(a), ctypes.byref(p), ctypes.byref(n)))
+        return self._take(p, n.value)
+
+    def pipeline_decompress_into(self, stages, stream, out, n=None):
+        """pipeline_decompress of the first n bytes of `stream` (default: all) into a caller-owned buffer: returns the text length"""
+        arr, k = _stages(stages)
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol = ctypes.c_size_t()
+        rc = self._L.tdc_gpu_pipeline_decompress_into(self._h, arr, k, _ptr(a), len(a) if n is None else n, _ptr(oa), oa.size, ctypes.byref(ol))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value
+
     def blocks_decompress(self, blob, coder=CODER_HUFF):
         """inverse of blocks_compress on this context's device: the concatenated raw bytes"""
         a = _u8(blob)
@@ -546,6 +636,71 @@ class BWTCompressor:
     def decompress(self, stream):
         text, _ = self.ctx.bwt_decompress(stream)
         return unescape(text) if text else b""
+
+
+def parse_chain(spec):
+    """`a:b:c` (util/algorithm_parser/AlgorithmAST.hpp:119-129: chain(chain(a, b), c)) -> stage list; a, b, c out of bwt, rle,
+    rle(offset=N), mtf, encode(huff)"""
+    import re
+    stages = []
+    for part in str(spec).replace(" ", "").split(":"):
+        m = re.fullmatch(r"rle(?:\((?:offset=(\d+))?\))?", part)
+        if m:
+            stages.append((STAGE_RLE, int(m.group(1) or 0)))
+        elif part in ("bwt", "bwt()"):
+            stages.append((STAGE_BWT, 0))
+        elif part in ("mtf", "mtf()"):
+            stages.append((STAGE_MTF, 0))
+        elif part in ("encode(huff)", "encode(coder=huff)", "encode"):
+            stages.append((STAGE_HUFF, 0))
+        else:
+            raise RuntimeError("No implementation found for compressor %s" % part)
+    return stages
+
+
+class ChainCompressor:
+    """Mirror of tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) for chains of bwt, rle, mtf and encode(huff), e.g. the
+    reference's bwtzip = "bwt:rle:mtf:encode(huff)": every stage's whole output is the next stage's input, on the device.  Only a
+    leading bwt has input restrictions: its input is escaped + 0-terminated, and unescaped again on the way back."""
+
+    def __init__(self, ctx, spec):
+        self.ctx, self.stages = ctx, parse_chain(spec)
+        self.last_stats = None
+
+    def compress(self, data):
+        lead = self.stages[0][0] == STAGE_BWT
+        out, st = self.ctx.pipeline_compress(self.stages, escape(data) if lead else data)
+        self.last_stats = st
+        return out
+
+    def decompress(self, stream):
+        text = self.ctx.pipeline_decompress(self.stages, stream)
+        if self.stages[0][0] == STAGE_BWT:
+            return unescape(text) if text else b""
+        return text
+
+
+class RunLengthEncoder(ChainCompressor):
+    """Mirror of tdc::RunLengthEncoder (compressors/RunLengthEncoder.hpp:52-74), option offset"""
+
+    def __init__(self, ctx, offset=0):
+        ChainCompressor.__init__(self, ctx, "rle(offset=%d)" % int(offset))
+
+
+class MTFCompressor(ChainCompressor):
+    """Mirror of tdc::MTFCompressor (compressors/MTFCompressor.hpp:45-69)"""
+
+    def __init__(self, ctx):
+        ChainCompressor.__init__(self, ctx, "mtf")
+
+
+class LiteralEncoder(ChainCompressor):
+    """Mirror of tdc::LiteralEncoder<coder> (compressors/LiteralEncoder.hpp:11-42), the algorithm `encode(coder)`; coder huff only"""
+
+    def __init__(self, ctx, coder="huff"):
+        if coder != "huff":
+            raise RuntimeError("No implementation found for compressor encode(coder=%s)" % coder)
+        ChainCompressor.__init__(self, ctx, "encode(huff)")
 
 
 class LZ78Compressor:

@@ -29,6 +29,8 @@ SYMBOLS = [
     "tdc_gpu_lcpcomp_compress_keep", "tdc_gpu_stream_fetch", "tdc_gpu_stream_fetch_dev", "tdc_gpu_host_register", "tdc_gpu_host_unregister",
     "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
     "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
+    "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
+    "tdc_gpu_pipeline_decompress_into", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
 ]
 
 
@@ -43,10 +45,19 @@ class Stats(ctypes.Structure):
         [(k, ctypes.c_uint32) for k in ("small_levels", "purges", "window_pass", "window_lcut",
                                         "sa_key_words", "sa_text_rounds", "sa_mode", "sa_overlapped", "eager_levels", "eager_phases", "sa_star_chains",
                                         "probes", "max_push_targets")] +
-        [("d2h_early", ctypes.c_uint64)])
+        [("d2h_early", ctypes.c_uint64)] +
+        [("pipe_stages", ctypes.c_uint32), ("pipe_reserved", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8)])
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["pipe_len"] = list(self.pipe_len)[:self.pipe_stages]
+        d["pipe_ms"] = list(self.pipe_ms)[:self.pipe_stages]
+        return d
+
+
+class Stage(ctypes.Structure):
+    """tdc_gpu_stage: kind (STAGE_BWT / _RLE / _MTF / _HUFF) and param (the rle offset)"""
+    _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_uint64)]
 
 
 _lib = None
@@ -123,6 +134,16 @@ def load():
     L.tdc_gpu_bwt_decompress.argtypes = [vp, vp, sz, pvp, psz, ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_bwt_decompress_into.argtypes = [vp, vp, sz, vp, sz, psz, ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_bwt_inverse_stage.argtypes = [vp, vp, sz, u32, u32, vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    pst = ctypes.POINTER(Stage)
+    L.tdc_gpu_pipeline_bound.argtypes = [pst, i32, sz]
+    L.tdc_gpu_pipeline_bound.restype = sz
+    L.tdc_gpu_pipeline_compress.argtypes = [vp, pst, i32, vp, sz, pvp, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_pipeline_compress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_pipeline_decompress.argtypes = [vp, pst, i32, vp, sz, pvp, psz]
+    L.tdc_gpu_pipeline_decompress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz]
+    L.tdc_rle_decode.argtypes = [vp, sz, ctypes.c_uint64, vp, sz, psz]
+    L.tdc_mtf_decode.argtypes = [vp, sz, vp, sz, psz]
+    L.tdc_huff_decode_literals.argtypes = [vp, sz, vp, sz, psz]
     L.tdc_gpu_lcpcomp_decompress_coder.argtypes = [vp, vp, sz, ctypes.c_int, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_encode_arith.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]
     L.tdc_gpu_encode_ascii.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]

@@ -3,10 +3,13 @@
 #include "stages.hpp"
 #include "prim.hpp"
 #include "huffman_host.hpp"
+#include "bytestages.hpp"
+#include "../host/tdc_coders.hpp"
 
 #include <new>
 #include <string>
 #include <vector>
+#include <chrono>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
@@ -364,6 +367,7 @@ const OptionDef OPTIONS[] = {
     { "dec_done",         [](Ctx& c, long v) { c.dec_done = v != 0; } },
     { "dec_log",          [](Ctx& c, long v) { c.dec_log = v != 0; } },
     { "bwt_log",          [](Ctx& c, long v) { c.bwt_log = v != 0; } },
+    { "pipe_log",         [](Ctx& c, long v) { c.pipe_log = v != 0; } },
     { "window_force_fail",[](Ctx& c, long v) { c.window_force_fail = v ? 1 : 0; } },
     { "window_large",     [](Ctx& c, long v) { c.window_large_lists = v ? 1 : 0; } },
     { "window_src",       [](Ctx& c, long v) { c.window_src = v ? 1 : 0; } },
@@ -1169,15 +1173,17 @@ int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t
 
 // ---- bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------------------------------------------------
 namespace {
-void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, HostOut ho, tdc_gpu_stats* stats) {
-    if (!ho.out_len || (!ho.out && !ho.into)) throw ArgError{TDC_GPU_ERR_ARG, "out/out_len is NULL"};
+// d_keep (a pipeline's first stage: n + 64 bytes the caller took from the arena it reserved): the transform stays there, nothing is
+// downloaded and `ho` is not used
+void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, HostOut ho, tdc_gpu_stats* stats, u8* d_keep = nullptr) {
+    if (!d_keep && (!ho.out_len || (!ho.out && !ho.into))) throw ArgError{TDC_GPU_ERR_ARG, "out/out_len is NULL"};
     check_text_args(text, n);
     if (text[n - 1] != 0) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "text does not end with a 0 sentinel"};
-    *ho.out_len = n;
-    if (ho.into && ho.cap < n) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+    if (!d_keep) *ho.out_len = n;
+    if (!d_keep && ho.into && ho.cap < n) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
     Ctx& c = ctx->c;
     if (stats) memset(stats, 0, sizeof(*stats));
-    reserve_arena(c, arena_need(c, n));
+    if (!d_keep) reserve_arena(c, arena_need(c, n));
     Events ev(c);
     const int e0 = ev.tick();
     PreGuard pre_guard{c};
@@ -1193,12 +1199,12 @@ void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, HostOut 
     const int e2 = ev.tick();
     build_suffix_array(c, d_text, n, d_sa, d_isa, &ss, &ex);
     const int e3 = ev.tick();
-    u8* d_out = (u8*)d_isa;                                  // (the ranks are not needed: the transform takes their place)
-    HostBuf h(ho.into ? 1 : n);
-    u8* dst = ho.into ? ho.into : h.as<u8>();
+    u8* d_out = d_keep ? d_keep : (u8*)d_isa;                // (the ranks are not needed: the transform takes their place)
+    HostBuf h(ho.into || d_keep ? 1 : n);
+    u8* dst = d_keep ? nullptr : (ho.into ? ho.into : h.as<u8>());
     const bool sent = bwt_gather(c, d_text, d_sa, n, d_out, dst);
     const int e4 = ev.tick();
-    if (!sent) HIP_TRY(hipMemcpyAsync(dst, d_out, n, hipMemcpyDeviceToHost, c.stream));
+    if (!sent && dst) HIP_TRY(hipMemcpyAsync(dst, d_out, n, hipMemcpyDeviceToHost, c.stream));
     const int e5 = ev.tick();
     if (stats) {
         stats->n = n; stats->out_len = n;
@@ -1211,7 +1217,7 @@ void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, HostOut 
         ev.span(&stats->ms_total, e0, e5);
     }
     ev.finish();
-    if (!ho.into) *ho.out = h.release<uint8_t>();
+    if (!ho.into && !d_keep) *ho.out = h.release<uint8_t>();
 }
 
 void bwt_decompress_common(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, DecodeOut& o, size_t* out_len,
@@ -1278,6 +1284,226 @@ int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, 
         if (heads) *heads = bs.heads;
         if (launches) *launches = bs.launches;
     });
+}
+
+// ---- rle, mtf, encode(huff) and chains (bytestages.hip) -----------------------------------------------------------
+namespace {
+bool pipeline_valid(const tdc_gpu_stage* st, int k) {
+    if (!st || k < 1 || k > TDC_GPU_PIPELINE_MAX_STAGES) return false;
+    for (int i = 0; i < k; ++i) {
+        if (st[i].kind < TDC_GPU_STAGE_BWT || st[i].kind > TDC_GPU_STAGE_HUFF) return false;
+        if (st[i].kind == TDC_GPU_STAGE_BWT && i) return false;
+        if (st[i].kind == TDC_GPU_STAGE_RLE && st[i].param > ((u64)1 << 62)) return false;
+    }
+    return true;
+}
+u64 stage_bound(const tdc_gpu_stage& st, u64 n) {
+    const u64 b = st.kind == TDC_GPU_STAGE_RLE ? rle_bound(n, st.param) : st.kind == TDC_GPU_STAGE_HUFF ? huff_literals_bound(n) : n;
+    return std::min<u64>(b, STAGE_MAX_BYTES);                // (a stage that would write more fails before it writes)
+}
+const char* stage_name(int kind) { return kind == TDC_GPU_STAGE_BWT ? "bwt" : kind == TDC_GPU_STAGE_RLE ? "rle" : kind == TDC_GPU_STAGE_MTF ? "mtf" : "encode(huff)"; }
+
+void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t n, HostOut ho, tdc_gpu_stats* stats) {
+    if (!ho.out_len || (!ho.out && !ho.into)) throw ArgError{TDC_GPU_ERR_ARG, "out/out_len is NULL"};
+    if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage (its input is the escaped, 0-terminated view)"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle (offset <= 2^62), mtf or encode(huff)"};
+    if (n > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the input must not be longer than 2^32 - 2 bytes"};
+    const bool lead_bwt = stages[0].kind == TDC_GPU_STAGE_BWT;
+    Ctx& c = ctx->c;
+    const bool plog = c.pipe_log != 0;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto t_last = t_start;
+    float ms[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    auto tick = [&](int i) {                                  // (synchronises: only with the diagnostic option)
+        if (!plog) return;
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        const auto now = std::chrono::steady_clock::now();
+        ms[i] = std::chrono::duration<float, std::milli>(now - t_last).count();
+        t_last = now;
+    };
+    // the arena for the whole call: what the suffix array needs, or every intermediate at its worst case with the stages' scratch
+    u64 need = 0, len = n;
+    for (int i = lead_bwt ? 1 : 0; i < k; ++i) { need += stage_scratch_bound(len) + stage_bound(stages[i], len) + 4096; len = stage_bound(stages[i], len); }
+    need += n + 4096;
+    if (lead_bwt) {
+        check_text_args(in, n);                               // (before the arena is sized from n)
+        need = std::max<u64>(need, arena_need(c, n) + n + 4096);
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    tdc_gpu_stats local;
+    tdc_gpu_stats* st = stats ? stats : &local;
+    reserve_arena(c, need);
+    StageOut cur;
+    cur.d = c.arena.get<u8>(n + 64);
+    cur.len = n;
+    const size_t base_mark = c.arena.mark();
+    u64 lens[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    if (!lead_bwt && n) HIP_TRY(hipMemcpyAsync(cur.d, in, n, hipMemcpyHostToDevice, c.stream));
+    for (int i = 0; i < k; ++i) {
+        try {
+            switch (stages[i].kind) {
+                case TDC_GPU_STAGE_BWT:
+                    bwt_compress_host(ctx, in, n, HostOut{nullptr, nullptr, 0, nullptr}, st, cur.d);
+                    c.arena.release_top();
+                    c.arena.release(base_mark);               // the suffix array's scratch goes back before the byte stages take theirs
+                    break;
+                case TDC_GPU_STAGE_RLE: cur = rle_encode_device(c, cur.d, cur.len, stages[i].param); break;
+                case TDC_GPU_STAGE_MTF: cur = mtf_encode_device(c, cur.d, cur.len); break;
+                default: cur = huff_literals_device(c, cur.d, cur.len); break;
+            }
+        } catch (const StageTooLarge&) {
+            throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: a stage's output would pass 2^32 - 2 bytes"};
+        }
+        lens[i] = cur.len;
+        tick(i);
+    }
+    const size_t out_len = (size_t)cur.len;
+    *ho.out_len = out_len;
+    if (ho.into && ho.cap < out_len) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+    HostBuf h(ho.into ? 1 : out_len);
+    u8* dst = ho.into ? ho.into : h.as<u8>();
+    if (out_len) {
+        c.wait_for(c.copy_stream, c.stream);
+        HIP_TRY(hipMemcpyAsync(dst, cur.d, out_len, hipMemcpyDeviceToHost, c.copy_stream));
+        HIP_TRY(hipStreamSynchronize(c.copy_stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    st->n = n; st->out_len = out_len; st->pipe_stages = (uint32_t)k;
+    for (int i = 0; i < k; ++i) { st->pipe_len[i] = lens[i]; st->pipe_ms[i] = ms[i]; }
+    st->arena_bytes = c.arena.high;
+    st->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (plog) {
+        u64 prev = n;
+        for (int i = 0; i < k; ++i) {
+            fprintf(stderr, "pipe:     %-14s %12llu -> %12llu bytes %9.2f ms\n", stage_name(stages[i].kind), (unsigned long long)prev, (unsigned long long)lens[i], ms[i]);
+            prev = lens[i];
+        }
+        fprintf(stderr, "pipe:     total incl. download %9.2f ms\n", st->ms_total);
+    }
+    if (!ho.into) *ho.out = h.release<uint8_t>();
+}
+
+// host decoder of one stage: `in` -> `out` (at most STAGE_MAX_BYTES)
+void host_stage_decode(const tdc_gpu_stage& st, const std::vector<uint8_t>& in, std::vector<uint8_t>& out) {
+    auto run = [&](uint8_t* o, size_t cap) {
+        tdc_amd::ByteSink sink(o, cap);
+        if (st.kind == TDC_GPU_STAGE_RLE) tdc_amd::rle_decode(in.data(), in.size(), st.param, sink);
+        else if (st.kind == TDC_GPU_STAGE_MTF) tdc_amd::mtf_decode(in.data(), in.size(), sink);
+        else tdc_amd::huff_decode_literals(in.data(), in.size(), sink);
+        return sink.n;
+    };
+    try {
+        if (st.kind == TDC_GPU_STAGE_MTF) out.resize(in.size());
+        else {
+            const u64 need = run(nullptr, 0);
+            if (need > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: a stage decodes to more than 2^32 - 2 bytes"};
+            out.resize((size_t)need);
+        }
+        run(out.data(), out.size());
+    } catch (const std::runtime_error&) {
+        throw ArgError{TDC_GPU_ERR_ARG, "pipeline: malformed stream"};
+    }
+}
+
+void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, DecodeOut& o, size_t* out_len) {
+    if ((!in && len) || !out_len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf or encode(huff)"};
+    if (len > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the stream must not be longer than 2^32 - 2 bytes"};
+    const bool plog = ctx->c.pipe_log != 0;
+    std::vector<uint8_t> a(in, in + len), b;
+    for (int i = k - 1; i >= (stages[0].kind == TDC_GPU_STAGE_BWT ? 1 : 0); --i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        host_stage_decode(stages[i], a, b);
+        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (host)\n", stage_name(stages[i].kind), b.size(), a.size(),
+                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        a.swap(b);
+    }
+    if (stages[0].kind == TDC_GPU_STAGE_BWT) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bwt_decompress_common(ctx, a.data(), a.size(), 0, 0, o, out_len, nullptr, nullptr);
+        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (device)\n", "bwt", *out_len, a.size(),
+                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return;
+    }
+    *out_len = a.size();
+    if (o.into) {
+        if (o.cap < a.size()) throw ArgError{TDC_GPU_ERR_OOM, "output buffer too small (*out_len holds the required size)"};
+        if (!a.empty()) memcpy(o.into, a.data(), a.size());
+    } else {
+        o.owned = (u8*)malloc(a.size() ? a.size() : 1);
+        if (!o.owned) throw std::bad_alloc();
+        if (!a.empty()) memcpy(o.owned, a.data(), a.size());
+    }
+}
+
+int host_decode_entry(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len, const std::function<void(tdc_amd::ByteSink&)>& f) {
+    if ((!in && len) || !out_len) return TDC_GPU_ERR_ARG;
+    try {
+        tdc_amd::ByteSink sink(out, out_cap);
+        f(sink);
+        *out_len = sink.n > (u64)SIZE_MAX ? SIZE_MAX : (size_t)sink.n;
+        return out && sink.n > out_cap ? TDC_GPU_ERR_ARG : TDC_GPU_OK;
+    } catch (const std::runtime_error&) { return TDC_GPU_ERR_ARG;
+    } catch (...) { return TDC_GPU_ERR_INTERNAL; }
+}
+}  // namespace
+
+size_t tdc_gpu_pipeline_bound(const tdc_gpu_stage* stages, int nstages, size_t n) {
+    if (!pipeline_valid(stages, nstages) || n > STAGE_MAX_BYTES) return 0;
+    u64 len = n;
+    for (int i = 0; i < nstages; ++i) {
+        const u64 b = stages[i].kind == TDC_GPU_STAGE_RLE ? rle_bound(len, stages[i].param) : stages[i].kind == TDC_GPU_STAGE_HUFF ? huff_literals_bound(len) : len;
+        if (b > STAGE_MAX_BYTES) return 0;
+        len = b;
+    }
+    return (size_t)len;
+}
+
+int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t** out,
+                              size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { pipeline_compress_host(ctx, stages, nstages, in, n, HostOut{out, nullptr, 0, out_len}, stats); });
+}
+
+int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
+                                   size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        pipeline_compress_host(ctx, stages, nstages, in, n, HostOut{nullptr, out, out_cap, out_len}, stats);
+    });
+}
+
+int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len, uint8_t** out,
+                                size_t* out_len) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+        DecodeOut o;
+        pipeline_decompress_host(ctx, stages, nstages, in, len, o, out_len);
+        *out = o.owned;
+    });
+}
+
+int tdc_gpu_pipeline_decompress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
+                                     uint8_t* out, size_t out_cap, size_t* out_len) {
+    return guarded(ctx, [&] {
+        if (!out) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        DecodeOut o;
+        o.into = out; o.cap = out_cap;
+        pipeline_decompress_host(ctx, stages, nstages, in, len, o, out_len);
+    });
+}
+
+int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::rle_decode(in, len, offset, s); });
+}
+int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::mtf_decode(in, len, s); });
+}
+int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::huff_decode_literals(in, len, s); });
 }
 
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx) { return ctx ? ctx->last_decode_device : 0; }

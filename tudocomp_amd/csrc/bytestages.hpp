@@ -1,0 +1,36 @@
+// bytestages.hpp -- the three byte-stream compressors behind bwt in the reference's `bwtzip = bwt:rle:mtf:encode(huff)` chain, on the
+// device (bytestages.hip).  Citations are relative to the reference's include/tudocomp/.
+//   rle           compressors/RunLengthEncoder.hpp:15-32 + util/vbyte.hpp:28-37
+//   mtf           compressors/MTFCompressor.hpp:16-33
+//   encode(huff)  compressors/LiteralEncoder.hpp:23-32 with coders/HuffmanCoder.hpp
+// Every function reads a device buffer of n bytes (n <= 2^32 - 2, at least 16 readable bytes behind it), takes its output buffer from
+// the arena once the output length is known, and enqueues on c.stream.  An output of more than 2^32 - 2 bytes: StageTooLarge, thrown
+// before anything of it is written.
+#pragma once
+#include "common.hpp"
+
+namespace tdc {
+
+constexpr u64 STAGE_MAX_BYTES = 0xFFFFFFFEull;
+struct StageTooLarge { u64 bytes; };
+
+// kernel geometry (the tests place their lengths around these borders)
+constexpr u32 RLE_PER_THREAD = 16, RLE_TILE = 256 * RLE_PER_THREAD;
+// mtf: one thread encodes MTF_CHUNK bytes from its own copy of the list.  Building that copy costs about 2 x 256 list steps whatever the
+// chunk holds, encoding costs one step per unit of rank: with 1024 bytes per chunk the set-up is at most half a step per byte, and a
+// text of 64 MiB still fills every compute unit with one workgroup (256 chunks = 256 KiB per workgroup).
+constexpr u32 MTF_CHUNK = 1024, MTF_TILE = 256 * MTF_CHUNK;
+constexpr u32 HUFF_PER_THREAD = 16, HUFF_TILE = 256 * HUFF_PER_THREAD;
+
+// worst-case output lengths (64-bit: they may pass STAGE_MAX_BYTES)
+u64 rle_bound(u64 n, u64 offset);
+u64 huff_literals_bound(u64 n);
+// device scratch a stage takes from the arena besides its output
+u64 stage_scratch_bound(u64 n);
+
+struct StageOut { u8* d = nullptr; u64 len = 0; };
+StageOut rle_encode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
+StageOut mtf_encode_device(Ctx& c, const u8* d_in, size_t n);
+StageOut huff_literals_device(Ctx& c, const u8* d_in, size_t n);
+
+}  // namespace tdc

@@ -508,6 +508,95 @@ public:
     }
 };
 
+// tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) over bwt, rle, mtf and encode(huff) -- e.g. the reference's
+// bwtzip = bwt:rle:mtf:encode(huff) -- and the three single compressors as chains of one stage: tdc::RunLengthEncoder
+// (compressors/RunLengthEncoder.hpp:52-74, option offset), tdc::MTFCompressor (compressors/MTFCompressor.hpp:45-69), tdc::LiteralEncoder
+// (compressors/LiteralEncoder.hpp:11-42, `encode(coder)`, coder huff).  compress(): every stage on the device, intermediates in device
+// memory (tdc_gpu_pipeline_compress).  decompress(): the host loops of tdc_coders.hpp from the last stage to the first, a leading bwt by
+// BWTCompressor::decompress.  Only a leading bwt has input restrictions.
+class ChainCompressor : public Compressor {
+protected:
+    std::vector<tdc_gpu_stage> m_stages;
+    std::shared_ptr<GpuContext> m_ctx;
+    int m_device = 0;
+    static tdc_gpu_stage parse_stage(const std::string& part) {
+        const AlgorithmValue av = parse_algorithm_id(part, {part.compare(0, 6, "encode") == 0 ? "coder" : "offset"});
+        if (av.name == "bwt") return {TDC_GPU_STAGE_BWT, 0};
+        if (av.name == "mtf") return {TDC_GPU_STAGE_MTF, 0};
+        if (av.name == "rle") {
+            const long o = av.get_int("offset", 0);
+            if (o < 0) throw std::runtime_error("rle: offset must not be negative");
+            return {TDC_GPU_STAGE_RLE, (uint64_t)o};
+        }
+        if (av.name == "encode" && av.get("coder", "huff") == "huff") return {TDC_GPU_STAGE_HUFF, 0};
+        throw std::runtime_error("No implementation found for compressor " + part);       // Registry.hpp:214
+    }
+public:
+    tdc_gpu_stats last_stats{};
+    void set_device(int d) { m_device = d; }
+    // `a:b:c` (util/algorithm_parser/AlgorithmAST.hpp:119-129: chain(chain(a, b), c))
+    ChainCompressor(const std::string& spec, std::shared_ptr<GpuContext> ctx) : m_ctx(std::move(ctx)) {
+        size_t b = 0; int depth = 0;
+        for (size_t i = 0; i <= spec.size(); ++i) {
+            if (i < spec.size() && spec[i] == '(') ++depth;
+            if (i < spec.size() && spec[i] == ')') --depth;
+            if (i == spec.size() || (spec[i] == ':' && depth == 0)) { m_stages.push_back(parse_stage(spec.substr(b, i - b))); b = i + 1; }
+        }
+        for (size_t i = 1; i < m_stages.size(); ++i)
+            if (m_stages[i].kind == TDC_GPU_STAGE_BWT) throw std::runtime_error("bwt is only available as the first stage of a chain");
+        if (m_stages.size() > TDC_GPU_PIPELINE_MAX_STAGES) throw std::runtime_error("a chain has at most 8 stages");
+    }
+    const std::vector<tdc_gpu_stage>& stages() const { return m_stages; }
+    InputRestrictions input_restrictions() const override {
+        return m_stages[0].kind == TDC_GPU_STAGE_BWT ? InputRestrictions{true, true} : InputRestrictions{};
+    }
+    void compress(Input& input, Output& output) override {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const bytes view = input.as_view();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_pipeline_compress(m_ctx->h, m_stages.data(), (int)m_stages.size(), view.data(), view.size(), &out, &out_len, &last_stats);
+        if (rc == TDC_GPU_ERR_NO_SENTINEL) throw std::logic_error(tdc_gpu_strerror(rc));
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
+    }
+    void decompress(Input& input, Output& output) override {
+        bytes a = input.raw(), b;
+        for (size_t i = m_stages.size(); i-- > (m_stages[0].kind == TDC_GPU_STAGE_BWT ? 1u : 0u); ) {
+            const tdc_gpu_stage& st = m_stages[i];
+            auto run = [&](uint8_t* o, size_t cap) {
+                ByteSink sink(o, cap);
+                if (st.kind == TDC_GPU_STAGE_RLE) rle_decode(a.data(), a.size(), st.param, sink);
+                else if (st.kind == TDC_GPU_STAGE_MTF) mtf_decode(a.data(), a.size(), sink);
+                else huff_decode_literals(a.data(), a.size(), sink);
+                return sink.n;
+            };
+            const uint64_t need = run(nullptr, 0);
+            if (need > 0xFFFFFFFEull) throw std::runtime_error("corrupt stream: a stage decodes to more than 2^32 - 2 bytes");
+            b.assign((size_t)need, 0);
+            run(b.data(), b.size());
+            a.swap(b);
+        }
+        if (m_stages[0].kind == TDC_GPU_STAGE_BWT) {
+            BWTCompressor inv(AlgorithmValue(), m_ctx);
+            Input in(a);
+            inv.decompress(in, output);
+        } else output.write(a.data(), a.size());
+    }
+};
+class RunLengthEncoder : public ChainCompressor {
+public:
+    RunLengthEncoder(const AlgorithmValue& opts, std::shared_ptr<GpuContext> ctx) : ChainCompressor("rle(offset=" + opts.get("offset", "0") + ")", std::move(ctx)) {}
+};
+class MTFCompressor : public ChainCompressor {
+public:
+    explicit MTFCompressor(std::shared_ptr<GpuContext> ctx) : ChainCompressor("mtf", std::move(ctx)) {}
+};
+class LiteralEncoder : public ChainCompressor {
+public:
+    LiteralEncoder(const AlgorithmValue& opts, std::shared_ptr<GpuContext> ctx) : ChainCompressor("encode(coder=" + opts.get("coder", "huff") + ")", std::move(ctx)) {}
+};
+
 // ---- registry (what is actually registered; Registry.hpp:204-231) ---------------------------------------------
 struct Selection {
     std::string id_string;
@@ -528,13 +617,28 @@ inline std::vector<std::string> registered_algorithms() {
              "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]",
              "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
-             "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]" };
+             "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
+             "rle                                                                         [MI355X; host decoder]",
+             "rle(offset=0)                                                               [MI355X; host decoder]",
+             "mtf                                                                         [MI355X: chunk summaries + one list per thread; host decoder]",
+             "encode(huff)                                                                [MI355X; host decoder]" };
 }
 
 inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuContext> ctx = nullptr, int device = 0) {
+    // chains (`a:b`) are reached through the library and the facade classes, not through the command line
+    if (id.find(':') != std::string::npos) throw std::runtime_error("No implementation found for compressor " + id + " (chains are not available on the command line)");
     AlgorithmValue av = parse_algorithm_id(id, {"coder", "comp", "dec", "textds"});
     Selection s;
     s.id_string = id;
+    if (av.name == "rle" || av.name == "mtf" || av.name == "encode") {
+        std::unique_ptr<ChainCompressor> z;
+        if (av.name == "rle") z = std::make_unique<RunLengthEncoder>(parse_algorithm_id(id, {"offset"}), std::move(ctx));
+        else if (av.name == "mtf") z = std::make_unique<MTFCompressor>(std::move(ctx));
+        else z = std::make_unique<LiteralEncoder>(parse_algorithm_id(id, {"coder"}), std::move(ctx));
+        z->set_device(device);
+        s.compressor = std::move(z);
+        return s;
+    }
     if (av.name == "lz78") {
         auto z = std::make_unique<LZ78Compressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dec"}), std::move(ctx));
         z->set_device(device);

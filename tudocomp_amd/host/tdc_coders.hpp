@@ -361,4 +361,124 @@ inline void decode_text(decoder_t& decoder, std::vector<uint8_t>& text) {
     }
 }
 
+// ---- the byte-stream compressors behind bwt (bwtzip = bwt:rle:mtf:encode(huff)) on the host ------------------------------------------
+// They are the text of the C ABI's host decoders (tdc_rle_decode, tdc_mtf_decode, tdc_huff_decode_literals) and the host side of the
+// CPU tests; the encoders restate what the reference's loops emit (the device kernels are pinned against the same rule).
+// A sink that counts everything and stores what fits: out == nullptr measures.
+struct ByteSink {
+    uint8_t* out; size_t cap; uint64_t n = 0;
+    ByteSink(uint8_t* o, size_t c) : out(o), cap(o ? c : 0) {}
+    void put(uint8_t c) { if (n < cap) out[n] = c; if (~n) ++n; }
+    void fill(uint8_t c, uint64_t k) {
+        for (uint64_t i = n; i < cap && i - n < k; ++i) out[i] = c;
+        n = k > ~n ? ~(uint64_t)0 : n + k;                     // (saturates: a ten-byte vbyte may ask for 2^64 - 1 bytes)
+    }
+};
+// util/vbyte.hpp:28-37 (write) and :13-25 (read): seven bits per byte, least significant group first, bit 7 = "more"
+template <typename sink_t> inline void write_vbyte(sink_t& os, uint64_t v) {
+    while (v >= 128) { os.put((uint8_t)(0x80u | (v & 0x7Fu))); v >>= 7; }
+    os.put((uint8_t)v);
+}
+inline uint64_t read_vbyte(const uint8_t* in, size_t n, size_t& i) {
+    uint64_t v = 0;
+    for (unsigned k = 0; ; ++k) {
+        if (i >= n) throw std::runtime_error("corrupt rle stream: a vbyte runs off the end");
+        if (k == 10) throw std::runtime_error("corrupt rle stream: a vbyte of more than ten bytes");
+        const uint8_t b = in[i++];
+        v |= (uint64_t)(b & 0x7Fu) << (7 * k);
+        if (!(b & 0x80u)) return v;
+    }
+}
+// rle_encode (compressors/RunLengthEncoder.hpp:15-32) as that loop behaves on x86-64: char is signed and istream::peek() yields 0 .. 255,
+// so only bytes below 0x80 extend a run; the endless loop on a trailing 0xFF 0xFF (peek() == EOF == (char)0xFF) is cut off at the end of
+// the input, where it emits what a 0xFF in mid-stream emits.
+template <typename sink_t> inline void rle_encode(const uint8_t* in, size_t n, uint64_t offset, sink_t& os) {
+    if (!n) return;
+    uint8_t prev = in[0];
+    os.put(prev);
+    for (size_t i = 1; i < n; ) {
+        const uint8_t c = in[i++];
+        if (prev == c) {
+            uint64_t run = 0;
+            while (c < 0x80u && i < n && in[i] == c) { ++run; ++i; }
+            os.put(c);
+            write_vbyte(os, run + offset);
+        } else os.put(c);
+        prev = c;
+    }
+}
+// rle_decode (:36-50): after two equal bytes a vbyte follows, run = vbyte - offset
+template <typename sink_t> inline void rle_decode(const uint8_t* in, size_t n, uint64_t offset, sink_t& os) {
+    if (!n) return;
+    uint8_t prev = in[0];
+    os.put(prev);
+    for (size_t i = 1; i < n; ) {
+        const uint8_t c = in[i++];
+        if (prev == c) {
+            const uint64_t v = read_vbyte(in, n, i);
+            if (v < offset) throw std::runtime_error("corrupt rle stream: run length below the offset");
+            os.fill(c, v - offset);
+        }
+        os.put(c);
+        prev = c;
+    }
+}
+// mtf_encode / mtf_decode (compressors/MTFCompressor.hpp:16-43): the list starts as 0 .. 255
+template <typename sink_t> inline void mtf_encode(const uint8_t* in, size_t n, sink_t& os) {
+    uint8_t list[256];
+    for (int i = 0; i < 256; ++i) list[i] = (uint8_t)i;
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t c = in[i];
+        unsigned j = 0;
+        while (list[j] != c) ++j;
+        os.put((uint8_t)j);
+        for (; j > 0; --j) list[j] = list[j - 1];
+        list[0] = c;
+    }
+}
+template <typename sink_t> inline void mtf_decode(const uint8_t* in, size_t n, sink_t& os) {
+    uint8_t list[256];
+    for (int i = 0; i < 256; ++i) list[i] = (uint8_t)i;
+    for (size_t i = 0; i < n; ++i) {
+        unsigned j = in[i];
+        const uint8_t c = list[j];
+        os.put(c);
+        for (; j > 0; --j) list[j] = list[j - 1];
+        list[0] = c;
+    }
+}
+// LiteralEncoder::compress / ::decompress (compressors/LiteralEncoder.hpp:23-41) with HuffmanCoder
+struct BufferLiterals {
+    const uint8_t* p; size_t n, i = 0;
+    bool has_next() const { return i < n; }
+    Literal next() { const Literal l{p[i], i}; ++i; return l; }
+};
+inline void huff_encode_literals(const uint8_t* in, size_t n, std::vector<uint8_t>& out) {
+    auto bits = std::make_shared<BitOStream>(out);
+    HuffmanCoder::Encoder coder(bits, BufferLiterals{in, n});
+    for (size_t i = 0; i < n; ++i) coder.encode(in[i], literal_r);
+    bits->finish();
+}
+template <typename sink_t> inline void huff_decode_literals(const uint8_t* in, size_t n, sink_t& os) {
+    if (!n) throw std::runtime_error("corrupt stream: no Huffman header");
+    // bits in front of the terminator (io/BitOStream.hpp:53-64): a header that needs more of them than there are is cut off
+    const unsigned u = in[n - 1] & 7u;
+    if (u >= 6 && n < 2) throw std::runtime_error("corrupt stream: no Huffman header");
+    const uint64_t total = u >= 6 ? (uint64_t)(n - 2) * 8 + u : (uint64_t)(n - 1) * 8 + u;
+    if (total < 1) throw std::runtime_error("corrupt stream: no Huffman header");
+    if (in[0] & 0x80u) {                                     // "1" + table: longest, numl[], sigma as 8-bit groups, sigma bytes
+        BitIStream probe(in, n);
+        uint64_t need = 1;
+        auto group = [&] { uint64_t v = probe.read_compressed_int(); need += 8; for (uint64_t x = v >> 7; x; x >>= 7) need += 8; return v; };
+        probe.read_bit();
+        const uint64_t longest = group() & 0xFF;
+        for (uint64_t i = 0; i < longest && need <= total; ++i) (void)group();
+        const uint64_t sigma = need <= total ? group() : 0;
+        need += 8 * sigma;
+        if (need > total || !longest || sigma > 256) throw std::runtime_error("corrupt stream: Huffman header cut off or inconsistent");
+    }
+    HuffmanCoder::Decoder dec(std::make_shared<BitIStream>(in, n));
+    while (!dec.eof()) os.put(dec.template decode<uliteral_t>(literal_r));
+}
+
 }  // namespace tdc_amd
