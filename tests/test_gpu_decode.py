@@ -4,6 +4,7 @@ decode_text_internal, compressors/LCPCompressor.hpp:23-76, with HuffmanCoder::De
 A context created with TDC_GPU_DEC_PARSE=2 parses EVERY stream on the device (the default takes streams of 1 MiB and more), so the
 small corpus, random inputs, the reference-held decode vectors and damaged streams all go through the next() / chain-marking /
 count / scan / emit kernels; the oracle's streams must decode to the oracle's texts, damaged streams must be refused, never crash."""
+import ctypes
 import os
 
 import numpy as np
@@ -147,6 +148,17 @@ def test_decompress_into_caller_buffer(gpu_ctx):
         with pytest.raises(T.TdcGpuError) as e:
             gpu_ctx.lcpcomp_decompress_into(stream, small)
         assert e.value.status == -5
+        # this entry point does not report the required size: *out_len is left alone, nothing is written, and the text is the
+        # decoder's refusal, not the "*out_len holds the required size" of the other _into entry points
+        L = T._native.load()
+        sa = np.frombuffer(stream, dtype=np.uint8)
+        small[:] = 0xA5
+        ol = ctypes.c_size_t(12345)
+        rc = L.tdc_gpu_lcpcomp_decompress_into(gpu_ctx._h, sa.ctypes.data_as(ctypes.c_void_p), len(sa), T.CODER_HUFF,
+                                               small.ctypes.data_as(ctypes.c_void_p), small.size, ctypes.byref(ol), None, None)
+        msg = L.tdc_gpu_last_error(gpu_ctx._h).decode()
+        assert rc == -5 and ol.value == 12345 and bool((small == 0xA5).all()), (rc, ol.value)
+        assert msg.startswith("out of memory (decode") and "out_len" not in msg, msg
         tiny_text = O.escape(b"abcabcabc hello hello")
         s2, _ = O.lcpcomp_huff_compress(tiny_text, 2, 1)              # (host parse path into a caller buffer)
         n2, st2 = gpu_ctx.lcpcomp_decompress_into(s2, out)

@@ -313,6 +313,16 @@ def test_compress_keep_and_fetch(gpu_ctx):
         out = np.zeros(ln + 8, dtype=np.uint8)
         assert gpu_ctx.stream_fetch(out) == ln
         _same(out[:ln].tobytes(), w, "keep + fetch %s/%s" % (kind, coder))
+    # the NULL checks of the entry point: no length pointer, no text
+    L = T._native.load()
+    text = np.frombuffer(text_of("english", N3), dtype=np.uint8)
+    tp, ol = text.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t()
+    rc = L.tdc_gpu_lcpcomp_compress_keep(gpu_ctx._h, tp, len(text), 2, 1, T.CODER_HUFF, T.COMP_ARRAYS, None, None)
+    assert rc == -2 and L.tdc_gpu_last_error(gpu_ctx._h) == b"out/out_len is NULL"
+    rc = L.tdc_gpu_lcpcomp_compress_keep(gpu_ctx._h, None, len(text), 2, 1, T.CODER_HUFF, T.COMP_ARRAYS, ctypes.byref(ol), None)
+    assert rc == -2 and L.tdc_gpu_last_error(gpu_ctx._h) == b"text is NULL"
+    with pytest.raises(T.TdcGpuError):                  # (a refused call keeps no stream either)
+        gpu_ctx.stream_fetch(np.zeros(8, dtype=np.uint8))
 
 
 def test_compress_dev(gpu_ctx):

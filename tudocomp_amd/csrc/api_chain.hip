@@ -1,0 +1,332 @@
+// api_chain.hip -- C ABI (include/tdc_gpu.h): bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip), the byte stages rle, mtf and encode(huff)
+// (bytestages.hip) and chains of them, with the host decoders of the byte stages.
+#include "api.hpp"
+#include "bytestages.hpp"
+#include "../host/tdc_coders.hpp"
+
+#include <vector>
+#include <chrono>
+#include <functional>
+
+using namespace tdc;
+
+namespace {
+// Upload + suffix array + gather: the transform of text[0..n) in a device buffer -- d_out (n + 64 bytes) if given, else the place of the
+// ranks in the arena the caller reserved.  host_dst (nullable) is where bwt_finish() will download it: bwt_gather may send it there
+// chunk by chunk already (`sent`).
+struct BwtRun { u8* d_out; bool sent; int e0, e4; };
+BwtRun bwt_device(Ctx& c, const uint8_t* text, size_t n, u8* d_out, u8* host_dst, tdc_gpu_stats* stats, Events& ev) {
+    const int e0 = ev.tick();
+    TextUpload up(c);
+    const u8* d_text = up.send(text, n);
+    const int e1 = ev.tick();
+    validate_device_text(c, d_text, n);
+    // the suffix array as tdc_gpu_suffix_array builds it; with the sink of the wide path the inverse suffix array is not materialised
+    u32* d_sa = c.arena.get<u32>(n);
+    u32* d_isa = c.arena.get<u32>(n);
+    SAStats ss;
+    SAExtra ex;
+    ex.lcp8 = c.arena.get<u8>(n + 64);
+    const int e2 = ev.tick();
+    build_suffix_array(c, d_text, n, d_sa, d_isa, &ss, &ex);
+    const int e3 = ev.tick();
+    if (!d_out) d_out = (u8*)d_isa;                          // (the ranks are not needed: the transform takes their place)
+    const bool sent = bwt_gather(c, d_text, d_sa, n, d_out, host_dst);
+    const int e4 = ev.tick();
+    if (stats) {
+        stats->n = n; stats->out_len = n;
+        sa_stats(stats, ss, &ex);
+        stats->arena_bytes = c.arena.high;
+        // ms_encode: the gather (with a page-locked destination the downloads of its chunks run inside it, and ms_d2h is what is left: nothing)
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_sa, e2, e3); ev.span(&stats->ms_encode, e3, e4);
+    }
+    return BwtRun{d_out, sent, e0, e4};
+}
+// the download of what bwt_gather has not sent, and the end of the call's event frame
+void bwt_finish(Ctx& c, const BwtRun& r, size_t n, u8* host_dst, tdc_gpu_stats* stats, Events& ev) {
+    if (!r.sent && host_dst) HIP_TRY(hipMemcpyAsync(host_dst, r.d_out, n, hipMemcpyDeviceToHost, c.stream));
+    const int e5 = ev.tick();
+    if (stats) { ev.span(&stats->ms_d2h, r.e4, e5); ev.span(&stats->ms_total, r.e0, e5); }
+    ev.finish();
+}
+
+void bwt_compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, Sink s, tdc_gpu_stats* stats) {
+    sink_check(s, "out/out_len is NULL");
+    check_host_text(text, n);
+    *s.out_len = n;
+    sink_fit(s, n);
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    reserve_arena(c, arena_need(c, n));
+    Events ev(c);
+    u8* dst = sink_host(s, n);
+    bwt_finish(c, bwt_device(c, text, n, nullptr, dst, stats, ev), n, dst, stats, ev);
+    sink_commit(s, n);
+}
+
+void bwt_decompress_common(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, Sink& s, uint32_t* host_lf,
+                           BwtInvStats* bs) {
+    if (!bwt && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    if (len >= 0x7FFFFFFFull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "bwt: the buffer must be shorter than 2^31 - 1 bytes (32-bit len_t)"};
+    if (len > 1) sink_fit(s, len);
+    const size_t n = run_decoder(s, "bwt: buffer too large", nullptr, [&] { return bwt_inverse(ctx->c, bwt, len, sample, max_steps, s, host_lf, bs); });
+    sink_commit(s, n);
+}
+
+void bwt_decompress_entry(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, Sink s, uint32_t* rounds) {
+    BwtInvStats bs;
+    bwt_decompress_common(ctx, bwt, len, 0, 0, s, nullptr, rounds ? &bs : nullptr);
+    if (rounds) *rounds = bs.rounds;
+}
+}  // namespace
+
+extern "C" {
+
+int tdc_gpu_bwt_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t** out, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { bwt_compress_host(ctx, text, n, sink_malloc(out, out_len), stats); });
+}
+
+int tdc_gpu_bwt_compress_into(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint8_t* out, size_t out_cap, size_t* out_len,
+                              tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { bwt_compress_host(ctx, text, n, sink_into(out, out_cap, out_len), stats); });
+}
+
+int tdc_gpu_bwt_decompress(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t** out, size_t* out_len, uint32_t* rounds) {
+    return guarded(ctx, [&] { bwt_decompress_entry(ctx, bwt, len, sink_malloc(out, out_len, "NULL argument"), rounds); });
+}
+
+int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint8_t* out, size_t out_cap, size_t* out_len,
+                                uint32_t* rounds) {
+    return guarded(ctx, [&] { bwt_decompress_entry(ctx, bwt, len, sink_into(out, out_cap, out_len), rounds); });
+}
+
+int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
+                              uint32_t* lf, uint64_t* heads, uint32_t* launches) {
+    return guarded(ctx, [&] {
+        if (!out && len > 1) throw ArgError{TDC_GPU_ERR_ARG, "out is NULL"};
+        size_t n = 0;
+        uint8_t nothing;                                      // (`out` may be NULL for inputs that decode to nothing)
+        Sink s = sink_into(out ? out : &nothing, len, &n);
+        BwtInvStats bs;
+        bwt_decompress_common(ctx, bwt, len, sample, max_steps, s, lf, &bs);
+        if (heads) *heads = bs.heads;
+        if (launches) *launches = bs.launches;
+    });
+}
+
+}  // extern "C"
+
+// ---- rle, mtf, encode(huff) and chains -------------------------------------------------------------------------------------------------
+namespace {
+bool pipeline_valid(const tdc_gpu_stage* st, int k) {
+    if (!st || k < 1 || k > TDC_GPU_PIPELINE_MAX_STAGES) return false;
+    for (int i = 0; i < k; ++i) {
+        if (st[i].kind < TDC_GPU_STAGE_BWT || st[i].kind > TDC_GPU_STAGE_HUFF) return false;
+        if (st[i].kind == TDC_GPU_STAGE_BWT && i) return false;
+        if (st[i].kind == TDC_GPU_STAGE_RLE && st[i].param > ((u64)1 << 62)) return false;
+    }
+    return true;
+}
+// worst-case output of one stage on n bytes
+u64 stage_worst(const tdc_gpu_stage& st, u64 n) {
+    return st.kind == TDC_GPU_STAGE_RLE ? rle_bound(n, st.param) : st.kind == TDC_GPU_STAGE_HUFF ? huff_literals_bound(n) : n;
+}
+// what the arena holds for it (a stage that would write more than STAGE_MAX_BYTES fails before it writes)
+u64 stage_bound(const tdc_gpu_stage& st, u64 n) { return std::min<u64>(stage_worst(st, n), STAGE_MAX_BYTES); }
+const char* stage_name(int kind) { return kind == TDC_GPU_STAGE_BWT ? "bwt" : kind == TDC_GPU_STAGE_RLE ? "rle" : kind == TDC_GPU_STAGE_MTF ? "mtf" : "encode(huff)"; }
+
+
+void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t n, Sink s, tdc_gpu_stats* stats) {
+    sink_check(s, "out/out_len is NULL");
+    if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage (its input is the escaped, 0-terminated view)"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle (offset <= 2^62), mtf or encode(huff)"};
+    if (n > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the input must not be longer than 2^32 - 2 bytes"};
+    const bool lead_bwt = stages[0].kind == TDC_GPU_STAGE_BWT;
+    Ctx& c = ctx->c;
+    const bool plog = c.pipe_log != 0;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto t_last = t_start;
+    float ms[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    auto tick = [&](int i) {                                  // (synchronises: only with the diagnostic option)
+        if (!plog) return;
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        const auto now = std::chrono::steady_clock::now();
+        ms[i] = std::chrono::duration<float, std::milli>(now - t_last).count();
+        t_last = now;
+    };
+    // the arena for the whole call: what the suffix array needs, or every intermediate at its worst case with the stages' scratch
+    u64 need = 0, len = n;
+    for (int i = lead_bwt ? 1 : 0; i < k; ++i) { need += stage_scratch_bound(len) + stage_bound(stages[i], len) + 4096; len = stage_bound(stages[i], len); }
+    need += n + 4096;
+    if (lead_bwt) {
+        check_text_args(in, n);                               // (before the arena is sized from n)
+        need = std::max<u64>(need, arena_need(c, n) + n + 4096);
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    tdc_gpu_stats local = {};
+    tdc_gpu_stats* st = stats ? stats : &local;
+    reserve_arena(c, need);
+    StageOut cur;
+    cur.d = c.arena.get<u8>(n + 64);
+    cur.len = n;
+    const size_t base_mark = c.arena.mark();
+    u64 lens[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    if (!lead_bwt && n) HIP_TRY(hipMemcpyAsync(cur.d, in, n, hipMemcpyHostToDevice, c.stream));
+    for (int i = 0; i < k; ++i) {
+        try {
+            switch (stages[i].kind) {
+                case TDC_GPU_STAGE_BWT: {
+                    check_host_text(in, n);
+                    Events ev(c);
+                    bwt_device(c, in, n, cur.d, nullptr, st, ev);
+                    ev.finish();
+                    c.arena.release(base_mark);               // the suffix array's scratch goes back before the byte stages take theirs
+                    break;
+                }
+                case TDC_GPU_STAGE_RLE: cur = rle_encode_device(c, cur.d, cur.len, stages[i].param); break;
+                case TDC_GPU_STAGE_MTF: cur = mtf_encode_device(c, cur.d, cur.len); break;
+                default: cur = huff_literals_device(c, cur.d, cur.len); break;
+            }
+        } catch (const StageTooLarge&) {
+            throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: a stage's output would pass 2^32 - 2 bytes"};
+        }
+        lens[i] = cur.len;
+        tick(i);
+    }
+    const size_t out_len = (size_t)cur.len;
+    *s.out_len = out_len;
+    sink_fit(s, out_len);
+    u8* dst = sink_host(s, out_len);
+    if (out_len) {
+        c.wait_for(c.copy_stream, c.stream);
+        HIP_TRY(hipMemcpyAsync(dst, cur.d, out_len, hipMemcpyDeviceToHost, c.copy_stream));
+        HIP_TRY(hipStreamSynchronize(c.copy_stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    st->n = n; st->out_len = out_len; st->pipe_stages = (uint32_t)k;
+    for (int i = 0; i < k; ++i) { st->pipe_len[i] = lens[i]; st->pipe_ms[i] = ms[i]; }
+    st->arena_bytes = c.arena.high;
+    st->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (plog) {
+        u64 prev = n;
+        for (int i = 0; i < k; ++i) {
+            fprintf(stderr, "pipe:     %-14s %12llu -> %12llu bytes %9.2f ms\n", stage_name(stages[i].kind), (unsigned long long)prev, (unsigned long long)lens[i], ms[i]);
+            prev = lens[i];
+        }
+        fprintf(stderr, "pipe:     total incl. download %9.2f ms\n", st->ms_total);
+    }
+    sink_commit(s, out_len);
+}
+
+
+// host decoder of one stage: `in` -> `out` (at most STAGE_MAX_BYTES)
+void host_stage_decode(const tdc_gpu_stage& st, const std::vector<uint8_t>& in, std::vector<uint8_t>& out) {
+    auto run = [&](uint8_t* o, size_t cap) {
+        tdc_amd::ByteSink sink(o, cap);
+        if (st.kind == TDC_GPU_STAGE_RLE) tdc_amd::rle_decode(in.data(), in.size(), st.param, sink);
+        else if (st.kind == TDC_GPU_STAGE_MTF) tdc_amd::mtf_decode(in.data(), in.size(), sink);
+        else tdc_amd::huff_decode_literals(in.data(), in.size(), sink);
+        return sink.n;
+    };
+    try {
+        if (st.kind == TDC_GPU_STAGE_MTF) out.resize(in.size());
+        else {
+            const u64 need = run(nullptr, 0);
+            if (need > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: a stage decodes to more than 2^32 - 2 bytes"};
+            out.resize((size_t)need);
+        }
+        run(out.data(), out.size());
+    } catch (const std::runtime_error&) {
+        throw ArgError{TDC_GPU_ERR_ARG, "pipeline: malformed stream"};
+    }
+}
+
+
+void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink s) {
+    if (!in && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf or encode(huff)"};
+    if (len > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the stream must not be longer than 2^32 - 2 bytes"};
+    const bool plog = ctx->c.pipe_log != 0;
+    std::vector<uint8_t> a(in, in + len), b;
+    for (int i = k - 1; i >= (stages[0].kind == TDC_GPU_STAGE_BWT ? 1 : 0); --i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        host_stage_decode(stages[i], a, b);
+        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (host)\n", stage_name(stages[i].kind), b.size(), a.size(),
+                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        a.swap(b);
+    }
+    if (stages[0].kind == TDC_GPU_STAGE_BWT) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bwt_decompress_common(ctx, a.data(), a.size(), 0, 0, s, nullptr, nullptr);
+        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (device)\n", "bwt", *s.out_len, a.size(),
+                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return;
+    }
+    *s.out_len = a.size();
+    sink_fit(s, a.size());
+    u8* dst = sink_host(s, a.size());
+    if (!a.empty()) memcpy(dst, a.data(), a.size());
+    sink_commit(s, a.size());
+}
+
+int host_decode_entry(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len, const std::function<void(tdc_amd::ByteSink&)>& f) {
+    if ((!in && len) || !out_len) return TDC_GPU_ERR_ARG;
+    try {
+        tdc_amd::ByteSink sink(out, out_cap);
+        f(sink);
+        *out_len = sink.n > (u64)SIZE_MAX ? SIZE_MAX : (size_t)sink.n;
+        return out && sink.n > out_cap ? TDC_GPU_ERR_ARG : TDC_GPU_OK;
+    } catch (const std::runtime_error&) { return TDC_GPU_ERR_ARG;
+    } catch (...) { return TDC_GPU_ERR_INTERNAL; }
+}
+}  // namespace
+
+extern "C" {
+
+size_t tdc_gpu_pipeline_bound(const tdc_gpu_stage* stages, int nstages, size_t n) {
+    if (!pipeline_valid(stages, nstages) || n > STAGE_MAX_BYTES) return 0;
+    u64 len = n;
+    for (int i = 0; i < nstages; ++i) {
+        len = stage_worst(stages[i], len);
+        if (len > STAGE_MAX_BYTES) return 0;                  // (where the arena's stage_bound() clamps, the public bound says "no bound")
+    }
+    return (size_t)len;
+}
+
+int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t** out,
+                              size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { pipeline_compress_host(ctx, stages, nstages, in, n, sink_malloc(out, out_len), stats); });
+}
+
+int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
+                                   size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { pipeline_compress_host(ctx, stages, nstages, in, n, sink_into(out, out_cap, out_len), stats); });
+}
+
+int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len, uint8_t** out,
+                                size_t* out_len) {
+    return guarded(ctx, [&] { pipeline_decompress_host(ctx, stages, nstages, in, len, sink_malloc(out, out_len, "NULL argument")); });
+}
+
+int tdc_gpu_pipeline_decompress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
+                                     uint8_t* out, size_t out_cap, size_t* out_len) {
+    return guarded(ctx, [&] { pipeline_decompress_host(ctx, stages, nstages, in, len, sink_into(out, out_cap, out_len)); });
+}
+
+int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::rle_decode(in, len, offset, s); });
+}
+int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::mtf_decode(in, len, s); });
+}
+int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::huff_decode_literals(in, len, s); });
+}
+
+}  // extern "C"

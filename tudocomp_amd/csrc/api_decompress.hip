@@ -1,0 +1,64 @@
+// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp (also lzss_lcp streams) and lz78 decompression.
+#include "api.hpp"
+
+using namespace tdc;
+
+namespace {
+void lcpcomp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, uint64_t* factors, uint32_t* rounds) {
+    ctx->last_decode_device = 0;                             // (a failed call must not report the previous call's value)
+    if (!stream) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    const int enc = lcpcomp_enc_coder(coder);
+    if (enc == 1) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lcpcomp(coder=arithmetic) streams cannot be decoded (neither can the reference)"};
+    DecodeStats ds;
+    // (no `need`: a caller's buffer that is too small is reported as the decoder's allocation failure, without the required size)
+    const size_t n = run_decoder(s, "lcpcomp: the stream decodes to too large a text", nullptr, [&] { return decode_lzss(ctx->c, stream, len, enc, s, &ds); });
+    if (factors) *factors = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+    ctx->last_decode_device = (int)ds.device_parse;
+    sink_commit(s, n);
+}
+
+void lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, uint64_t* phrases, uint32_t* rounds) {
+    if (coder != TDC_GPU_CODER_GAMMA) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lz78: only coder=gamma is built"};
+    if (!stream && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    DecodeStats ds;
+    size_t need = 0;
+    const size_t n = run_decoder(s, "lz78: the stream decodes to more than 2^32 - 2 bytes", &need, [&] { return decode_lz78_gamma(ctx->c, stream, len, s, &need, &ds); });
+    if (phrases) *phrases = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+    sink_commit(s, n);
+}
+}  // namespace
+
+extern "C" {
+
+int tdc_gpu_lcpcomp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, uint8_t** out, size_t* out_len,
+                               uint64_t* factors, uint32_t* rounds) {
+    return tdc_gpu_lcpcomp_decompress_coder(ctx, stream, len, TDC_GPU_CODER_HUFF, out, out_len, factors, rounds);
+}
+
+int tdc_gpu_lcpcomp_decompress_coder(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                                     uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lcpcomp_decompress(ctx, stream, len, coder, sink_malloc(out, out_len, "NULL argument"), factors, rounds); });
+}
+
+int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                    size_t* out_len, uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lcpcomp_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), factors, rounds); });
+}
+
+int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx) { return ctx ? ctx->last_decode_device : 0; }
+
+int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                            uint64_t* phrases, uint32_t* rounds) {
+    return guarded(ctx, [&] { lz78_decompress(ctx, stream, len, coder, sink_malloc(out, out_len, "NULL argument"), phrases, rounds); });
+}
+
+int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, uint64_t* phrases, uint32_t* rounds) {
+    return guarded(ctx, [&] { lz78_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), phrases, rounds); });
+}
+
+}  // extern "C"

@@ -255,7 +255,7 @@ bool bwt_gather(Ctx& c, const u8* d_text, const u32* d_sa, size_t n, u8* d_out, 
 }
 
 // decode_bwt (ds/bwt.hpp:77-98) with the complete C table.  Returns the text length (0 for inputs of at most one byte).
-size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, DecodeOut& out, u32* host_lf, BwtInvStats* st) {
+size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st) {
     BwtInvStats local;
     if (!st) st = &local;
     *st = BwtInvStats();

@@ -198,7 +198,7 @@ struct Ctx {
     int msd_partition = 1;         // bucketed scatter: MSD partition with atomic slots instead of two stable LSD passes (env TDC_GPU_MSD_PARTITION=0)
     int bucket_scatter = 1;        // big random scatters (rank, Phi) go through one radix partition by destination window (env TDC_GPU_BUCKET_SCATTER=0 disables)
     // (the options below used to be read from the environment wherever they were used; since round 6 every option is a field that only
-    //  tdc_gpu_ctx_set_option() writes -- api.hip, one table -- and the shipped library never looks at TDC_GPU_* variables unless
+    //  tdc_gpu_ctx_set_option() writes -- api_ctx.hip, one table -- and the shipped library never looks at TDC_GPU_* variables unless
     //  TDC_GPU_DEBUG_KNOBS=1 asks tdc_gpu_ctx_create() to apply them through that same function)
     int upload_tail_n = 3, upload_tail_pct = 60;   // the last upload_tail_n chunks of the overlapped upload shrink by this factor each (0.6, 0.36, 0.22: what is left behind the last copy is the device work of a small chunk)
     int upload_chunks = 16;        // chunks of the overlapped upload (4 .. 24; option upload_chunks)
@@ -215,7 +215,7 @@ struct Ctx {
     u32 hist_cache[256] = {};
     const u8* hist_ptr = nullptr;
     size_t hist_n = 0;
-    // side streams: every call returns with them idle (api.hip guarded()), so their events are reused from call to call
+    // side streams: every call returns with them idle (api.hpp guarded()), so their events are reused from call to call
     hipStream_t copy_stream = nullptr;
     hipStream_t aux_stream = nullptr;  // low-priority side stream: work that fills idle device time behind the upload (wsort.hip wsort_pre_chunk); may be null
     hipEvent_t ev_join = nullptr;      // wait_for()

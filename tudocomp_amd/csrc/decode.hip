@@ -724,8 +724,8 @@ static bool host_pinned(const void* p) {
 }
 
 // where the decoded text goes: the caller's buffer, or a buffer allocated here (2 MiB aligned, transparent huge pages asked for: a
-// 256 MiB text otherwise pays 65 536 page faults in front of the download) that the caller releases with free()
-u8* decode_dest(DecodeOut& o, size_t n) {
+// 256 MiB text otherwise pays 65 536 page faults in front of the download) that the sink owns (free()-compatible)
+u8* decode_dest(Sink& o, size_t n) {
     if (o.into) {
         if (n > o.cap) throw HipError{hipErrorOutOfMemory, "decompress: output buffer too small", (int)__LINE__};
         return o.into;
@@ -744,7 +744,7 @@ u8* decode_dest(DecodeOut& o, size_t n) {
 // Resolves the reference forest of n text positions on the device (d_text holds the literals at their positions, the factor list is
 // on the device as well) and downloads the text.
 void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
-                                 u32* d_changed, DecodeOut& out, DecodeStats* st) {
+                                 u32* d_changed, Sink& out, DecodeStats* st) {
     hipStream_t s = c.stream;
     const bool dlog = c.dec_log != 0;
     auto t_last = std::chrono::steady_clock::now();
@@ -844,7 +844,7 @@ static bool dev_coder(const SleHeader& H, DevCoder<SleTab>& D) {
 // literal runs); throws StreamFormatError for malformed input.
 template <typename Tab>
 static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssFields& H, const DevCoder<Tab>& D, u64 x0, u64 total,
-                               DecodeOut& out, DecodeStats* st) {
+                               Sink& out, DecodeStats* st) {
     if (H.fdist_max > DEC_MAX_RUN) return false;
     const u64 la_bits = 1 + H.dbits + H.fdist_max * D.code_max + H.W + D.lenf_max;     // the longest token a candidate may read
     const u32 nwords = (u32)((DEC_TILE + la_bits + 31) / 32 + 4);
@@ -1034,7 +1034,7 @@ static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssF
 }
 
 // coder: 0 = HuffmanCoder, 2 = ASCIICoder, 3 | kmer << 8 = SLECoder (the coder ids of encode_stream)
-size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, DecodeOut& out, DecodeStats* st) {
+size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, Sink& out, DecodeStats* st) {
     DecodeStats local;
     if (!st) st = &local;
     *st = DecodeStats();

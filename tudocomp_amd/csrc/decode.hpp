@@ -85,13 +85,13 @@ struct BitWinG {
 };
 
 // where a decoded text of n bytes goes: out.into if set (HipError hipErrorOutOfMemory if n > out.cap), else a buffer allocated here
-// (out.owned; the caller releases it with free())
-u8* decode_dest(DecodeOut& o, size_t n);
+// (out.owned; the sink frees it unless it is released to the caller)
+u8* decode_dest(Sink& o, size_t n);
 // Resolves the reference forest of n text positions on the device and downloads the text into decode_dest(out, n).  d_text (n + 64
 // bytes) holds the literals at their positions; the factor list (d_pos, d_src, d_len: z entries, length 0 allowed) copies
 // text[d_src[i] + j] to d_pos[i] + j, j < d_len[i], every source in front of its target.  d_ref: n entries of scratch, d_changed: one
 // word.  st->rounds receives the number of pointer-jumping rounds.  n < 2^32 - 1 (positions and NONE32 share the u32 range).
 void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
-                          u32* d_changed, DecodeOut& out, DecodeStats* st);
+                          u32* d_changed, Sink& out, DecodeStats* st);
 
 }  // namespace tdc

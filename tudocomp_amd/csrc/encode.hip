@@ -525,7 +525,7 @@ static void encode_prelude(Ctx& c, const u8* text, size_t n, FactorSpace& fs, En
 static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k, u8* d_out, size_t out_cap, EncodeStats* st);
 
 // The encoder in two halves.  The first one -- gaps, literal histogram, coder header, bits per tile, their scan -- needs the factors'
-// positions and lengths but not their sources, so the caller may run it while the factors are still being flattened (api.hip,
+// positions and lengths but not their sources, so the caller may run it while the factors are still being flattened (api_compress.hip,
 // run_factorize: on the copy stream, next to the first flatten round); the second half packs the bits and needs everything.
 #ifndef TDC_PACK_CH
 #define TDC_PACK_CH 16     // (8: 0.3 ms more behind the last chunk at 2e9 B, 32: the same as 16)

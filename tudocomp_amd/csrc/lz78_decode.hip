@@ -173,7 +173,7 @@ void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, 
 
 }  // namespace
 
-size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, DecodeOut& out, size_t* need, DecodeStats* st) {
+size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t* need, DecodeStats* st) {
     DecodeStats local;
     if (!st) st = &local;
     *st = DecodeStats();

@@ -59,7 +59,7 @@ void ss_fanouts(Ctx& c, size_t n, int& L, u32 F[3], u32& os, u32 leaf3 = 0, int 
 // the text).  Bit-packed keys make the common prefix of two keys a count of leading zeros, which is where the LCP values come from.
 struct WKeyGen { const u8* text; size_t n; int b, s, pad; u32 inv /* ceil(65536 / b) */; u8 code[256]; };
 struct WSortStats { u32 levels = 0, range_leaves = 0, samples = 0, units = 0, large_leaves = 0, kw = 0, refined_units = 0, trunc_units = 0, longrun_units = 0, leaf_stages = 0, wave_runs = 0; u64 large_pairs = 0; u64 nonheads = 0; };
-// Level 1 of wsort_suffixes done chunk by chunk BEHIND THE UPLOAD of a host text (api.hip compress_host): the code map comes from the
+// Level 1 of wsort_suffixes done chunk by chunk BEHIND THE UPLOAD of a host text (api.hpp TextUpload): the code map comes from the
 // bytes of chunk 0 (the full histogram confirms it afterwards, else the work is thrown away), the splitters from a sample of chunk 0,
 // and every chunk is counted and scattered into its own part of the record buffers as soon as it (and the chunk behind it: a key reads
 // up to 64 bytes ahead) has arrived.  Level 2 then reads the buckets of all chunks as pieces of one segment.  Buffers live at the top of

@@ -123,7 +123,7 @@ void factorize_max_heap(Ctx& c, size_t n, const u32* sa, const u32* isa, const u
 struct FlattenStats { u64 num_flattened = 0; u64 max_depth_lb = 0; u32 rounds = 0; };
 // a10: compressors/lzss/LZSSFactors.hpp:79-132 ; rewrites fs.fsrc in place.
 // `between` (optional) is called with r = 1, 2, ... once round r has been enqueued and before the host waits for its count, and with 0
-// when the rounds are over: the place for work that does not need the flattened sources (api.hip runs the first half of the encoder
+// when the rounds are over: the place for work that does not need the flattened sources (api_compress.hip runs the first half of the encoder
 // there, step by step on another stream).  Whatever it takes from the arena is gone when flatten_factors returns.
 // rec_keep (optional, room for 16 bytes per factor): the records {pos, len, original source, final source} in position order are built
 // there and stay valid for the caller; fs.fsrc is NOT rewritten then.
@@ -174,15 +174,29 @@ namespace tdc {
 // references resolved on the device by pointer jumping.  `text` receives the (still escaped, 0-terminated) text.
 struct DecodeStats { u64 factors = 0; u32 rounds = 0; u32 device_parse = 0; };
 struct StreamFormatError { const char* what; };          // malformed input
-// destination of a decoded text: `into` (cap bytes) if set, else `owned` is allocated by the decoder (release with free())
-struct DecodeOut { u8* into = nullptr; size_t cap = 0; u8* owned = nullptr; };
+// Where the bytes a call produces go: the caller's buffer `into` of `cap` bytes, or a buffer allocated during the call (`owned`: by
+// decode_dest for the decoders, by sink_host of the C ABI layer for everything else) that is handed to the caller through *out by
+// release() once the call has succeeded and freed otherwise, or -- `keep`, lcpcomp only -- nowhere: the stream stays on the device.
+// *out_len receives the length (api.hpp: how the entry points build one, and the "too small" rule).
+struct Sink {
+    u8* into = nullptr; size_t cap = 0;
+    u8* owned = nullptr;
+    uint8_t** out = nullptr; size_t* out_len = nullptr;
+    bool keep = false;
+    Sink() = default;
+    Sink(Sink&& o) : into(o.into), cap(o.cap), owned(o.owned), out(o.out), out_len(o.out_len), keep(o.keep) { o.owned = nullptr; }
+    Sink(const Sink&) = delete;
+    Sink& operator=(const Sink&) = delete;
+    ~Sink() { free(owned); }
+    u8* release() { u8* r = owned; owned = nullptr; return r; }
+};
 // the same for streams written with another coder: 0 = HuffmanCoder, 2 = ASCIICoder, 3 | kmer << 8 = SLECoder
-size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, DecodeOut& out, DecodeStats* st);
+size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, Sink& out, DecodeStats* st);
 // LZ78Compressor::decompress (compressors/LZ78Compressor.hpp:142-160) for coder=gamma, parsed on the device (lz78_decode.hip).
 // Returns the text length; *need (nullable) receives it as soon as it is known -- also when out.into is too small (HipError
 // hipErrorOutOfMemory).  Malformed input: StreamFormatError; a text of more than 2^32 - 2 bytes: DecodeTooLarge.
 struct DecodeTooLarge { u64 n; };
-size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, DecodeOut& out, size_t* need, DecodeStats* st);
+size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t* need, DecodeStats* st);
 // a17: compressors/LZ78Compressor.hpp:64-140 -- sequential parse on the host; returns the number of (id, char) pairs
 size_t lz78_parse_host(const u8* in, size_t n, std::vector<u32>& ids, std::vector<u8>& chars, bool* leftover_is_high);
 // a16: coders/EliasGammaCoder.hpp:26-29 + io/BitOStream.hpp:105-129 on the device; returns the stream length
@@ -200,6 +214,6 @@ bool bwt_gather(Ctx& c, const u8* d_text, const u32* d_sa, size_t n, u8* d_out, 
 // len >= 2^31 - 1: DecodeTooLarge; out.into too small: HipError hipErrorOutOfMemory -- each before anything is written to `out`.
 constexpr u32 BWT_SAMPLE = 256, BWT_STEPS_PER_SAMPLE = 4;
 struct BwtInvStats { u64 heads = 0; u32 launches = 0, rounds = 0, longest = 0, sample = 0, max_steps = 0; };
-size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, DecodeOut& out, u32* host_lf, BwtInvStats* st);
+size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st);
 
 }  // namespace tdc

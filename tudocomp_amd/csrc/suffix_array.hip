@@ -892,7 +892,7 @@ int build_suffix_array_wide(Ctx& c, const u8* text, size_t n, u32* sa, u32* isa,
     WKeyGen g1 = g;                                            // the 64-bit keys of the text rounds
     g1.s = per_word > 64 ? 64 : per_word; g1.pad = 64 - g1.s * b;
     st->sym_bits = b; st->init_syms = g.s;
-    // level 1 may have been done behind the upload already (api.hip): its record buffers sit at the top of the arena
+    // level 1 may have been done behind the upload already (api_compress.hip): its record buffers sit at the top of the arena
     WPre* pre = (c.wpre && c.wpre->active && c.wpre->text == text && c.wpre->n == n && c.wpre->KW == KW) ? c.wpre : nullptr;
     struct TopGuard { Ctx& c; WPre* p; ~TopGuard() { if (p) { p->active = false; p->begun = false; c.arena.release_top(); } } } top_guard{c, pre};
 
