@@ -82,7 +82,7 @@ typedef struct {
     uint32_t max_push_targets;  /* most target levels the pushes of one level went to (arrays, max_lcp)                        */
     uint64_t d2h_early;         /* tdc_gpu_lcpcomp_compress_into: stream bytes copied to `out` while the pack still ran            */
     uint32_t pipe_stages;       /* tdc_gpu_pipeline_compress: number of stages, ...                                                 */
-    uint32_t pipe_reserved;
+    uint32_t pipe_dev;          /* tdc_gpu_pipeline_decompress_stats: bit i = stage i was decoded (bwt: inverted) on the device      */
     uint64_t pipe_len[8];       /* ... the length in bytes behind stage i, ...                                                      */
     float    pipe_ms[8];        /* ... and what stage i took (host clock around a synchronisation; only with option pipe_log)       */
 } tdc_gpu_stats;
@@ -322,12 +322,20 @@ int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
  * on the copy stream (page-locked memory -- tdc_gpu_host_alloc -- receives it at the host link's rate). */
 int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
                                    size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
-/* Inverse, stage by stage from the last one: rle, mtf and encode(huff) are decoded by the host loops below, a leading bwt by
- * tdc_gpu_bwt_decompress on the device (*out then holds the escaped, 0-terminated text).  Malformed input: TDC_GPU_ERR_ARG. */
+/* Inverse, stage by stage from the last one, on the device: one upload of the stream, the decoders of rle, mtf and encode(huff)
+ * (csrc/bytestages_decode.hip) and the inverse of a leading bwt work from buffer to buffer in the arena, one download (*out then holds the
+ * escaped, 0-terminated text if the pipeline starts with bwt).  Option dec_parse picks the path once per call from the stream's length:
+ * 1 (default) = the device for streams of 1 MiB and more, 2 = the device for every stream, 0 = the host loops below, which are the
+ * specification of the device decoders (same bytes, same refusals) and also take the call when the device cannot hold the arena.
+ * Malformed input, or a stage that decodes to more than 2^32 - 2 bytes: TDC_GPU_ERR_ARG. */
 int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len, uint8_t** out,
                                 size_t* out_len);
 int tdc_gpu_pipeline_decompress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
                                      uint8_t* out, size_t out_cap, size_t* out_len);
+/* _into with stats (not NULL): n (the stream's length), out_len, pipe_stages, pipe_len[i] = the length behind stage i as in the stats of
+ * the compress call (what stage i's decoder read), pipe_ms[] (option pipe_log), pipe_dev, ms_total, arena_bytes. */
+int tdc_gpu_pipeline_decompress_stats(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
+                                      uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
 /* The host decoders (no context, no GPU): rle_decode (RunLengthEncoder.hpp:36-50), MTFCompressor::decompress (MTFCompressor.hpp:35-43,
  * 60-68), LiteralEncoder::decompress (LiteralEncoder.hpp:34-41 with HuffmanCoder::Decoder).  out == NULL: nothing is written and *out_len
  * receives the decoded length.  Otherwise at most out_cap bytes are written; a text that does not fit is refused like malformed input

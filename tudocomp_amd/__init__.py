@@ -520,7 +520,8 @@ class Context:
         return ol.value, st.as_dict()
 
     def pipeline_decompress(self, stages, stream):
-        """inverse of pipeline_compress: host loops for rle, mtf and encode(huff), the device inverse for a leading bwt"""
+        """inverse of pipeline_compress, stage by stage on the device (option dec_parse: 1 = streams of 1 MiB and more, 2 = every stream,
+        0 = the host loops for rle, mtf and encode(huff))"""
         arr, k = _stages(stages)
         a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
@@ -537,6 +538,18 @@ class Context:
         if rc:
             self._raise_required(rc, ol.value)
         return ol.value
+
+    def pipeline_decompress_stats(self, stages, stream, out, n=None):
+        """pipeline_decompress_into with stats: returns (text length, stats dict).  pipe_len[i] = the length behind stage i as in the stats
+        of pipeline_compress, pipe_ms per stage with option pipe_log, pipe_dev: bit i = stage i ran on the device."""
+        arr, k = _stages(stages)
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_pipeline_decompress_stats(self._h, arr, k, _ptr(a) if len(a) else None, len(a) if n is None else n, _ptr(oa), oa.size, ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
 
     def blocks_decompress(self, blob, coder=CODER_HUFF):
         """inverse of blocks_compress on this context's device: the concatenated raw bytes"""

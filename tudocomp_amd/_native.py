@@ -30,7 +30,7 @@ SYMBOLS = [
     "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
     "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
     "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
-    "tdc_gpu_pipeline_decompress_into", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
+    "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
 ]
 
 
@@ -46,7 +46,7 @@ class Stats(ctypes.Structure):
                                         "sa_key_words", "sa_text_rounds", "sa_mode", "sa_overlapped", "eager_levels", "eager_phases", "sa_star_chains",
                                         "probes", "max_push_targets")] +
         [("d2h_early", ctypes.c_uint64)] +
-        [("pipe_stages", ctypes.c_uint32), ("pipe_reserved", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8)])
+        [("pipe_stages", ctypes.c_uint32), ("pipe_dev", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8)])
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -141,6 +141,7 @@ def load():
     L.tdc_gpu_pipeline_compress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]
     L.tdc_gpu_pipeline_decompress.argtypes = [vp, pst, i32, vp, sz, pvp, psz]
     L.tdc_gpu_pipeline_decompress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz]
+    L.tdc_gpu_pipeline_decompress_stats.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]
     L.tdc_rle_decode.argtypes = [vp, sz, ctypes.c_uint64, vp, sz, psz]
     L.tdc_mtf_decode.argtypes = [vp, sz, vp, sz, psz]
     L.tdc_huff_decode_literals.argtypes = [vp, sz, vp, sz, psz]

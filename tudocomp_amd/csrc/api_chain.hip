@@ -1,5 +1,5 @@
 // api_chain.hip -- C ABI (include/tdc_gpu.h): bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip), the byte stages rle, mtf and encode(huff)
-// (bytestages.hip) and chains of them, with the host decoders of the byte stages.
+// (bytestages.hip, bytestages_decode.hip) and chains of them, with the host decoders of the byte stages.
 #include "api.hpp"
 #include "bytestages.hpp"
 #include "../host/tdc_coders.hpp"
@@ -245,27 +245,41 @@ void host_stage_decode(const tdc_gpu_stage& st, const std::vector<uint8_t>& in, 
 }
 
 
-void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink s) {
-    if (!in && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
-    sink_check(s, "NULL argument");
-    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
-        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage"};
-    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf or encode(huff)"};
-    if (len > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the stream must not be longer than 2^32 - 2 bytes"};
+// what a call reports (tdc_gpu_pipeline_decompress_stats): lens[i] = the length behind stage i's encoder = in front of its decoder, as in
+// the stats of the compress call; dev: bit i = stage i ran on the device
+struct PipeReport { u64 lens[TDC_GPU_PIPELINE_MAX_STAGES] = {0}; float ms[TDC_GPU_PIPELINE_MAX_STAGES] = {0}; uint32_t dev = 0; };
+
+void pipe_line(bool plog, int kind, u64 out, u64 in, double ms, bool dev) {
+    if (plog) fprintf(stderr, "pipe:     %-14s %12llu <- %12llu bytes %9.2f ms (%s)\n", stage_name(kind), (unsigned long long)out, (unsigned long long)in, ms, dev ? "device" : "host");
+}
+
+// the inverse of a leading bwt from a host buffer or (on_device) from the arena
+void bwt_invert_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, Sink& s, bool on_device) {
+    if (len >= 0x7FFFFFFFull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "bwt: the buffer must be shorter than 2^31 - 1 bytes (32-bit len_t)"};
+    if (len > 1) sink_fit(s, len);
+    const size_t n = run_decoder(s, "bwt: buffer too large", nullptr, [&] { return bwt_inverse(ctx->c, bwt, len, 0, 0, s, nullptr, nullptr, on_device); });
+    sink_commit(s, n);
+}
+
+// the host loops: the fall-back (option dec_parse = 0, small streams, a device that cannot hold the arena) and the specification
+void pipeline_decompress_loops(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink& s, PipeReport& rep) {
     const bool plog = ctx->c.pipe_log != 0;
     std::vector<uint8_t> a(in, in + len), b;
     for (int i = k - 1; i >= (stages[0].kind == TDC_GPU_STAGE_BWT ? 1 : 0); --i) {
         const auto t0 = std::chrono::steady_clock::now();
+        rep.lens[i] = a.size();
         host_stage_decode(stages[i], a, b);
-        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (host)\n", stage_name(stages[i].kind), b.size(), a.size(),
-                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        rep.ms[i] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pipe_line(plog, stages[i].kind, b.size(), a.size(), rep.ms[i], false);
         a.swap(b);
     }
     if (stages[0].kind == TDC_GPU_STAGE_BWT) {
         const auto t0 = std::chrono::steady_clock::now();
-        bwt_decompress_common(ctx, a.data(), a.size(), 0, 0, s, nullptr, nullptr);
-        if (plog) fprintf(stderr, "pipe:     %-14s %12zu <- %12zu bytes %9.2f ms (device)\n", "bwt", *s.out_len, a.size(),
-                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        rep.lens[0] = a.size();
+        bwt_invert_into(ctx, a.data(), a.size(), s, false);
+        rep.dev |= 1u;
+        rep.ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pipe_line(plog, TDC_GPU_STAGE_BWT, *s.out_len, a.size(), rep.ms[0], true);
         return;
     }
     *s.out_len = a.size();
@@ -273,6 +287,140 @@ void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
     u8* dst = sink_host(s, a.size());
     if (!a.empty()) memcpy(dst, a.data(), a.size());
     sink_commit(s, a.size());
+}
+
+// The stages backwards on the device: one upload, every intermediate in the arena, one download.  False: the device cannot hold the
+// arena (nothing has been written, the host loops take the call).  An arena that turns out too small for a stage's output -- the
+// lengths are only known once the stage in front has been decoded -- is reserved again with what is known by then and the call starts
+// over: at most once per stage.
+bool pipeline_decompress_device(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink& s, PipeReport& rep) {
+    Ctx& c = ctx->c;
+    const bool plog = c.pipe_log != 0;
+    const bool lead_bwt = stages[0].kind == TDC_GPU_STAGE_BWT;
+    const int first = lead_bwt ? 1 : 0;
+    u64 known[TDC_GPU_PIPELINE_MAX_STAGES] = {0};              // decoded length of stage i, once an attempt has seen it
+    bool have[TDC_GPU_PIPELINE_MAX_STAGES] = {false};
+    u64 extra = 0;
+    for (int attempt = 0; attempt < 2 * TDC_GPU_PIPELINE_MAX_STAGES + 4; ++attempt) {
+        u64 need = len + 4096 + extra, L = len;
+        for (int i = k - 1; i >= first; --i) {
+            const u64 out = have[i] ? known[i] : stages[i].kind == TDC_GPU_STAGE_MTF ? L : std::min<u64>(3 * L + 4096, STAGE_MAX_BYTES);
+            need += out + 4096 + stage_decode_scratch_bound(L, out);
+            L = out;
+        }
+        if (lead_bwt) need += bwt_inverse_arena((size_t)std::min<u64>(L, 0x7FFFFFFFull)) + 4096;
+        try { reserve_arena(c, need); }
+        catch (const ArgError& e) { if (e.code == TDC_GPU_ERR_OOM) return false; throw; }
+        catch (const HipError& e) { if (e.e == hipErrorOutOfMemory) { (void)hipGetLastError(); return false; } throw; }
+        rep = PipeReport();
+        auto t_last = std::chrono::steady_clock::now();
+        auto tick = [&]() -> float {                                // (synchronises: only with the diagnostic option)
+            if (!plog) return 0.f;
+            HIP_TRY(hipStreamSynchronize(c.stream));
+            const auto now = std::chrono::steady_clock::now();
+            const float ms = std::chrono::duration<float, std::milli>(now - t_last).count();
+            t_last = now;
+            return ms;
+        };
+        StageOut cur;
+        cur.d = c.arena.get<u8>(len + 64);
+        cur.len = len;
+        if (len) HIP_TRY(hipMemcpyAsync(cur.d, in, len, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(hipMemsetAsync(cur.d + len, 0, 64, c.stream));
+        bool again = false;
+        for (int i = k - 1; i >= first && !again; --i) {
+            rep.lens[i] = cur.len;
+            bool dev = true;
+            try {
+                try {
+                    switch (stages[i].kind) {
+                        case TDC_GPU_STAGE_RLE: cur = rle_decode_device(c, cur.d, (size_t)cur.len, stages[i].param); break;
+                        case TDC_GPU_STAGE_MTF: cur = mtf_decode_device(c, cur.d, (size_t)cur.len); break;
+                        default: cur = huff_decode_device(c, cur.d, (size_t)cur.len); break;
+                    }
+                } catch (const StageHostOnly&) {                 // this one stage through its host loop
+                    dev = false;
+                    c.arena.release_top();
+                    std::vector<uint8_t> a((size_t)cur.len), b;
+                    if (cur.len) HIP_TRY(hipMemcpy(a.data(), cur.d, (size_t)cur.len, hipMemcpyDeviceToHost));
+                    host_stage_decode(stages[i], a, b);
+                    const size_t off = align_up(c.arena.top, 256);
+                    if (off + b.size() + 64 > c.arena.size) throw StageArenaShort{b.size()};
+                    StageOut o;
+                    o.d = c.arena.get<u8>(b.size() + 64); o.len = b.size();
+                    if (o.len) HIP_TRY(hipMemcpy(o.d, b.data(), b.size(), hipMemcpyHostToDevice));
+                    cur = o;
+                }
+            } catch (const StageArenaShort& a) {
+                known[i] = a.out_bytes; have[i] = true; again = true;
+            } catch (const HipError& e) {
+                if (e.e != hipErrorOutOfMemory) throw;             // the stage's scratch did not fit
+                (void)hipGetLastError();
+                extra = extra ? 2 * extra : need; again = true;
+            } catch (const StageTooLarge&) {
+                throw ArgError{TDC_GPU_ERR_ARG, "pipeline: a stage decodes to more than 2^32 - 2 bytes"};
+            } catch (const StreamFormatError&) {
+                throw ArgError{TDC_GPU_ERR_ARG, "pipeline: malformed stream"};
+            }
+            c.arena.release_top();                                // the stage's scratch goes back once its output exists
+            if (again) break;
+            known[i] = cur.len; have[i] = true;
+            if (dev) rep.dev |= 1u << i;
+            rep.ms[i] = tick();
+            pipe_line(plog, stages[i].kind, cur.len, rep.lens[i], rep.ms[i], dev);
+        }
+        if (again) { HIP_TRY(hipStreamSynchronize(c.stream)); continue; }
+        if (lead_bwt) {
+            if (cur.len < 0x7FFFFFFFull && align_up(c.arena.top, 256) + bwt_inverse_arena((size_t)cur.len) > c.arena.size) { HIP_TRY(hipStreamSynchronize(c.stream)); continue; }
+            rep.lens[0] = cur.len;
+            bwt_invert_into(ctx, cur.d, (size_t)cur.len, s, true);
+            rep.dev |= 1u;
+            rep.ms[0] = tick();
+            pipe_line(plog, TDC_GPU_STAGE_BWT, *s.out_len, cur.len, rep.ms[0], true);
+            return true;
+        }
+        const size_t out_len = (size_t)cur.len;
+        *s.out_len = out_len;
+        sink_fit(s, out_len);
+        u8* dst = sink_host(s, out_len);
+        if (out_len) {
+            c.wait_for(c.copy_stream, c.stream);
+            HIP_TRY(hipMemcpyAsync(dst, cur.d, out_len, hipMemcpyDeviceToHost, c.copy_stream));
+            HIP_TRY(hipStreamSynchronize(c.copy_stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        sink_commit(s, out_len);
+        return true;
+    }
+    return false;
+}
+
+void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink s, tdc_gpu_stats* stats = nullptr) {
+    if (!in && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf or encode(huff)"};
+    if (len > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the stream must not be longer than 2^32 - 2 bytes"};
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const auto t_start = std::chrono::steady_clock::now();
+    PipeReport rep;
+    // option dec_parse, decided once per call from the stream's length: 1 = the device for streams of 1 MiB and more, 2 = always, 0 = never
+    // (a pipeline of bwt alone has no byte stage: the path it always took)
+    const bool byte_stages = k > (stages[0].kind == TDC_GPU_STAGE_BWT ? 1 : 0);
+    const bool device = byte_stages && c.dec_parse && (c.dec_parse >= 2 || len >= ((size_t)1 << 20));
+    if (!device || !pipeline_decompress_device(ctx, stages, k, in, len, s, rep)) {
+        rep = PipeReport();
+        pipeline_decompress_loops(ctx, stages, k, in, len, s, rep);
+    }
+    if (c.dec_log) fprintf(stderr, "pipe:     decompress %zu <- %zu bytes, stages on the device 0x%x\n", *s.out_len, len, rep.dev);
+    if (stats) {
+        stats->n = len; stats->out_len = *s.out_len; stats->pipe_stages = (uint32_t)k; stats->pipe_dev = rep.dev;
+        for (int i = 0; i < k; ++i) { stats->pipe_len[i] = rep.lens[i]; stats->pipe_ms[i] = c.pipe_log ? rep.ms[i] : 0.f; }
+        stats->arena_bytes = c.arena.high;
+        stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
 }
 
 int host_decode_entry(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len, const std::function<void(tdc_amd::ByteSink&)>& f) {
@@ -317,6 +465,11 @@ int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, i
 int tdc_gpu_pipeline_decompress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
                                      uint8_t* out, size_t out_cap, size_t* out_len) {
     return guarded(ctx, [&] { pipeline_decompress_host(ctx, stages, nstages, in, len, sink_into(out, out_cap, out_len)); });
+}
+
+int tdc_gpu_pipeline_decompress_stats(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len,
+                                      uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { pipeline_decompress_host(ctx, stages, nstages, in, len, sink_into(out, out_cap, out_len), stats); });
 }
 
 int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len) {

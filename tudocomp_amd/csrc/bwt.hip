@@ -254,8 +254,11 @@ bool bwt_gather(Ctx& c, const u8* d_text, const u32* d_sa, size_t n, u8* d_out, 
     return true;
 }
 
+// upper bound of what bwt_inverse takes from the arena for a transform of n bytes (hashed slots: at most 2 n / sample + 1)
+size_t bwt_inverse_arena(size_t n) { return 6 * n + (size_t)cdiv(n, LF_TILE) * 1024 + (2 * n / BWT_SAMPLE + n / BWT_SAMPLE + 4) * 16 + ((size_t)16 << 20); }
+
 // decode_bwt (ds/bwt.hpp:77-98) with the complete C table.  Returns the text length (0 for inputs of at most one byte).
-size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st) {
+size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st, bool on_device) {
     BwtInvStats local;
     if (!st) st = &local;
     *st = BwtInvStats();
@@ -284,8 +287,9 @@ size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps,
     mx.inv_a = inv_odd(MIX_A); mx.inv_b = inv_odd(MIX_B);
     const u32 ntiles = cdiv(n, LF_TILE);
     const size_t cap = (size_t)mx.T + n / M + 2;             // hashed slots + one per max_steps rows walked
-    c.ensure_arena(6 * n + (size_t)ntiles * 1024 + cap * 16 + ((size_t)16 << 20));
-    u8* d_b = c.arena.get<u8>(n + 64);
+    // (on_device: the transform lies in the arena already, what is needed comes from the room above it)
+    if (!on_device) c.ensure_arena(6 * n + (size_t)ntiles * 1024 + cap * 16 + ((size_t)16 << 20));
+    u8* d_b = on_device ? const_cast<u8*>(bwt) : c.arena.get<u8>(n + 64);
     u32* d_lf = c.arena.get<u32>(n);
     u8* d_out = c.arena.get<u8>(n + 64);
     u32* d_tab = c.arena.get<u32>(257);
@@ -293,7 +297,7 @@ size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps,
     H.cnt = c.arena.get<u32>(4);
     H.hrow = c.arena.get<u32>(cap); H.hlen = c.arena.get<u32>(cap); H.w = (unsigned long long*)c.arena.get<u64>(cap);
     H.cap = (u32)std::min<size_t>(cap, 0xFFFFFFFEull);
-    HIP_TRY(hipMemcpyAsync(d_b, bwt, n, hipMemcpyHostToDevice, s));
+    if (!on_device) HIP_TRY(hipMemcpyAsync(d_b, bwt, n, hipMemcpyHostToDevice, s));
     tick("upload");
 
     // C from the byte histogram; exactly one 0 byte

@@ -33,4 +33,16 @@ StageOut rle_encode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
 StageOut mtf_encode_device(Ctx& c, const u8* d_in, size_t n);
 StageOut huff_literals_device(Ctx& c, const u8* d_in, size_t n);
 
+// The decoders (bytestages_decode.hip): the host loops of host/tdc_coders.hpp are their specification, including what they refuse.
+// d_in: n bytes in the arena (256-byte aligned, 64 allocated bytes behind them).  The output comes from the bottom of the arena, scratch
+// from its top (Arena::alloc_top: the caller releases it once the output exists).  Malformed input: StreamFormatError; an output of more
+// than 2^32 - 2 bytes: StageTooLarge; an output the arena has no room for: StageArenaShort with its length -- each before anything of
+// the output is written; a Huffman header that does not end inside the first 4 KiB (no encoder writes one): StageHostOnly.
+struct StageArenaShort { u64 out_bytes; };
+struct StageHostOnly {};
+u64 stage_decode_scratch_bound(u64 n, u64 out);
+StageOut rle_decode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
+StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n);
+StageOut huff_decode_device(Ctx& c, const u8* d_in, size_t n);
+
 }  // namespace tdc

@@ -214,6 +214,9 @@ bool bwt_gather(Ctx& c, const u8* d_text, const u32* d_sa, size_t n, u8* d_out, 
 // len >= 2^31 - 1: DecodeTooLarge; out.into too small: HipError hipErrorOutOfMemory -- each before anything is written to `out`.
 constexpr u32 BWT_SAMPLE = 256, BWT_STEPS_PER_SAMPLE = 4;
 struct BwtInvStats { u64 heads = 0; u32 launches = 0, rounds = 0, longest = 0, sample = 0, max_steps = 0; };
-size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st);
+// on_device: `bwt` lies in the arena already (256-byte aligned, 64 allocated bytes behind it) and stays where it is; the inverse takes
+// what it needs from the room above the arena's current top (bwt_inverse_arena(len) bytes at most with the default sample).
+size_t bwt_inverse_arena(size_t n);
+size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps, Sink& out, u32* host_lf, BwtInvStats* st, bool on_device = false);
 
 }  // namespace tdc

@@ -512,8 +512,9 @@ public:
 // bwtzip = bwt:rle:mtf:encode(huff) -- and the three single compressors as chains of one stage: tdc::RunLengthEncoder
 // (compressors/RunLengthEncoder.hpp:52-74, option offset), tdc::MTFCompressor (compressors/MTFCompressor.hpp:45-69), tdc::LiteralEncoder
 // (compressors/LiteralEncoder.hpp:11-42, `encode(coder)`, coder huff).  compress(): every stage on the device, intermediates in device
-// memory (tdc_gpu_pipeline_compress).  decompress(): the host loops of tdc_coders.hpp from the last stage to the first, a leading bwt by
-// BWTCompressor::decompress.  Only a leading bwt has input restrictions.
+// memory (tdc_gpu_pipeline_compress).  decompress(): tdc_gpu_pipeline_decompress -- the stages backwards on the device for streams of
+// 1 MiB and more, the host loops of tdc_coders.hpp below that (option dec_parse) and on a machine without a device.  Only a leading bwt
+// has input restrictions.
 class ChainCompressor : public Compressor {
 protected:
     std::vector<tdc_gpu_stage> m_stages;
@@ -560,9 +561,10 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
-    void decompress(Input& input, Output& output) override {
+    // without a device (no context can be created) the byte stages are still decodable: the host loops, which need none
+    void decompress_host(Input& input, Output& output) {
         bytes a = input.raw(), b;
-        for (size_t i = m_stages.size(); i-- > (m_stages[0].kind == TDC_GPU_STAGE_BWT ? 1u : 0u); ) {
+        for (size_t i = m_stages.size(); i-- > 0; ) {
             const tdc_gpu_stage& st = m_stages[i];
             auto run = [&](uint8_t* o, size_t cap) {
                 ByteSink sink(o, cap);
@@ -577,11 +579,23 @@ public:
             run(b.data(), b.size());
             a.swap(b);
         }
-        if (m_stages[0].kind == TDC_GPU_STAGE_BWT) {
-            BWTCompressor inv(AlgorithmValue(), m_ctx);
-            Input in(a);
-            inv.decompress(in, output);
-        } else output.write(a.data(), a.size());
+        output.write(a.data(), a.size());
+    }
+    void decompress(Input& input, Output& output) override {
+        if (!m_ctx) {
+            try { m_ctx = std::make_shared<GpuContext>(m_device); }
+            catch (const std::exception&) {
+                if (m_stages[0].kind == TDC_GPU_STAGE_BWT) throw;
+                decompress_host(input, output);
+                return;
+            }
+        }
+        const bytes& in = input.raw();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_pipeline_decompress(m_ctx->h, m_stages.data(), (int)m_stages.size(), in.data(), in.size(), &out, &out_len);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
     }
 };
 class RunLengthEncoder : public ChainCompressor {
