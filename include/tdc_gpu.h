@@ -229,6 +229,30 @@ int tdc_gpu_lcpcomp_factorize(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, u
 /* FactorBuffer::flatten on a caller-supplied factor list sorted by pos (LZSSFactors.hpp:79-132); src rewritten in place */
 int tdc_gpu_flatten(tdc_gpu_ctx* ctx, size_t n, const uint32_t* pos, uint32_t* src, const uint32_t* len, size_t z,
                     uint64_t* num_flattened, uint64_t* max_depth_lb);
+/* ---- the shared device primitives (csrc/prim.hpp) one by one, for tests/test_gpu_prims.py; no reference counterpart.  Host buffers in
+ * and out.  Every precondition of a primitive is checked on the host first: TDC_GPU_ERR_ARG, and nothing is launched. ---- */
+/* op 0: exclusive_sum_u32, 1: exclusive_sum_u64, 2: inclusive_max_u32 over the n words (4 / 8 / 4 bytes each) of `data`, which the result
+ * replaces.  in_place != 0: in == out on the device as well, else two buffers.  total (NULL: the primitive gets a null d_total; op 2
+ * has none): one word that receives the grand total. */
+int tdc_gpu_prim_scan(tdc_gpu_ctx* ctx, int op, void* data, size_t n, int in_place, void* total);
+/* kind 0: radix_sort_pairs_u32, 1: radix_sort_pairs_u64 (stable), 2: sort_pairs_u64_distinct (keys pairwise distinct on the sorted
+ * bits), on bits [begin_bit, end_bit) of the keys (4 / 8 / 8 bytes each); end_bit <= 32 / 64 / 64.  keys / vals are replaced by the
+ * contents of the buffer pair the primitive names. */
+int tdc_gpu_prim_sort_pairs(tdc_gpu_ctx* ctx, int kind, void* keys, uint32_t* vals, size_t n, int begin_bit, int end_bit);
+/* bucketed_scatter_u32: dst (n_dst words, every one `fill` beforehand) with dst[idx[j]] = val[j], j < m; idx pairwise distinct and
+ * < n_dst.  permutation != 0: idx holds every index of [0, m) once and m is n_dst or n_dst - 1.  second_tmp = 0: without the second
+ * pair of temporaries.  offset (0 or 1): idx / val start that many elements behind an aligned device address. */
+int tdc_gpu_prim_bucketed_scatter(tdc_gpu_ctx* ctx, const uint32_t* idx, const uint32_t* val, size_t m, uint32_t* dst, size_t n_dst,
+                                  uint32_t fill, int permutation, int second_tmp, int offset);
+/* msd_partition_pairs_u32: the m pairs grouped by idx >> (bits - 2 * db), in place; db 8 or 9, 2 * db < bits <= 32, idx < 2^bits */
+int tdc_gpu_prim_msd_partition(tdc_gpu_ctx* ctx, uint32_t* idx, uint32_t* val, size_t m, int bits, int db);
+/* select_by_class: outA (m words, every one fillA beforehand) / outB (m words of fillB; NULL iff srcB is NULL) receive the selected
+ * elements of srcA (NULL: their indices) / srcB in order, *count their number */
+int tdc_gpu_prim_select(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t want, size_t m, const uint32_t* srcA, const uint64_t* srcB,
+                        uint32_t fillA, uint64_t fillB, uint32_t* outA, uint64_t* outB, uint32_t* count);
+/* mark_orbit_u32: mark[i] = 1 on the chain 0, next[0], next[next[0]], ... and 0 elsewhere; i < next[i] <= n for every i */
+int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, uint8_t* mark);
+
 /* ---- LCPCompressor::decompress (LCPCompressor.hpp:140-150 -> decode_text_internal :23-76, HuffmanCoder::Decoder
  * coders/HuffmanCoder.hpp:572-612); lzss_lcp(coder=huff) streams have the same format (LZSSLCPCompressor.hpp:125-130).
  * Streams of 1 MiB and more whose longest literal run is at most 512 are parsed ON THE DEVICE (rounds 4-5, DESIGN.md section 5: where

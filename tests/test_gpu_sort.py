@@ -9,27 +9,9 @@ import pytest
 
 import tudocomp_amd as T
 from oracle import oracle as O
+from tests.prim_inputs import sort_key_cases as _cases
 
 pytestmark = pytest.mark.gpu
-
-
-def _cases(n, rng):
-    yield "uniform", rng.integers(0, 2**64, size=n, dtype=np.uint64)
-    yield "low_bits_only", rng.integers(0, 1 << 20, size=n, dtype=np.uint64)
-    yield "high_bits_only", rng.integers(0, 1 << 20, size=n, dtype=np.uint64) << np.uint64(44)
-    yield "all_equal", np.full(n, 0x0123456789ABCDEF, dtype=np.uint64)
-    yield "two_values", rng.integers(0, 2, size=n, dtype=np.uint64) * np.uint64(0xFFFFFFFFFFFFFFFF)
-    few = rng.integers(0, 2**64, size=37, dtype=np.uint64)
-    yield "37_values", few[rng.integers(0, 37, size=n)]
-    # Zipf-like: half of the pairs share 5 heavy keys, the rest is uniform (the shape of text keys)
-    z = rng.integers(0, 2**64, size=n, dtype=np.uint64)
-    heavy = rng.integers(0, 2**64, size=5, dtype=np.uint64)
-    m = rng.random(n) < 0.5
-    z[m] = heavy[rng.integers(0, 5, size=int(m.sum()))]
-    yield "heavy_keys", z
-    yield "sorted", np.sort(rng.integers(0, 2**64, size=n, dtype=np.uint64))
-    yield "reversed", np.sort(rng.integers(0, 2**64, size=n, dtype=np.uint64))[::-1].copy()
-    yield "max_keys", np.where(rng.random(n) < 0.3, np.uint64(0xFFFFFFFFFFFFFFFF), rng.integers(0, 2**64, size=n, dtype=np.uint64))
 
 
 def _check(ctx, keys, algo):
@@ -39,6 +21,8 @@ def _check(ctx, keys, algo):
     assert np.array_equal(k, np.sort(keys))
     assert np.array_equal(keys[v], k)                           # every value still travels with its key
     assert np.array_equal(np.sort(v), vals)                     # and the values are a permutation
+    if algo == 0:                                               # the LSD sort is stable (the splitter sort is documented as unstable)
+        assert np.array_equal(v, np.argsort(keys, kind="stable"))
 
 
 @pytest.mark.parametrize("levels", [0, 1, 2, 3])

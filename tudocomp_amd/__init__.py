@@ -380,6 +380,71 @@ class Context:
         self._check(self._L.tdc_gpu_sort_pairs_u64(self._h, _ptr(k), _ptr(v), len(k), int(algo)))
         return k, v
 
+    # ---- the shared device primitives one by one (csrc/api_prims.hip; tests/test_gpu_prims.py) ------------
+    _SCAN_OPS = {"sum_u32": (0, np.uint32), "sum_u64": (1, np.uint64), "max_u32": (2, np.uint32)}
+    _SORT_KINDS = {"u32": (0, np.uint32), "u64": (1, np.uint64), "distinct": (2, np.uint64)}
+
+    def prim_scan(self, op, data, in_place=False, want_total=True):
+        """exclusive_sum_u32 / exclusive_sum_u64 / inclusive_max_u32 (op "sum_u32" | "sum_u64" | "max_u32"); returns (scan, total or None)."""
+        code, dt = self._SCAN_OPS[op]
+        a = np.ascontiguousarray(data, dtype=dt).copy()
+        tot = np.zeros(1, dtype=dt) if want_total and code != 2 else None
+        self._check(self._L.tdc_gpu_prim_scan(self._h, code, _ptr(a), len(a), int(bool(in_place)), _ptr(tot) if tot is not None else None))
+        return a, (int(tot[0]) if tot is not None else None)
+
+    def prim_sort_pairs(self, kind, keys, vals, begin_bit, end_bit):
+        """radix_sort_pairs_u32 / radix_sort_pairs_u64 / sort_pairs_u64_distinct (kind "u32" | "u64" | "distinct") on bits
+        [begin_bit, end_bit); returns the (keys, vals) of the buffer pair the primitive names."""
+        code, dt = self._SORT_KINDS[kind]
+        k = np.ascontiguousarray(keys, dtype=dt).copy()
+        v = np.ascontiguousarray(vals, dtype=np.uint32).copy()
+        if len(k) != len(v):
+            raise ValueError("keys and vals differ in length")
+        self._check(self._L.tdc_gpu_prim_sort_pairs(self._h, code, _ptr(k), _ptr(v), len(k), int(begin_bit), int(end_bit)))
+        return k, v
+
+    def prim_bucketed_scatter(self, idx, val, n_dst, fill=0xFFFFFFFF, permutation=False, second_tmp=True, offset=0):
+        """bucketed_scatter_u32 into n_dst words that all hold `fill` beforehand; returns dst."""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        v = np.ascontiguousarray(val, dtype=np.uint32)
+        if len(i) != len(v):
+            raise ValueError("idx and val differ in length")
+        dst = np.empty(int(n_dst), dtype=np.uint32)
+        self._check(self._L.tdc_gpu_prim_bucketed_scatter(self._h, _ptr(i), _ptr(v), len(i), _ptr(dst), int(n_dst), int(fill),
+                                                          int(bool(permutation)), int(bool(second_tmp)), int(offset)))
+        return dst
+
+    def prim_msd_partition(self, idx, val, bits, db):
+        """msd_partition_pairs_u32; returns (out_idx, out_val)."""
+        i = np.ascontiguousarray(idx, dtype=np.uint32).copy()
+        v = np.ascontiguousarray(val, dtype=np.uint32).copy()
+        if len(i) != len(v):
+            raise ValueError("idx and val differ in length")
+        self._check(self._L.tdc_gpu_prim_msd_partition(self._h, _ptr(i), _ptr(v), len(i), int(bits), int(db)))
+        return i, v
+
+    def prim_select(self, cls, want, src_a=None, src_b=None, fill_a=0xFFFFFFFF, fill_b=0xFFFFFFFFFFFFFFFF):
+        """select_by_class; returns (outA, outB or None, count): all m output words, `fill` where the primitive wrote nothing."""
+        c = np.ascontiguousarray(cls, dtype=np.uint8)
+        m = len(c)
+        a = None if src_a is None else np.ascontiguousarray(src_a, dtype=np.uint32)
+        b = None if src_b is None else np.ascontiguousarray(src_b, dtype=np.uint64)
+        if (a is not None and len(a) != m) or (b is not None and len(b) != m):
+            raise ValueError("cls, src_a and src_b differ in length")
+        oa = np.empty(m, dtype=np.uint32)
+        ob = None if b is None else np.empty(m, dtype=np.uint64)
+        cnt = ctypes.c_uint32(0)
+        self._check(self._L.tdc_gpu_prim_select(self._h, _ptr(c), int(want), m, None if a is None else _ptr(a), None if b is None else _ptr(b),
+                                                int(fill_a), int(fill_b), _ptr(oa), None if ob is None else _ptr(ob), ctypes.byref(cnt)))
+        return oa, ob, cnt.value
+
+    def prim_mark_orbit(self, nxt):
+        """mark_orbit_u32; returns mark (u8)."""
+        a = np.ascontiguousarray(nxt, dtype=np.uint32)
+        mark = np.empty(len(a), dtype=np.uint8)
+        self._check(self._L.tdc_gpu_prim_mark_orbit(self._h, _ptr(a), len(a), _ptr(mark)))
+        return mark
+
     def suffix_array(self, text):
         a = _u8(text)
         sa = np.empty(len(a), dtype=np.uint32)

@@ -837,6 +837,7 @@ __global__ __launch_bounds__(256) void small_sort_kernel(const u64* __restrict__
                                                           u64 keymask) {
     __shared__ u64 xk[SMALL_SORT_MAX];
     __shared__ u32 xv[SMALL_SORT_MAX];
+    __shared__ u32 top_src;
     u64 k[8];
     u32 v[8];
 #pragma unroll
@@ -844,12 +845,20 @@ __global__ __launch_bounds__(256) void small_sort_kernel(const u64* __restrict__
         const u32 i = threadIdx.x * 8 + r;
         k[r] = (i < n) ? (keys_in[i] & keymask) : ~0ull;      // padding sorts to the end
         v[r] = (i < n) ? i : 0xFFFFFFFFu;                      // carry the input index: the full pair is re-read at the end
+        // a real key of all ones (end_bit = 64; at most one, the keys are distinct) ties with the padding, and the network may leave a
+        // padding element in its slot n - 1: remember where it came from (top_src is only read for such a slot, so it stays
+        // unwritten when no key is all ones: a padding element never lands below n then)
+        if (i < n && k[r] == ~0ull) top_src = i;
     }
     block_bitonic_sort_2048(k, v, xk, xv, np2);
+    __syncthreads();
 #pragma unroll
     for (u32 r = 0; r < 8; ++r) {
         const u32 i = threadIdx.x * 8 + r;
-        if (i < n) { keys_out[i] = keys_in[v[r]]; vals_out[i] = vals_in[v[r]]; }
+        if (i < n) {
+            const u32 src = (v[r] == 0xFFFFFFFFu) ? top_src : v[r];
+            keys_out[i] = keys_in[src]; vals_out[i] = vals_in[src];
+        }
     }
 }
 

@@ -101,8 +101,9 @@ bool wsort_sorted_runs(Ctx& c, const u64* k1, u64* k2, u32* v, size_t m, int k1_
 bool wsort_sorted_runs_from_text(Ctx& c, const u32* a_sa, const u32* a_r1, size_t m, const WKeyGen& g, u32 h, u64* k1, u64* k2, u32* v, int k1_bits);
 
 // Same contract as radix_sort_pairs_u64 for keys that are pairwise DISTINCT on the sorted bits (stability is then
-// irrelevant): inputs of at most 2048 pairs are sorted by one workgroup in LDS (bitonic network), larger ones by the
-// radix sort.  Used for the many tiny per-level sorts of the factorizer.
+// irrelevant): one workgroup sorts inputs of at most 2048 pairs in LDS (bitonic network on the keys masked to end_bit; begin_bit == 0
+// only) and inputs of 2049 .. 8192 pairs with a whole LSD radix sort in one launch (any begin_bit); everything else -- more pairs, or
+// at most 2048 with begin_bit != 0 -- goes to radix_sort_pairs_u64.  Used for the many tiny per-level sorts of the factorizer.
 int sort_pairs_u64_distinct(Ctx& c, u64* keys[2], u32* vals[2], size_t n, int begin_bit, int end_bit);
 
 // dst[idx[j]] = val[j], j < m, for pairwise distinct idx[j] < n_dst: a radix partition by the top 16 bits of idx (two
