@@ -38,7 +38,8 @@ typedef enum {
 } tdc_gpu_status;
 
 /* coder ids (option `coder`, etc/registry_config.py:28-31,138-142) */
-enum { TDC_GPU_CODER_HUFF = 0, TDC_GPU_CODER_GAMMA = 1, TDC_GPU_CODER_ARITH = 2, TDC_GPU_CODER_ASCII = 3, TDC_GPU_CODER_SLE = 4 };
+enum { TDC_GPU_CODER_HUFF = 0, TDC_GPU_CODER_GAMMA = 1, TDC_GPU_CODER_ARITH = 2, TDC_GPU_CODER_ASCII = 3, TDC_GPU_CODER_SLE = 4,
+       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw only */ };
 /* coder=sle(kmer=K) (coders/SLECoder.hpp:36-40; the reference's default is 3): the option travels in bits 8.. of `coder` */
 #define TDC_GPU_CODER_SLE_K(K) (TDC_GPU_CODER_SLE | ((K) << 8))
 /* factorization strategy of lcpcomp (option `comp`, LCPCompressor.hpp:87): ArraysComp or PLCPPeaksStrategy */
@@ -294,6 +295,28 @@ int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len,
 int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                  size_t* out_len, uint64_t* phrases, uint32_t* rounds);
 
+/* ---- lzw: LZWCompressor<BitCoder | EliasGammaCoder, ...> (compressors/LZWCompressor.hpp:39-133, lzw/LZWDecoding.hpp:12-99; DESIGN.md
+ * section 5.4).  No input restrictions.  coder: TDC_GPU_CODER_BIT (the reference's default: code k in bits_for(k + 256) bits) or
+ * TDC_GPU_CODER_GAMMA; anything else: TDC_GPU_ERR_UNSUPPORTED.  dict_size is 0 (unlimited), as in the reference's default.
+ * compress: the parse is sequential and runs on the host (tdc_lzw_factors), the codes are packed on the device.  Inputs of 2^32 - 256
+ * bytes and more: TDC_GPU_ERR_TOO_LARGE.  stats (may be NULL): n, out_len, factors (= number of codes), ms_h2d / ms_encode / ms_d2h /
+ * ms_total. */
+int tdc_gpu_lzw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, int coder, uint8_t** out, size_t* out_len,
+                         tdc_gpu_stats* stats);
+/* decompress: on the device for streams of 64 KiB and more (option dec_parse = 2: every stream, 0: never), else a host loop that restates
+ * lzw::decode_step; tdc_gpu_ctx_last_decode_on_device tells which.  On the device the codes are read side by side (coder=bit: from
+ * closed-form offsets; coder=gamma: the orbit parse of the lz78 decoder), a code c >= 256 is the copy of phrase c - 256 and the byte
+ * behind it in the text, lengths come from pointer jumping and the text from the reference resolver.  codes / rounds (nullable): number
+ * of codes / pointer-jumping rounds.  Malformed input -- code k (0-based) above 255 + k, a code cut off by the end of the stream, a
+ * gamma field wider than 32 bits --: TDC_GPU_ERR_ARG.  A text of more than 2^32 - 2 bytes: TDC_GPU_ERR_TOO_LARGE (found before
+ * anything of the text's size is allocated). */
+int tdc_gpu_lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                           uint64_t* codes, uint32_t* rounds);
+/* The same into the CALLER's buffer `out` of out_cap bytes.  TDC_GPU_ERR_OOM if the text does not fit; *out_len then holds the
+ * required size. */
+int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                size_t* out_len, uint64_t* codes, uint32_t* rounds);
+
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG
  * for an inner 0, TDC_GPU_ERR_TOO_LARGE).  out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0): n bytes, no header.  The suffix array is the one
@@ -368,6 +391,10 @@ int tdc_gpu_pipeline_decompress_stats(tdc_gpu_ctx* ctx, const tdc_gpu_stage* sta
 int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len);
 int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
 int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
+/* The same contract for LZWCompressor::decompress (lzw::decode_step restated; coder TDC_GPU_CODER_BIT or TDC_GPU_CODER_GAMMA, else
+ * TDC_GPU_ERR_UNSUPPORTED): the specification of tdc_gpu_lzw_decompress and its path for small streams.  TDC_GPU_ERR_ARG for what that
+ * call refuses, TDC_GPU_ERR_TOO_LARGE for a text of more than 2^32 - 2 bytes. */
+int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
 
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,
@@ -396,6 +423,10 @@ int tdc_huffman_table(const uint32_t counts[256], uint32_t* sigma, uint32_t* lon
  * ids[k] = id of the longest dictionary phrase at the start of factor k (0: none; ids count from 1 in insertion order), chars[k] = the byte
  * behind it, a leftover phrase at the end of the text as (parent id, last byte).  *ids / *chars are malloc'd (tdc_gpu_free). */
 int tdc_lz78_factors(const uint8_t* in, size_t n, uint32_t** ids, uint8_t** chars, size_t* z);
+/* compressors/LZWCompressor.hpp:39-108 : the LZW parse on its own (host; what tdc_gpu_lzw_compress codes on the device).  codes[k] = id of
+ * the dictionary node phrase k ends in (0 .. 255: the bytes; 256 + j: phrase j and the byte behind it), the left-over phrase included; no
+ * codes for the empty input.  *codes is malloc'd (tdc_gpu_free). */
+int tdc_lzw_factors(const uint8_t* in, size_t n, uint32_t** codes, size_t* z);
 /* The start-up check of tdc_gpu_ctx_create() on its own (no GPU): rebuilds two built-in fixture tables (sigma 40 and 200, many
  * equal counts) and compares them with what the reference build yields; TDC_GPU_ERR_INTERNAL if this build's C++ library
  * orders ties differently (coders/HuffmanCoder.hpp:88-120 heap functions, :455 unstable std::sort) -- every call with

@@ -16,6 +16,7 @@ CODER_GAMMA = 1
 CODER_ARITH = 2
 CODER_ASCII = 3
 CODER_SLE = 4            # coder=sle(kmer=k): CODER_SLE | (k << 8), k = 0 means the reference's default 3
+CODER_BIT = 5            # BitCoder: lzw only
 COMP_ARRAYS = 0
 COMP_PLCPPEAKS = 1
 COMP_MAXLCP = 2
@@ -98,6 +99,20 @@ def lz78_factors(data):
     return i, c
 
 
+def lzw_factors(data):
+    """The LZW parse on its own (host; compressors/LZWCompressor.hpp:39-108): the codes as a numpy array."""
+    L = _native.load()
+    a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    codes, z = ctypes.c_void_p(), ctypes.c_size_t()
+    rc = L.tdc_lzw_factors(_ptr(a) if len(a) else None, len(a), ctypes.byref(codes), ctypes.byref(z))
+    if rc:
+        raise TdcGpuError(rc)
+    try:
+        return np.ctypeslib.as_array(ctypes.cast(codes, ctypes.POINTER(ctypes.c_uint32)), (max(z.value, 1),))[:z.value].copy()
+    finally:
+        L.tdc_gpu_free(codes)
+
+
 def option_names():
     """Names of the library's options (tdc_gpu_ctx_set_option)."""
     L = _native.load()
@@ -160,6 +175,11 @@ def mtf_decode(data):
 def huff_decode_literals(data):
     """LiteralEncoder<HuffmanCoder>::decompress (compressors/LiteralEncoder.hpp:34-41) on the host"""
     return _host_decode("tdc_huff_decode_literals", data)
+
+
+def lzw_decode(data, coder=CODER_BIT):
+    """LZWCompressor::decompress (lzw::decode_step restated) on the host"""
+    return _host_decode("tdc_lzw_decode", data, int(coder))
 
 
 def device_count():
@@ -369,6 +389,14 @@ class Context:
                                                   ctypes.byref(st)))
         return self._take(out, n.value), st.as_dict()
 
+    def lzw_compress(self, data, coder=CODER_BIT):
+        """LZWCompressor<BitCoder | EliasGammaCoder>::compress on raw bytes (no escaping).  Returns (stream, stats)."""
+        a = _u8(data)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_lzw_compress(self._h, _ptr(a) if len(a) else None, len(a), coder, ctypes.byref(out), ctypes.byref(n),
+                                                 ctypes.byref(st)))
+        return self._take(out, n.value), st.as_dict()
+
     def bound(self, n, coder=None):
         return self._L.tdc_gpu_lcpcomp_bound(n) if coder is None else self._L.tdc_gpu_lcpcomp_bound_coder(n, coder)
 
@@ -508,6 +536,29 @@ class Context:
             err.required = n.value if rc == -5 else None
             raise err
         return n.value, {"phrases": f.value, "rounds": r.value}
+
+    def lzw_decompress(self, stream, coder=CODER_BIT):
+        """LZWCompressor::decompress: returns the text and {"codes", "rounds", "device_parse"} (option dec_parse picks the path)."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_lzw_decompress(self._h, _ptr(a) if len(a) else None, len(a), coder, ctypes.byref(p), ctypes.byref(n),
+                                                   ctypes.byref(f), ctypes.byref(r)))
+        return self._take(p, n.value), {"codes": f.value, "rounds": r.value,
+                                        "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
+    def lzw_decompress_into(self, stream, out, coder=CODER_BIT):
+        """lzw_decompress into a caller-owned buffer (a PinnedBuffer or a writable uint8 array; `stream` may be a PinnedBuffer too):
+        returns (text length, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the text length."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n = ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.tdc_gpu_lzw_decompress_into(self._h, _ptr(a) if len(a) else None, len(a), coder, _ptr(oa), oa.size, ctypes.byref(n),
+                                                 ctypes.byref(f), ctypes.byref(r))
+        if rc:
+            self._raise_required(rc, n.value)
+        return n.value, {"codes": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
 
     # ---- bwt ---------------------------------------------------------------------------------------------
     def _raise_required(self, rc, n):
@@ -799,6 +850,34 @@ class LZ78Compressor:
         """LZ78Compressor::decompress (:142-160): the stream is parsed and the phrases are expanded on the device."""
         text, _ = self.ctx.lz78_decompress(stream)
         return text
+
+
+class LZWCompressor:
+    """Mirror of tdc::LZWCompressor<coder, trie> (compressors/LZWCompressor.hpp:19-135); no input restrictions.  coder: bit (the
+    reference's default) or gamma; lz78trie is accepted and ignored (every back-end yields the same ids); dict_size must be 0.
+    dec="host": the host loop that restates lzw::decode_step; dec="gpu": the device decoder (tdc_gpu_lzw_decompress)."""
+
+    _CODERS = {"bit": CODER_BIT, "gamma": CODER_GAMMA}
+
+    def __init__(self, ctx, coder="bit", lz78trie="ternary", dec="host", dict_size=0):
+        if coder not in self._CODERS:
+            raise RuntimeError("No implementation found for compressor lzw(coder=%s,lz78trie=%s)" % (coder, lz78trie))
+        if int(dict_size) != 0:
+            raise RuntimeError("lzw: dict_size=%s is not available (only 0, the unlimited dictionary)" % (dict_size,))
+        if dec not in ("host", "gpu"):
+            raise RuntimeError("lzw: dec must be host or gpu")
+        self.ctx, self.coder, self.dec = ctx, self._CODERS[coder], dec
+        self.last_stats = None
+
+    def compress(self, data):
+        out, st = self.ctx.lzw_compress(data, self.coder)
+        self.last_stats = st
+        return out
+
+    def decompress(self, stream):
+        if self.dec == "gpu":
+            return self.ctx.lzw_decompress(stream, self.coder)[0]
+        return lzw_decode(stream, self.coder)
 
 
 class LZSSLCPCompressor:

@@ -33,6 +33,7 @@ SYMBOLS = [
     "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
     "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
     "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
+    "tdc_gpu_lzw_compress", "tdc_gpu_lzw_decompress", "tdc_gpu_lzw_decompress_into", "tdc_lzw_factors", "tdc_lzw_decode",
 ]
 
 
@@ -162,6 +163,11 @@ def load():
     L.tdc_unescape.argtypes = [vp, sz, vp]
     L.tdc_unescape.restype = sz
     L.tdc_lz78_factors.argtypes = [vp, sz, pvp, pvp, psz]
+    L.tdc_lzw_factors.argtypes = [vp, sz, pvp, psz]
+    L.tdc_lzw_decode.argtypes = [vp, sz, i32, vp, sz, psz]
+    L.tdc_gpu_lzw_compress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_lzw_decompress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lzw_decompress_into.argtypes = [vp, vp, sz, i32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     L.tdc_gpu_option_count.argtypes = []
     L.tdc_gpu_option_name.argtypes = [i32]

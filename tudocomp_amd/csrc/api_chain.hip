@@ -431,6 +431,7 @@ int host_decode_entry(const uint8_t* in, size_t len, uint8_t* out, size_t out_ca
         *out_len = sink.n > (u64)SIZE_MAX ? SIZE_MAX : (size_t)sink.n;
         return out && sink.n > out_cap ? TDC_GPU_ERR_ARG : TDC_GPU_OK;
     } catch (const std::runtime_error&) { return TDC_GPU_ERR_ARG;
+    } catch (const std::length_error&) { return TDC_GPU_ERR_TOO_LARGE;       // (lzw_decode: more than 2^32 - 2 bytes)
     } catch (...) { return TDC_GPU_ERR_INTERNAL; }
 }
 }  // namespace
@@ -480,6 +481,10 @@ int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, 
 }
 int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
     return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::huff_decode_literals(in, len, s); });
+}
+int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) return TDC_GPU_ERR_UNSUPPORTED;
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::lzw_decode(in, len, coder == TDC_GPU_CODER_BIT, s); });
 }
 
 }  // extern "C"

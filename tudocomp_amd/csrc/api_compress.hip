@@ -1,4 +1,4 @@
-// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp and lz78 compression -- the upload, the text's arrays, the factors,
+// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78 and lzw compression -- the upload, the text's arrays, the factors,
 // the whole pipeline on host and device buffers.
 #include "api.hpp"
 
@@ -373,7 +373,7 @@ int tdc_gpu_stream_fetch_dev(tdc_gpu_ctx* ctx, void* d_dst, size_t cap, size_t* 
 
 }  // extern "C"
 
-// ---- lzss_lcp, lz78 ------------------------------------------------------------------------------------------------------------------
+// ---- lzss_lcp, lz78, lzw ------------------------------------------------------------------------------------------------------------------
 namespace {
 // shared front end of the two lzss_lcp entry points: text to the device, SA + ISA, factorization into position space
 u8* run_lzss_lcp(Ctx& c, const uint8_t* text, size_t n, uint32_t threshold, DevArrays& A, tdc_gpu_stats* st, Events& ev) {
@@ -476,6 +476,40 @@ int tdc_gpu_lz78_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, int cod
         }
         const int e1 = ev.tick();
         const size_t len = lz78_gamma_encode(c, d_ids, d_chars, z, d_out, cap);
+        const int e2 = ev.tick();
+        sink_download(c, s, d_out, len);
+        const int e3 = ev.tick();
+        if (stats) {
+            stats->n = n; stats->out_len = len; stats->factors = z; stats->arena_bytes = c.arena.high;
+            ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_encode, e1, e2); ev.span(&stats->ms_d2h, e2, e3); ev.span(&stats->ms_total, e0, e3);
+        }
+        ev.finish();
+        sink_commit(s, len);
+    });
+}
+
+int tdc_gpu_lzw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, int coder, uint8_t** out, size_t* out_len,
+                         tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] {
+        if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzw: only coder=bit and coder=gamma are built"};
+        Sink s = sink_malloc(out, out_len);
+        if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+        sink_check(s, "NULL argument");
+        if (n >= 0xFFFFFF00ull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzw: input must be < 2^32 - 256 bytes"};
+        Ctx& c = ctx->c;
+        if (stats) memset(stats, 0, sizeof(*stats));
+        std::vector<u32> codes;
+        const size_t z = lzw_parse_host(in, n, codes);
+        // arena: codes (4 B each) + tile sums + worst-case output (bit: 33 bits, gamma: 2 * 32 + 1 bits: < 9 B per code)
+        const size_t cap = align_up(z * 9 + 64, 8);
+        reserve_arena(c, z * 4 + cap + ((size_t)64 << 20));
+        Events ev(c);
+        const int e0 = ev.tick();
+        u32* d_codes = c.arena.get<u32>(z + 1);
+        u8* d_out = c.arena.get<u8>(cap);
+        if (z) HIP_TRY(hipMemcpyAsync(d_codes, codes.data(), z * 4, hipMemcpyHostToDevice, c.stream));
+        const int e1 = ev.tick();
+        const size_t len = lzw_encode(c, d_codes, z, coder == TDC_GPU_CODER_BIT, d_out, cap);
         const int e2 = ev.tick();
         sink_download(c, s, d_out, len);
         const int e3 = ev.tick();

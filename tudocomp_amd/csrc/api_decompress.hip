@@ -1,4 +1,4 @@
-// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp (also lzss_lcp streams) and lz78 decompression.
+// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp (also lzss_lcp streams), lz78 and lzw decompression.
 #include "api.hpp"
 
 using namespace tdc;
@@ -30,6 +30,21 @@ void lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int co
     if (rounds) *rounds = ds.rounds;
     sink_commit(s, n);
 }
+
+void lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, uint64_t* codes, uint32_t* rounds) {
+    ctx->last_decode_device = 0;
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzw: only coder=bit and coder=gamma are built"};
+    if (!stream && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    DecodeStats ds;
+    size_t need = 0;
+    const size_t n = run_decoder(s, "lzw: the stream decodes to more than 2^32 - 2 bytes", &need,
+                                 [&] { return decode_lzw(ctx->c, stream, len, coder == TDC_GPU_CODER_BIT, s, &need, &ds); });
+    if (codes) *codes = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+    ctx->last_decode_device = (int)ds.device_parse;
+    sink_commit(s, n);
+}
 }  // namespace
 
 extern "C" {
@@ -59,6 +74,16 @@ int tdc_gpu_lz78_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len,
 int tdc_gpu_lz78_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                  size_t* out_len, uint64_t* phrases, uint32_t* rounds) {
     return guarded(ctx, [&] { lz78_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), phrases, rounds); });
+}
+
+int tdc_gpu_lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                           uint64_t* codes, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzw_decompress(ctx, stream, len, coder, sink_malloc(out, out_len, "NULL argument"), codes, rounds); });
+}
+
+int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                size_t* out_len, uint64_t* codes, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzw_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), codes, rounds); });
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include "stages.hpp"
 
 #include <algorithm>
+#include <functional>
 
 namespace tdc {
 
@@ -93,5 +94,24 @@ u8* decode_dest(Sink& o, size_t n);
 // word.  st->rounds receives the number of pointer-jumping rounds.  n < 2^32 - 1 (positions and NONE32 share the u32 range).
 void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
                           u32* d_changed, Sink& out, DecodeStats* st);
+
+
+// ---- what the LZ78 and the LZW decoder share (lz78_decode.hip) ---------------------------------------------------------------------
+// option dec_log: the time since the previous call, on stderr under `who` (synchronises the stream); nothing without the option
+using DecTick = std::function<void(const char*)>;
+DecTick dec_ticker(Ctx& c, const char* who);
+// Items of nv self-delimiting gamma codes (2: LZ78's (id, char) pairs, 1: one LZW code) from bit 0 of the uploaded stream s32 (padded
+// with 64 zero bytes) to bit `total`: next() of every bit position, the orbit of bit 0, the items decoded side by side -- segment by
+// segment (option dec_seg).  ids[k] (and chars[k], nv == 2) receive item k; item k must hold an id <= k + slack.  Returns the number
+// of items.  Malformed input: StreamFormatError; more than zcap items: DecodeItemOverflow, before anything is written behind zcap.
+struct DecodeItemOverflow { u64 items; };
+size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick);
+// Phrases -> text.  LZ78 (lzw = false): phrase k is phrase ids[k] - 1 (none for 0) followed by chars[k].  LZW: phrase k is the byte
+// ids[k] below 256, else phrase ids[k] - 256 and the byte behind it in the text.  Lengths by pointer jumping over the links, starts by
+// one 64-bit scan, then the factor list and the literals go to resolve_and_download.  Returns the text length, *need (nullable) as
+// decode_lz78_gamma; DecodeTooLarge above 2^32 - 2 bytes before anything of that size is allocated; `who` names the caller where
+// out.into is too small.  ids / chars lie in the arena, nothing above them is live.
+size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
+                      const DecTick& tick);
 
 }  // namespace tdc

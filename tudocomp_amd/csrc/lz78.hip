@@ -5,6 +5,7 @@
 // host (option a; lz78_host.cpp).
 // The coder side is data-parallel and runs on the GPU with the same cost / scan / pack scheme as encode.hip:
 // gamma(v) = bits_for(v) zeros, "1", v in bits_for(v) bits; pair i contributes gamma(id_i) gamma(c_i).
+// The kernels take one or two values per item: lzw(coder=gamma) (lzw.hip) writes gamma(code_k) alone.
 #include "stages.hpp"
 #include "prim.hpp"
 
@@ -16,20 +17,22 @@ namespace tdc {
 
 // (the LZ78 parse itself: lz78_host.cpp)
 
-// ---- device: gamma coding of the (id, char) pairs --------------------------------------------------------------
+// ---- device: gamma coding of the items -- (id, char) pairs (PAIR), or single values ------------------------------
 constexpr int G_PER_THREAD = 8;
 constexpr int G_TILE = 256 * G_PER_THREAD;
 
 __device__ __forceinline__ u32 dev_bits_for(u32 v) { return v ? (32u - (u32)__builtin_clz(v)) : 1u; }
-__device__ __forceinline__ u32 gamma_cost(u32 id, u32 ch) { return 2 * dev_bits_for(id) + 2 * dev_bits_for(ch) + 2; }
+template <bool PAIR>
+__device__ __forceinline__ u32 gamma_cost(u32 id, u32 ch) { return 2 * dev_bits_for(id) + 1 + (PAIR ? 2 * dev_bits_for(ch) + 1 : 0); }
 
+template <bool PAIR>
 __global__ __launch_bounds__(256) void gamma_tile_bits_kernel(const u32* __restrict__ ids, const u8* __restrict__ chars, size_t z,
                                                                u64* __restrict__ tile_bits) {
     __shared__ u32 sm[4];
     const size_t i0 = (size_t)blockIdx.x * G_TILE + (size_t)threadIdx.x * G_PER_THREAD;
     u32 sum = 0;
 #pragma unroll
-    for (int j = 0; j < G_PER_THREAD; ++j) if (i0 + j < z) sum += gamma_cost(ids[i0 + j], chars[i0 + j]);
+    for (int j = 0; j < G_PER_THREAD; ++j) if (i0 + j < z) sum += gamma_cost<PAIR>(ids[i0 + j], PAIR ? chars[i0 + j] : 0u);
     sum = wave_reduce_sum(sum);
     if (lane_id() == 0) sm[wave_id()] = sum;
     __syncthreads();
@@ -50,6 +53,7 @@ __device__ __forceinline__ void g_put_bits(u64* __restrict__ out, u64 bitpos, u6
     }
 }
 
+template <bool PAIR>
 __global__ __launch_bounds__(256) void gamma_pack_kernel(const u32* __restrict__ ids, const u8* __restrict__ chars, size_t z,
                                                           const u64* __restrict__ tile_off, u64* __restrict__ out) {
     __shared__ u32 sm[5];
@@ -60,8 +64,8 @@ __global__ __launch_bounds__(256) void gamma_pack_kernel(const u32* __restrict__
     for (int j = 0; j < G_PER_THREAD; ++j) {
         const bool v = i0 + j < z;
         id[j] = v ? ids[i0 + j] : 0u;
-        ch[j] = v ? chars[i0 + j] : 0u;
-        if (v) sum += gamma_cost(id[j], ch[j]);
+        ch[j] = (PAIR && v) ? chars[i0 + j] : 0u;
+        if (v) sum += gamma_cost<PAIR>(id[j], ch[j]);
     }
     u32 total;
     const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
@@ -73,9 +77,11 @@ __global__ __launch_bounds__(256) void gamma_pack_kernel(const u32* __restrict__
             const u32 b1 = dev_bits_for(id[j]);
             g_put_bits(out, pos + b1, (1ull << b1) | id[j], b1 + 1);      // the b1 leading zeros are already there (zeroed buffer)
             pos += 2 * b1 + 1;
-            const u32 b2 = dev_bits_for(ch[j]);
-            g_put_bits(out, pos + b2, (1ull << b2) | ch[j], b2 + 1);
-            pos += 2 * b2 + 1;
+            if (PAIR) {
+                const u32 b2 = dev_bits_for(ch[j]);
+                g_put_bits(out, pos + b2, (1ull << b2) | ch[j], b2 + 1);
+                pos += 2 * b2 + 1;
+            }
         }
     }
 }
@@ -88,8 +94,13 @@ __global__ void gamma_terminator_kernel(u8* out, u64 total_bits) {          // i
     else out[byte + 1] = (u8)u;
 }
 
-// pairs (device) -> gamma bit stream in d_out (zeroed here); returns the stream length in bytes
-size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap) {
+void bit_stream_terminator(Ctx& c, u8* d_out, u64 total_bits) {
+    gamma_terminator_kernel<<<1, 64, 0, c.stream>>>(d_out, total_bits);
+    LAUNCH_CHECK();
+}
+
+// items (device; d_chars == NULL: one value per item) -> gamma bit stream in d_out (zeroed here); returns the stream length in bytes
+size_t gamma_encode_items(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap) {
     hipStream_t s = c.stream;
     const size_t mark = c.arena.mark();
     const unsigned tiles = z ? cdiv(z, G_TILE) : 0;
@@ -98,24 +109,30 @@ size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, 
     if (z) {
         tile_bits = c.arena.get<u64>(tiles + 1);
         u64* d_total = c.arena.get<u64>(1);
-        gamma_tile_bits_kernel<<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits);
+        if (d_chars) gamma_tile_bits_kernel<true><<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits);
+        else gamma_tile_bits_kernel<false><<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits);
         LAUNCH_CHECK();
         exclusive_sum_u64(c, tile_bits, tile_bits, tiles, d_total);
         total_bits = c.read(d_total);
     }
     const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
     const size_t padded = align_up(out_len + 8, 8);
-    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "lz78: output buffer too small", (int)__LINE__};
+    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "gamma coder: output buffer too small", (int)__LINE__};
     HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
     if (z) {
-        gamma_pack_kernel<<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits, (u64*)d_out);
+        if (d_chars) gamma_pack_kernel<true><<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits, (u64*)d_out);
+        else gamma_pack_kernel<false><<<tiles, 256, 0, s>>>(d_ids, d_chars, z, tile_bits, (u64*)d_out);
         LAUNCH_CHECK();
     }
-    gamma_terminator_kernel<<<1, 64, 0, s>>>(d_out, total_bits);
-    LAUNCH_CHECK();
+    bit_stream_terminator(c, d_out, total_bits);
     HIP_TRY(hipStreamSynchronize(s));
     c.arena.release(mark);
     return out_len;
+}
+
+size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap) {
+    if (!d_chars) throw HipError{hipErrorInvalidValue, "lz78: pairs need their chars", (int)__LINE__};
+    return gamma_encode_items(c, d_ids, d_chars, z, d_out, out_cap);
 }
 
 }  // namespace tdc

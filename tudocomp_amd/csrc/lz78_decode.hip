@@ -17,11 +17,16 @@
 // pair cut off by the end of the stream (the reference loops forever on a cut-off unary code), an id field of more than 32 bits, a
 // char field of more than 64 bits (no encoder writes one; it bounds the work of a candidate), and id_k > k (a phrase that does not
 // exist yet).  A decoded length above 2^32 - 2 throws DecodeTooLarge before anything of the text's size is allocated.
+//
+// lzw streams (lzw.hip) are the same two problems with other constants, so both halves are shared (decode.hpp):
+// parse_gamma_items() parses items of one gamma code as well as pairs, expand_phrases() takes the LZW link rule (code - 256, a literal
+// below that) beside the LZ78 one.
 #include "stages.hpp"
 #include "prim.hpp"
 #include "decode.hpp"
 
 #include <chrono>
+#include <memory>
 #include <vector>
 
 namespace tdc {
@@ -36,7 +41,8 @@ constexpr u32 LZD_NW = (LZD_TILE + LZD_REACH + 31) / 32 + 4;      // stream word
 #endif
 
 // The pair that starts at bit x (read_elias_gamma<u32>, read_elias_gamma<u8>): 0 and its end, id and char; < 0: no pair there.
-template <typename Win>
+// NV == 1: the item is the first code alone.
+template <int NV, typename Win>
 __device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end, u32& id, u32& ch) {
     end = x; id = 0; ch = 0;
     const u64 w = bw.peek(x);                                     // (zeros behind the end of the stream)
@@ -45,6 +51,7 @@ __device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end
     if (b1 > 32) return -1;                                       // id field wider than a factorid_t
     if (b1) id = (u32)(bw.peek(x + b1 + 1) >> (64 - b1));
     const u64 y = x + 2 * b1 + 1;
+    if (NV == 1) { end = y; return end > total ? -3 : 0; }
     const u64 v = bw.peek(y);
     u32 b2;
     if (v) b2 = (u32)__builtin_clzll(v);
@@ -57,6 +64,7 @@ __device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end
 }
 
 // next() for the bit positions x_in .. x_in + m - 1 (index = position - x_in); m: the pair leaves the segment, or there is no pair
+template <int NV>
 __global__ __launch_bounds__(256) void lz_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, u64 total, u32* __restrict__ next) {
     __shared__ u32 sw[LZD_NW];
     const u32 i0 = blockIdx.x * LZD_TILE;
@@ -70,37 +78,42 @@ __global__ __launch_bounds__(256) void lz_next_kernel(const u32* __restrict__ s3
         if (idx >= m) break;
         u64 end; u32 id, ch;
         u32 r = m;
-        if (lz_pair(bw, x_in + idx, total, end, id, ch) == 0) { const u64 d = end - x_in; r = d < (u64)m ? (u32)d : m; }
+        if (lz_pair<NV>(bw, x_in + idx, total, end, id, ch) == 0) { const u64 d = end - x_in; r = d < (u64)m ? (u32)d : m; }
         next[idx] = r;
     }
 }
 
 struct LzScalars { u64 exit_bit; u32 err; u32 pad; };
 
-// the pairs of a segment (offsets idx[0 .. cnt)), global pair index k0 + j: id, char, validation; the last one reports the exit
+// the pairs of a segment (offsets idx[0 .. cnt)), global pair index k0 + j: id, char, validation (id <= k + slack: 0 for LZ78, where
+// id k is the newest phrase; 255 for LZW, whose code 256 + j names phrase j); the last one reports the exit
+template <int NV>
 __global__ __launch_bounds__(256) void lz_pairs_kernel(const u32* __restrict__ s32, u64 x_in, const u32* __restrict__ idx, u32 cnt, u64 total,
-                                                        u64 k0, u32* __restrict__ ids, u8* __restrict__ chars, LzScalars* __restrict__ sc) {
+                                                        u64 k0, u32 slack, u32* __restrict__ ids, u8* __restrict__ chars,
+                                                        LzScalars* __restrict__ sc) {
     const BitWinG bw{s32, total};
     for (u32 j = blockIdx.x * 256 + threadIdx.x; j < cnt; j += gridDim.x * 256) {
         const u64 x = x_in + idx[j];
         const u64 k = k0 + j;
         u64 end; u32 id, ch;
-        const int st = lz_pair(bw, x, total, end, id, ch);
+        const int st = lz_pair<NV>(bw, x, total, end, id, ch);
+        const bool late = (u64)id > k + slack;
         if (st < 0) atomicOr(&sc->err, 1u);
-        else if ((u64)id > k) atomicOr(&sc->err, 2u);
-        ids[k] = (st < 0 || (u64)id > k) ? 0u : id;
-        chars[k] = (u8)ch;
+        else if (late) atomicOr(&sc->err, 2u);
+        ids[k] = (st < 0 || late) ? 0u : id;
+        if (NV == 2) chars[k] = (u8)ch;
         if (j == cnt - 1) sc->exit_bit = end;
     }
 }
 
 // J[k] = (link << 32) | acc: len_k = acc + len(link), link = NONE32 once acc is the length
 // (the per-phrase kernels loop with a grid stride: up to 2^32 - 2 phrases, launched with dec_grid())
-__global__ void lz_link_kernel(const u32* __restrict__ ids, size_t z, u64* __restrict__ J) {
+// base: the value that names phrase 0 -- 1 for LZ78 ids, 256 for LZW codes; smaller values link nowhere
+__global__ void lz_link_kernel(const u32* __restrict__ ids, size_t z, u32 base, u64* __restrict__ J) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += stride) {
         const u32 id = ids[k];
-        J[k] = ((u64)(id ? id - 1 : NONE32) << 32) | 1ull;
+        J[k] = ((u64)(id >= base ? id - base : NONE32) << 32) | 1ull;
     }
 }
 
@@ -134,14 +147,22 @@ __global__ void lz_len_kernel(const u64* __restrict__ J, size_t z, u64* __restri
 }
 
 // phrase k -> factor (start_k, start_{id_k - 1}, len_k - 1); S = the phrase starts (n <= 2^32 - 2: they fit 32 bits)
+// LZW: code c >= 256 -> the factor (start_k, start_{c - 256}, len_k), one byte longer than its source phrase (a KwKwK code overlaps its
+// own first byte); a literal code is a factor of length 0
+template <bool LZW>
 __global__ void lz_factor_kernel(const u32* __restrict__ ids, const u64* __restrict__ J, const u64* __restrict__ S, size_t z,
                                  u32* __restrict__ fpos, u32* __restrict__ fsrc, u32* __restrict__ flen) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += stride) {
         const u32 id = ids[k];
         fpos[k] = (u32)S[k];
-        fsrc[k] = id ? (u32)S[id - 1] : 0u;
-        flen[k] = (u32)J[k] - 1u;
+        if (LZW) {
+            fsrc[k] = id >= 256u ? (u32)S[id - 256u] : 0u;
+            flen[k] = id >= 256u ? (u32)J[k] : 0u;
+        } else {
+            fsrc[k] = id ? (u32)S[id - 1] : 0u;
+            flen[k] = (u32)J[k] - 1u;
+        }
     }
 }
 
@@ -150,6 +171,12 @@ __global__ void lz_literal_kernel(const u32* __restrict__ fpos, const u32* __res
                                   u8* __restrict__ text) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += stride) text[(size_t)fpos[k] + flen[k]] = chars[k];
+}
+// LZW: a code below 256 is its byte
+__global__ void lzw_literal_kernel(const u32* __restrict__ fpos, const u32* __restrict__ codes, size_t z, u8* __restrict__ text) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += stride)
+        if (codes[k] < 256u) text[fpos[k]] = (u8)codes[k];
 }
 
 // The arena is too small for what follows: the live arrays travel to the host and back into an arena of `bytes` (the size this call
@@ -173,40 +200,15 @@ void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, 
 
 }  // namespace
 
-size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t* need, DecodeStats* st) {
-    DecodeStats local;
-    if (!st) st = &local;
-    *st = DecodeStats();
-    const u64 total = FastBits(stream, len).total;                                     // (throws for a cut-off terminator)
-    if (total == 0) { decode_dest(out, 0); if (need) *need = 0; return 0; }             // the empty text's stream: no pairs
+size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick) {
     hipStream_t s = c.stream;
-    const bool dlog = c.dec_log != 0;                                                    // stage times on stderr (synchronises)
-    auto t_last = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
-        if (!dlog) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "lz78 decode: %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    // a pair takes 2 bits at least ("1" "1": id 0, char 0), and more than 2^32 - 2 pairs decode to more than 2^32 - 2 bytes
-    const u64 zcap = std::min<u64>(total / 2 + 1, 0xFFFFFFFEull);
     const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;                      // (tests shrink the segments)
-    const size_t seg = (size_t)std::min<u64>(seg_bits, total);
-    const size_t slack = (size_t)16 << 20;
-    c.ensure_arena(len + 64 + zcap * 5 + seg * 13 + slack);
-    void* d_stream = c.arena.get<u8>(len + 64);
-    u32* ids = c.arena.get<u32>(zcap);
-    u8* chars = c.arena.get<u8>(zcap + 64);
     LzScalars* d_sc = (LzScalars*)c.arena.alloc(sizeof(LzScalars));
     u32* d_cnt = c.arena.get<u32>(2);
-    HIP_TRY(hipMemcpyAsync(d_stream, stream, len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync((u8*)d_stream + len, 0, 64, s));
     HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(LzScalars), s));
-    const u32* s32 = (const u32*)d_stream;                                              // (arena allocations are 256-byte aligned)
-    tick("upload");
-
-    // ---- pair starts and pairs, segment by segment
+    static const char* const BAD_CHAIN[2] = {"corrupt stream: code chain", "corrupt stream: pair chain"};
+    static const char* const BAD_ITEM[2] = {"corrupt stream: malformed or cut-off code", "corrupt stream: malformed or cut-off pair"};
+    static const char* const BAD_ID[2] = {"corrupt stream: invalid compressed code", "corrupt stream: phrase id out of range"};
     size_t z = 0;
     u64 x_in = 0;
     while (x_in < total) {
@@ -215,7 +217,8 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
         u32* next = c.arena.get<u32>(m);
         u32* e1 = c.arena.get<u32>(m), *e2 = c.arena.get<u32>(m);
         u8* mark = c.arena.get<u8>(m);
-        lz_next_kernel<<<cdiv(m, LZD_TILE), 256, 0, s>>>(s32, x_in, m, total, next);
+        if (nv == 2) lz_next_kernel<2><<<cdiv(m, LZD_TILE), 256, 0, s>>>(s32, x_in, m, total, next);
+        else lz_next_kernel<1><<<cdiv(m, LZD_TILE), 256, 0, s>>>(s32, x_in, m, total, next);
         LAUNCH_CHECK();
         tick("next() of every bit");
         mark_orbit_u32(c, next, m, mark, e1, e2);
@@ -223,29 +226,38 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
         u32* idx = e1;                                                                  // (the exit arrays are free again)
         select_by_class(c, mark, 1, m, nullptr, idx, nullptr, nullptr, d_cnt);
         const u32 cnt = c.read(d_cnt);
-        tick("pair list");
-        if (cnt == 0) throw StreamFormatError{"corrupt stream: pair chain"};
-        if (z + cnt > zcap) throw DecodeTooLarge{z + cnt};                              // (more pairs than 2^32 - 2: more bytes)
-        lz_pairs_kernel<<<std::min<u32>(cdiv(cnt, 256), 4096u), 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, ids, chars, d_sc);
+        tick(nv == 2 ? "pair list" : "code list");
+        if (cnt == 0) throw StreamFormatError{BAD_CHAIN[nv - 1]};
+        if (z + cnt > zcap) throw DecodeItemOverflow{z + cnt};
+        const unsigned g = std::min<u32>(cdiv(cnt, 256), 4096u);
+        if (nv == 2) lz_pairs_kernel<2><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, slack, ids, chars, d_sc);
+        else lz_pairs_kernel<1><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, slack, ids, chars, d_sc);
         LAUNCH_CHECK();
         const LzScalars h = c.read(d_sc);
-        tick("pair decode");
+        tick(nv == 2 ? "pair decode" : "code decode");
         c.arena.release(mk);
         z += cnt;
-        if (h.err & 1u) throw StreamFormatError{"corrupt stream: malformed or cut-off pair"};
-        if (h.err & 2u) throw StreamFormatError{"corrupt stream: phrase id out of range"};
+        if (h.err & 1u) throw StreamFormatError{BAD_ITEM[nv - 1]};
+        if (h.err & 2u) throw StreamFormatError{BAD_ID[nv - 1]};
         if (h.exit_bit >= total) break;
-        if (h.exit_bit <= x_in) throw StreamFormatError{"corrupt stream: pair chain"};
+        if (h.exit_bit <= x_in) throw StreamFormatError{BAD_CHAIN[nv - 1]};
         x_in = h.exit_bit;
     }
-    st->factors = z;
+    return z;
+}
 
+size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
+                      const DecTick& tick) {
+    hipStream_t s = c.stream;
+    const size_t slack = (size_t)16 << 20;
+    const size_t zc = lzw ? 0 : z;                                                      // bytes of chars[] that live on
+    u32* d_cnt = c.arena.get<u32>(2);
     // ---- phrase lengths (pointer jumping), starts (64-bit scan), factor list
     {
         const size_t need1 = c.arena.mark() + z * 28 + slack;
         if (c.arena.size < need1) {
             void* pi = ids; void* pc = chars;
-            regrow_arena(c, need1, {{&pi, z * 4}, {&pc, z}});
+            regrow_arena(c, need1, {{&pi, z * 4}, {&pc, zc}});
             ids = (u32*)pi; chars = (u8*)pc;
             d_cnt = c.arena.get<u32>(2);
         }
@@ -255,12 +267,12 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
     u64* J = c.arena.get<u64>(z);
     u64* S = c.arena.get<u64>(z);
     u64* d_total = c.arena.get<u64>(1);
-    lz_link_kernel<<<dec_grid(z), 256, 0, s>>>(ids, z, J);
+    lz_link_kernel<<<dec_grid(z), 256, 0, s>>>(ids, z, lzw ? 256u : 1u, J);
     LAUNCH_CHECK();
     unsigned g = cdiv(z, 256 * 8); if (g > 16384) g = 16384;
     u32 len_rounds = 0;
     for (u32 round = 0;; ++round) {
-        if (round > 40) throw HipError{hipErrorUnknown, "lz78 decode: phrase lengths did not converge", (int)__LINE__};   // depth < 2^32
+        if (round > 40) throw HipError{hipErrorUnknown, "phrase lengths did not converge", (int)__LINE__};   // depth < 2^32
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(u32), s));
         lz_len_jump_kernel<<<g, 256, 0, s>>>(J, z, d_cnt);
         LAUNCH_CHECK();
@@ -274,8 +286,9 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
     tick("phrase lengths + starts");
     if (need) *need = (size_t)n;
     if (n > 0xFFFFFFFEull) throw DecodeTooLarge{n};                                     // checked before any text-sized allocation
-    if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, "lz78 decode: the caller's buffer is too small for the text", (int)__LINE__};
-    lz_factor_kernel<<<dec_grid(z), 256, 0, s>>>(ids, J, S, z, fpos, fsrc, flen);
+    if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, who, (int)__LINE__};
+    if (lzw) lz_factor_kernel<true><<<dec_grid(z), 256, 0, s>>>(ids, J, S, z, fpos, fsrc, flen);
+    else lz_factor_kernel<false><<<dec_grid(z), 256, 0, s>>>(ids, J, S, z, fpos, fsrc, flen);
     LAUNCH_CHECK();
     c.arena.release(mkB);
     tick("factor list");
@@ -284,21 +297,61 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
     {
         const size_t need2 = c.arena.mark() + (size_t)n * 5 + (size_t)n / 8 + slack;
         if (c.arena.size < need2) {
-            void* pp = fpos; void* ps = fsrc; void* pl = flen; void* pc = chars;
-            regrow_arena(c, need2, {{&pp, z * 4}, {&ps, z * 4}, {&pl, z * 4}, {&pc, z}});
-            fpos = (u32*)pp; fsrc = (u32*)ps; flen = (u32*)pl; chars = (u8*)pc;
+            void* pp = fpos; void* ps = fsrc; void* pl = flen; void* pc = chars; void* pi = ids;
+            regrow_arena(c, need2, {{&pp, z * 4}, {&ps, z * 4}, {&pl, z * 4}, {&pc, zc}, {&pi, lzw ? z * 4 : 0}});
+            fpos = (u32*)pp; fsrc = (u32*)ps; flen = (u32*)pl; chars = (u8*)pc; ids = (u32*)pi;
             d_cnt = c.arena.get<u32>(2);
         }
     }
     u8* d_text = c.arena.get<u8>((size_t)n + 64);
     u32* d_ref = c.arena.get<u32>((size_t)n);
-    lz_literal_kernel<<<dec_grid(z), 256, 0, s>>>(fpos, flen, chars, z, d_text);
+    if (lzw) lzw_literal_kernel<<<dec_grid(z), 256, 0, s>>>(fpos, ids, z, d_text);
+    else lz_literal_kernel<<<dec_grid(z), 256, 0, s>>>(fpos, flen, chars, z, d_text);
     LAUNCH_CHECK();
     tick("literals");
     resolve_and_download(c, (size_t)n, d_text, d_ref, fpos, fsrc, flen, z, d_cnt, out, st);
     st->rounds += len_rounds;
     tick("references + download");
     return (size_t)n;
+}
+
+size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t* need, DecodeStats* st) {
+    DecodeStats local;
+    if (!st) st = &local;
+    *st = DecodeStats();
+    const u64 total = FastBits(stream, len).total;                                     // (throws for a cut-off terminator)
+    if (total == 0) { decode_dest(out, 0); if (need) *need = 0; return 0; }             // the empty text's stream: no pairs
+    hipStream_t s = c.stream;
+    const DecTick tick = dec_ticker(c, "lz78 decode");
+    // a pair takes 2 bits at least ("1" "1": id 0, char 0), and more than 2^32 - 2 pairs decode to more than 2^32 - 2 bytes
+    const u64 zcap = std::min<u64>(total / 2 + 1, 0xFFFFFFFEull);
+    const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;
+    const size_t seg = (size_t)std::min<u64>(seg_bits, total);
+    const size_t slack = (size_t)16 << 20;
+    c.ensure_arena(len + 64 + zcap * 5 + seg * 13 + slack);
+    void* d_stream = c.arena.get<u8>(len + 64);
+    u32* ids = c.arena.get<u32>(zcap);
+    u8* chars = c.arena.get<u8>(zcap + 64);
+    HIP_TRY(hipMemcpyAsync(d_stream, stream, len, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync((u8*)d_stream + len, 0, 64, s));
+    tick("upload");
+    size_t z;
+    try { z = parse_gamma_items(c, (const u32*)d_stream, total, 2, 0, zcap, ids, chars, tick); }    // (arena allocations are 256-byte aligned)
+    catch (const DecodeItemOverflow& e) { throw DecodeTooLarge{e.items}; }              // (more pairs than 2^32 - 2: more bytes)
+    st->factors = z;
+    return expand_phrases(c, ids, chars, z, false, "lz78 decode: the caller's buffer is too small for the text", out, need, st, tick);
+}
+
+DecTick dec_ticker(Ctx& c, const char* who) {
+    if (!c.dec_log) return [](const char*) {};
+    auto t_last = std::make_shared<std::chrono::steady_clock::time_point>(std::chrono::steady_clock::now());
+    hipStream_t s = c.stream;
+    return [=](const char* what) {                                                       // stage times on stderr (synchronises)
+        (void)hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s: %-26s %8.2f ms\n", who, what, std::chrono::duration<double, std::milli>(now - *t_last).count());
+        *t_last = now;
+    };
 }
 
 }  // namespace tdc

@@ -13,59 +13,9 @@
 // already in cache.  A phrase costs about one memory latency instead of one per byte.  Nothing is approximate: the hash only says
 // where a node is kept (linear probing behind it), what is compared is (parent, byte) as before.
 #include "stages_host.hpp"
-
-#include <stdlib.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <new>
-#include <utility>
+#include "phrase_table.hpp"
 
 namespace tdc {
-namespace {
-
-struct PhraseTable {                 // open addressing; key = (parent << 8 | byte) + 1 (0: empty), value = child id
-    struct Slot { uint64_t key; uint32_t val; uint32_t htop; };     // htop: upper half of the string hash (placement after a growth)
-    struct Buf {
-        Slot* p = nullptr; size_t n = 0;
-        ~Buf() { free(p); }
-        void alloc(size_t count) {
-            free(p); p = nullptr; n = count;
-            const size_t bytes = (count * sizeof(Slot) + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-            p = (Slot*)aligned_alloc((size_t)2 << 20, bytes);       // the table of a 1 GB input is gigabytes large and every miss lands on
-            if (!p) throw std::bad_alloc();                         // a random page: huge pages where the kernel grants them
-#ifdef MADV_HUGEPAGE
-            (void)madvise(p, bytes, MADV_HUGEPAGE);
-#endif
-            memset(p, 0, count * sizeof(Slot));
-        }
-        void swap(Buf& o) { std::swap(p, o.p); std::swap(n, o.n); }
-    } slots;
-    uint64_t mask = 0;
-    int shift = 64;                                                 // slot of a hash: h >> shift
-    size_t used = 0;
-    void init(size_t cap_pow2) {
-        slots.alloc(cap_pow2); mask = cap_pow2 - 1; used = 0;
-        shift = 64; for (size_t c = cap_pow2; c > 1; c >>= 1) --shift;
-    }
-    size_t home(uint64_t h) const { return shift == 64 ? 0 : (size_t)(h >> shift); }
-    void grow() {
-        Buf os; os.swap(slots);
-        init((mask + 1) * 2);
-        for (size_t i = 0; i < os.n; ++i) if (os.p[i].key) {
-            size_t at = home((uint64_t)os.p[i].htop << 32);
-            while (slots.p[at].key) at = (at + 1) & mask;
-            slots.p[at] = os.p[i]; ++used;
-        }
-    }
-};
-
-// hash of a phrase prefix from the hash of the prefix one byte shorter (a function of the string alone)
-inline uint64_t roll(uint64_t h, uint8_t c) {
-    h = (h ^ ((uint64_t)c + 1)) * 0x9E3779B97F4A7C15ull;
-    return h ^ (h >> 29);
-}
-
-}  // namespace
 
 size_t lz78_parse_host(const uint8_t* in, size_t n, std::vector<uint32_t>& ids, std::vector<uint8_t>& chars, bool* leftover_is_high) {
     ids.clear(); chars.clear();
@@ -79,7 +29,7 @@ size_t lz78_parse_host(const uint8_t* in, size_t n, std::vector<uint32_t>& ids, 
     // depths requested ahead of the one being verified: a little more than a phrase is long (measured at 1e8 B of English-like text, 9.3
     // bytes per phrase: W = 10 -> 11 MB/s, 12 -> 27, 16 -> 25: a phrase that outruns its window waits for memory at every further
     // step, a window far beyond the phrase's end costs page walks for slots nobody looks at).  The window follows the running mean.
-    constexpr size_t RING = 64;                                    // (a power of two > the largest window)
+    constexpr size_t RING = PHRASE_RING;
     size_t W = 12, nphr = 0, last_i = 0;
     uint32_t next_id = 1;                                          // root = 0, ids in insertion order from 1 (LZ78Compressor.hpp:78-84)
     size_t i = 0;
@@ -89,7 +39,7 @@ size_t lz78_parse_host(const uint8_t* in, size_t n, std::vector<uint32_t>& ids, 
     while (i < n) {                                                // one phrase per iteration (:97-121)
         if ((tab.used + 1) * 2 >= tab.mask) tab.grow();
         node = 0; parent = 0;
-        uint64_t h = 0x243F6A8885A308D3ull;                        // hash of the empty prefix
+        uint64_t h = PHRASE_HASH0;
         size_t pa = i;                                             // the prefixes text[i .. pa) have been hashed and their slots requested
         for (;;) {
             // (a sliding window: every verified depth requests one more, so a long phrase never stops to wait for a new batch)
@@ -109,7 +59,7 @@ size_t lz78_parse_host(const uint8_t* in, size_t n, std::vector<uint32_t>& ids, 
             node = 0; parent = 0;
             if ((++nphr & 0xFFFFu) == 0) {                          // mean phrase length of the last 65 536 phrases + 3, within [8, 48]
                 const size_t mean = (i - last_i + 0x8000u) >> 16;
-                W = mean + 3 < 8 ? 8 : (mean + 3 > 48 ? 48 : mean + 3);
+                W = phrase_window(mean);
                 last_i = i;
             }
             break;

@@ -201,6 +201,20 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
 size_t lz78_parse_host(const u8* in, size_t n, std::vector<u32>& ids, std::vector<u8>& chars, bool* leftover_is_high);
 // a16: coders/EliasGammaCoder.hpp:26-29 + io/BitOStream.hpp:105-129 on the device; returns the stream length
 size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap);
+// the same kernels for items of one value (d_chars == NULL) or two; the reference's bit-stream terminator at bit total_bits of d_out
+size_t gamma_encode_items(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap);
+void bit_stream_terminator(Ctx& c, u8* d_out, u64 total_bits);
+
+// ---- lzw (compressors/LZWCompressor.hpp, lzw/LZWDecoding.hpp; lzw_host.cpp, lzw.hip) -----------------------
+// :39-108 -- the sequential parse on the host: codes[k] = id of the node phrase k ends in; returns the number of codes
+size_t lzw_parse_host(const u8* in, size_t n, std::vector<u32>& codes);
+// the codes (device) -> the stream in d_out, terminator included; bit: BitCoder (code k in bits_for(k + 256) bits), else EliasGammaCoder.
+// Returns the stream length.  d_out needs no zeroing for BitCoder (every word is written whole).
+size_t lzw_encode(Ctx& c, const u32* d_codes, size_t z, bool bit, u8* d_out, size_t out_cap);
+// :110-133 -- on the device for streams of LZW_DEVICE_MIN bytes and more (option dec_parse: 2 = every stream, 0 = never), else the host
+// loop (decode_step restated).  Results and exceptions as decode_lz78_gamma; st->device_parse tells which path ran.
+constexpr size_t LZW_DEVICE_MIN = (size_t)64 << 10;
+size_t decode_lzw(Ctx& c, const u8* stream, size_t len, bool bit, Sink& out, size_t* need, DecodeStats* st);
 
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform

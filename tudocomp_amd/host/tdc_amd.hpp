@@ -457,6 +457,51 @@ public:
     }
 };
 
+// tdc::LZWCompressor<BitCoder | EliasGammaCoder, trie>  (compressors/LZWCompressor.hpp:19-135): no input restrictions.  coder defaults to
+// bit, as in the reference; lz78trie is accepted and ignored (every back-end yields the same ids); dict_size must be 0 (no resets).
+class LZWCompressor : public Compressor {
+    AlgorithmValue m_opts;
+    std::shared_ptr<GpuContext> m_ctx;
+    int m_device = 0;
+    int m_coder = TDC_GPU_CODER_BIT;
+public:
+    tdc_gpu_stats last_stats{};
+    void set_device(int d) { m_device = d; }
+    LZWCompressor(AlgorithmValue opts, std::shared_ptr<GpuContext> ctx) : m_opts(std::move(opts)), m_ctx(std::move(ctx)) {
+        const std::string coder = m_opts.get("coder", "bit");
+        if (coder == "gamma") m_coder = TDC_GPU_CODER_GAMMA;
+        else if (coder != "bit") throw std::runtime_error("No implementation found for compressor lzw(coder=" + coder + ")");   // Registry.hpp:214
+        if (m_opts.get("dict_size", "0") != "0")
+            throw std::runtime_error("lzw: dict_size=" + m_opts.get("dict_size", "0") + " is not available (only dict_size=0, the unlimited dictionary)");
+    }
+    void compress(Input& input, Output& output) override {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const bytes& in = input.raw();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_lzw_compress(m_ctx->h, in.data(), in.size(), m_coder, &out, &out_len, &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
+    }
+    // LZWCompressor::decompress (:110-133): the host loop of tdc_coders.hpp (lzw::decode_step restated), which needs no device;
+    // dec=gpu (an addition, as for lz78): the device decoder (tdc_gpu_lzw_decompress).  The stream is the same either way.
+    void decompress(Input& input, Output& output) override {
+        const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_lzw_decompress(m_ctx->h, in.data(), in.size(), m_coder, &out, &out_len, nullptr, nullptr);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
+        struct { bytes v; void put(uint8_t c) { v.push_back(c); } } text;
+        lzw_decode(in.data(), in.size(), m_coder == TDC_GPU_CODER_BIT, text);
+        output.write(text.v.data(), text.v.size());
+    }
+};
+
 // tdc::BWTCompressor (compressors/BWTCompressor.hpp:14-67, ds/bwt.hpp): the Burrows-Wheeler transform of the escaped, 0-terminated view;
 // n bytes out, no header.
 class BWTCompressor : public Compressor {
@@ -630,6 +675,10 @@ inline std::vector<std::string> registered_algorithms() {
              "lzss_lcp(coder=huff, threshold=3)                                           [MI355X, libtdc_gpu.so]",
              "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]",
              "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]",
+             "lzw(coder=bit)                                                              [host parse + MI355X packer from closed-form bit offsets]",
+             "lzw(coder=gamma)                                                            [host parse + MI355X gamma packer]",
+             "lzw(coder=bit, dec=gpu)                                                     [decompression on the MI355X: codes read side by side, phrases expanded by pointer jumping]",
+             "lzw(coder=gamma, dec=gpu)                                                   [decompression parsed and expanded on the MI355X]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
              "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
              "rle                                                                         [MI355X; host decoder]",
@@ -655,6 +704,12 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
     }
     if (av.name == "lz78") {
         auto z = std::make_unique<LZ78Compressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dec"}), std::move(ctx));
+        z->set_device(device);
+        s.compressor = std::move(z);
+        return s;
+    }
+    if (av.name == "lzw") {
+        auto z = std::make_unique<LZWCompressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dict_size", "dec"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;

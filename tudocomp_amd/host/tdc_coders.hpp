@@ -481,4 +481,66 @@ template <typename sink_t> inline void huff_decode_literals(const uint8_t* in, s
     while (!dec.eof()) os.put(dec.template decode<uliteral_t>(literal_r));
 }
 
+// ---- LZWCompressor::decompress (compressors/LZWCompressor.hpp:110-133) with lzw::decode_step (lzw/LZWDecoding.hpp:12-99) restated ------
+// The specification of the device decoder (csrc/lzw.hip), its path for small streams, and the text of the C ABI's tdc_lzw_decode.
+// bit: BitCoder -- code k (0-based) in bits_for(k + 256) bits; else EliasGammaCoder.  dict_size = 0: the dictionary is never reset.
+// Dictionary entry 256 + j = (code j, first byte of string j + 1); a string is rebuilt byte by byte along that chain (:31-47).
+// Refused (std::runtime_error): code k above 255 + k (:72-76 "invalid compressed code"; code 0 = 256 would read an empty string), a code
+// cut off by the end of the stream (the reference reads zeros there), a gamma field of more than 32 bits.  More than 2^32 - 2 bytes
+// of text: std::length_error.
+template <typename sink_t> inline void lzw_decode(const uint8_t* in, size_t n, bool bit, sink_t& os) {
+    if (!n) return;
+    const unsigned u = in[n - 1] & 7u;                           // io/BitIStream.hpp:27-63: the bits in front of the terminator
+    if (u >= 6 && n < 2) throw std::runtime_error("corrupt stream: truncated stream");
+    const uint64_t total = u >= 6 ? (uint64_t)(n - 2) * 8 + u : (uint64_t)(n - 1) * 8 + u;
+    uint64_t pos = 0;
+    auto peek = [&]() -> uint64_t {                              // the next 57 bits and more, left-aligned; zeros behind the end
+        uint64_t w = 0;
+        const size_t b = (size_t)(pos >> 3);
+        for (size_t i = 0; i < 8; ++i) w = (w << 8) | (b + i < n ? in[b + i] : 0);
+        w <<= (pos & 7);
+        const uint64_t valid = total - pos;
+        return valid >= 64 ? w : (valid ? w & (~0ull << (64 - valid)) : 0);
+    };
+    std::vector<uint32_t> parent;
+    std::vector<uint8_t> last, tmp;
+    auto rebuild = [&](uint64_t x) {                             // rebuild_string: tmp = the string of x behind its first byte, reversed
+        tmp.clear();
+        while (x >= 256) { tmp.push_back(last[x - 256]); x = parent[x - 256]; }
+        return (uint8_t)x;
+    };
+    uint64_t k = 0, prev = 0, len = 0;
+    while (pos < total) {
+        uint64_t c;
+        if (bit) {
+            const unsigned w = coder_bits_for(k + 256);
+            if (pos + w > total) throw std::runtime_error("corrupt stream: cut-off code");
+            c = peek() >> (64 - w);
+            pos += w;
+        } else {
+            const uint64_t v = peek();
+            const unsigned b = v ? (unsigned)__builtin_clzll(v) : 64u;
+            if (b > 32 || pos + 2 * b + 1 > total) throw std::runtime_error("corrupt stream: malformed or cut-off code");
+            pos += b + 1;
+            c = b ? peek() >> (64 - b) : 0;
+            pos += b;
+        }
+        if (c > 255 + k) throw std::runtime_error("corrupt stream: invalid compressed code");
+        uint8_t head;
+        if (k && c == 255 + k) {                                 // :80-84 the entry is made first, from the previous string's first byte
+            parent.push_back((uint32_t)prev); last.push_back(rebuild(prev));
+            head = rebuild(c);
+        } else {                                                 // :85-91
+            head = rebuild(c);
+            if (k) { parent.push_back((uint32_t)prev); last.push_back(head); }
+        }
+        len += tmp.size() + 1;
+        if (len > 0xFFFFFFFEull) throw std::length_error("lzw: the stream decodes to more than 2^32 - 2 bytes");
+        os.put(head);
+        for (size_t i = tmp.size(); i-- > 0; ) os.put(tmp[i]);
+        prev = c;
+        ++k;
+    }
+}
+
 }  // namespace tdc_amd
