@@ -96,7 +96,8 @@ void tdc_gpu_ctx_destroy(tdc_gpu_ctx* ctx);
  * (an embedding process cannot change the algorithm by accident) -- unless TDC_GPU_DEBUG_KNOBS=1 is set, in which case
  * tdc_gpu_ctx_create() applies every TDC_GPU_<OPTION NAME IN UPPER CASE> variable through this same function (development aid,
  * tools/ab.sh).  `name`: an option name (README.md lists them; "wsort_min" and "TDC_GPU_WSORT_MIN" are the same option); out-of-range
- * values are clamped.  TDC_GPU_ERR_ARG for an unknown name.  tdc_gpu_option_count / _name enumerate the table. */
+ * values are clamped.  TDC_GPU_ERR_ARG for an unknown name.  tdc_gpu_option_count / _name enumerate the table -- all of it but
+ * the switches of folded passes (fused_cand, sel_tile_counts: README.md), which this function accepts like any other. */
 int tdc_gpu_ctx_set_option(tdc_gpu_ctx* ctx, const char* name, long value);
 int tdc_gpu_option_count(void);
 const char* tdc_gpu_option_name(int i);
@@ -251,6 +252,10 @@ int tdc_gpu_prim_msd_partition(tdc_gpu_ctx* ctx, uint32_t* idx, uint32_t* val, s
  * elements of srcA (NULL: their indices) / srcB in order, *count their number */
 int tdc_gpu_prim_select(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t want, size_t m, const uint32_t* srcA, const uint64_t* srcB,
                         uint32_t fillA, uint64_t fillB, uint32_t* outA, uint64_t* outB, uint32_t* count);
+/* select_by_class with the per-tile counts handed in (tile_counts[t] = number of cls[k] == want, 2048 t <= k < 2048 (t + 1); anything
+ * else is refused): outA as above */
+int tdc_gpu_prim_select_counts(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t want, size_t m, const uint32_t* srcA, const uint32_t* tile_counts,
+                               uint32_t fillA, uint32_t* outA, uint32_t* count);
 /* mark_orbit_u32: mark[i] = 1 on the chain 0, next[0], next[next[0]], ... and 0 elsewhere; i < next[i] <= n for every i */
 int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, uint8_t* mark);
 

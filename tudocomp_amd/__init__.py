@@ -466,6 +466,22 @@ class Context:
                                                 int(fill_a), int(fill_b), _ptr(oa), None if ob is None else _ptr(ob), ctypes.byref(cnt)))
         return oa, ob, cnt.value
 
+    def prim_select_counts(self, cls, want, tile_counts, src_a=None, fill_a=0xFFFFFFFF):
+        """select_by_class with the per-tile counts (2 048 classes per tile) handed in; returns (outA, count)."""
+        c = np.ascontiguousarray(cls, dtype=np.uint8)
+        m = len(c)
+        t = np.ascontiguousarray(tile_counts, dtype=np.uint32)
+        if len(t) != (m + 2047) // 2048:
+            raise ValueError("one count per tile of 2048 classes")
+        a = None if src_a is None else np.ascontiguousarray(src_a, dtype=np.uint32)
+        if a is not None and len(a) != m:
+            raise ValueError("cls and src_a differ in length")
+        oa = np.empty(m, dtype=np.uint32)
+        cnt = ctypes.c_uint32(0)
+        self._check(self._L.tdc_gpu_prim_select_counts(self._h, _ptr(c), int(want), m, None if a is None else _ptr(a), _ptr(t),
+                                                       int(fill_a), _ptr(oa), ctypes.byref(cnt)))
+        return oa, cnt.value
+
     def prim_mark_orbit(self, nxt):
         """mark_orbit_u32; returns mark (u8)."""
         a = np.ascontiguousarray(nxt, dtype=np.uint32)

@@ -18,7 +18,7 @@ SYMBOLS = [
     "tdc_gpu_lcpcomp_bound", "tdc_gpu_lcpcomp_bound_coder", "tdc_gpu_lcpcomp_compress_into", "tdc_gpu_host_alloc", "tdc_gpu_host_free",
     "tdc_gpu_lz78_compress", "tdc_gpu_lzss_lcp_compress", "tdc_gpu_lzss_lcp_factorize",
     "tdc_gpu_sort_pairs_u64", "tdc_gpu_suffix_array", "tdc_gpu_textds", "tdc_gpu_lcpcomp_factorize", "tdc_gpu_flatten", "tdc_gpu_encode_huff",
-    "tdc_gpu_prim_scan", "tdc_gpu_prim_sort_pairs", "tdc_gpu_prim_bucketed_scatter", "tdc_gpu_prim_msd_partition", "tdc_gpu_prim_select",
+    "tdc_gpu_prim_scan", "tdc_gpu_prim_sort_pairs", "tdc_gpu_prim_bucketed_scatter", "tdc_gpu_prim_msd_partition", "tdc_gpu_prim_select", "tdc_gpu_prim_select_counts",
     "tdc_gpu_prim_mark_orbit",
     "tdc_gpu_lcpcomp_decompress",
     "tdc_gpu_lcpcomp_compress_comp",
@@ -129,6 +129,7 @@ def load():
     L.tdc_gpu_prim_bucketed_scatter.argtypes = [vp, vp, vp, sz, vp, sz, u32, i32, i32, i32]
     L.tdc_gpu_prim_msd_partition.argtypes = [vp, vp, vp, sz, i32, i32]
     L.tdc_gpu_prim_select.argtypes = [vp, vp, ctypes.c_uint8, sz, vp, vp, u32, ctypes.c_uint64, vp, vp, ctypes.POINTER(u32)]
+    L.tdc_gpu_prim_select_counts.argtypes = [vp, vp, ctypes.c_uint8, sz, vp, vp, u32, vp, ctypes.POINTER(u32)]
     L.tdc_gpu_prim_mark_orbit.argtypes = [vp, vp, sz, vp]
     L.tdc_gpu_suffix_array.argtypes = [vp, vp, sz, vp, vp]
     L.tdc_gpu_textds.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(u32)]

@@ -169,6 +169,7 @@ struct DevArrays {
     u32 *sa = nullptr, *isa = nullptr, *phi = nullptr, *plcp = nullptr;
     FactorSpace fs;
     u32 maxlcp = 0;
+    CandFused cand;                         // the factorizer's candidates, classified by the fused scatter (run_textds; filled: it did)
     EncodeEarly* early = nullptr;           // first half of the encoder, run inside the flatten stage (run_factorize)
     DevArrays() = default;
     DevArrays(const DevArrays&) = delete;
@@ -178,7 +179,10 @@ struct DevArrays {
 // SA -> ISA -> Phi -> PLCP  (TextDS::require, ds/TextDS.hpp:247-292)
 // want_phi = false (lcpcomp with comp=arrays): where the fused scatter runs, Phi is not materialised -- 8-byte instead of 12-byte records
 // through its two partition levels; the factorizer takes a factor's source from SA[ISA[p] - 1] (A.phi stays NULL)
-void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats* st, Events* ev, bool want_phi = true);
+// cw (optional): factorize_arrays(threshold) comes next -- where the fused scatter runs without Phi, it classifies the candidates on the
+// way (CandFused) and zero-fills the length array the factorizer will use: the byte array (flen8) or the dense one
+struct CandWant { u32 threshold; bool flen8; };
+void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats* st, Events* ev, bool want_phi = true, const CandWant* cw = nullptr);
 // enc_coder >= 0 (with d_text): the stream is encoded next with this coder of encode_stream -- the first half of the encoder may run
 // inside the flatten stage
 void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, tdc_gpu_stats* st, Events* ev, int strategy = 0,

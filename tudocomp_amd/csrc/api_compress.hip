@@ -25,7 +25,14 @@ void validate_device_text(Ctx& c, const u8* d_text, size_t n) {
     if (zeros != 1) throw ArgError{TDC_GPU_ERR_ARG, "text contains 0 bytes besides the sentinel (escape the input first)"};
 }
 
-void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats* st, Events* ev, bool want_phi) {
+// the metric's path (lcpcomp(comp=arrays, coder=huff) with the encoder's first half inside the flatten stage: nothing reads the dense
+// flen[] array behind build_owner): the factor lengths travel as bytes until then
+static bool early_is_planned(const Ctx& c, size_t n, u32 threshold, int flatten, int strategy, int enc_coder, const u8* d_text) {
+    return strategy == TDC_GPU_COMP_ARRAYS && flatten && enc_coder == 0 && d_text && c.enc_early && c.enc_rec && c.huff_ok &&
+           n >= (c.enc_early >= 2 ? (size_t)1 : ((size_t)1 << 20)) && threshold >= 2;
+}
+
+void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats* st, Events* ev, bool want_phi, const CandWant* cw) {
     A.sa = c.arena.get<u32>(n);
     A.isa = c.arena.get<u32>(n);
     A.phi = nullptr;                                          // (taken behind the suffix array, and only where a Phi array is built)
@@ -40,7 +47,22 @@ void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats*
     int e2;
     if (!(ex.mode == 1 && !want_phi && c.phi_lazy)) A.phi = c.arena.get<u32>(n);
     if (ex.mode == 1) {                                       // ISA + Phi + PLCP in one scatter of the final suffix array
-        build_isa_phi_plcp_fused(c, A.sa, ex.lcp8, n, A.isa, A.phi, A.plcp, d_max);
+        // comp=arrays without Phi: the scatter's image kernel classifies the factorizer's candidates while it holds the PLCP values
+        // (CandFused).  What it fills is taken here, below the scatter's scratch; run_factorize finds the length array in place.
+        CandFused* cf = nullptr;
+        if (cw && c.fused_cand && !A.phi && fused_scatter_has_image(c, n)) {
+            cf = &A.cand;
+            cf->threshold = cw->threshold;
+            cf->lcut = factorize_arrays_lcut0(c, n, cw->threshold);
+            cf->cls = c.arena.get<u8>(n);
+            if (cf->lcut) cf->res8 = c.arena.get<u8>(n);
+            if (cw->flen8) cf->flen8 = A.fs.flen8 = c.arena.get<u8>(n + 64); else cf->flen = A.fs.flen = c.arena.get<u32>(n);
+            if (c.sel_tile_counts) cf->tilecnt = c.arena.get<u32>(cdiv(n, SEL_TILE_CLASSES));
+            cf->acc = c.arena.get<u32>((size_t)CF_COPIES * CF_ACC);
+            cf->lvlhist = c.arena.get<u32>(128);
+            cf->entries = cf->lvlhist + 64;
+        }
+        build_isa_phi_plcp_fused(c, A.sa, ex.lcp8, n, A.isa, A.phi, A.plcp, d_max, cf);
         e2 = ev ? ev->tick() : 0;
     } else {
         build_phi(c, A.sa, n, A.phi);
@@ -58,18 +80,15 @@ void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats*
 
 void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, tdc_gpu_stats* st, Events* ev, int strategy,
                    int enc_coder, const u8* d_text) {
-    A.fs.flen = c.arena.get<u32>(n);
+    if (!A.fs.flen) A.fs.flen = c.arena.get<u32>(n);          // (either length array may be in place already: run_textds, CandFused)
     A.fs.owner = c.arena.get<u32>(n);
     A.fs.fsrc = c.arena.get<u32>(n);
     A.fs.fpos = c.arena.get<u32>(n);
     A.fs.flenl = threshold >= 2 ? A.fs.fpos + (n + 1) / 2 : nullptr;    // (a factor covers >= threshold positions: at most n / 2 of them, the list of
                                                                          //  their lengths fits the upper half of the position list)
     A.fs.cls = c.arena.get<u8>(n + 64);                  // class bytes for the encoder (filled by build_owner)
-    // the metric's path (lcpcomp(comp=arrays, coder=huff) with the encoder's first half inside the flatten stage: nothing reads the dense
-    // flen[] array behind build_owner): the factor lengths travel as bytes until then
-    const bool early_planned = strategy == TDC_GPU_COMP_ARRAYS && flatten && enc_coder == 0 && d_text && c.enc_early && c.enc_rec && c.huff_ok &&
-                               n >= (c.enc_early >= 2 ? (size_t)1 : ((size_t)1 << 20)) && threshold >= 2;
-    if (early_planned && c.flen_bytes) A.fs.flen8 = c.arena.get<u8>(n + 64);
+    const bool early_planned = early_is_planned(c, n, threshold, flatten, strategy, enc_coder, d_text);
+    if (early_planned && c.flen_bytes && !A.fs.flen8) A.fs.flen8 = c.arena.get<u8>(n + 64);
     A.fs.want_owner_rem = early_planned ? (u32)c.owner_rem : 0u;   // (behind build_owner only the flatten rounds read owner[] on this path: the encoder reads cls[] and the records)
     FactorizeStats fz;
     FlattenStats fl;
@@ -77,7 +96,7 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
     if (strategy == TDC_GPU_COMP_PLCPPEAKS) plcp_peaks_factorize(c, n, A.phi, A.plcp, threshold, A.fs, &fz.factors);
     else if (strategy == TDC_GPU_COMP_MAXLCP) factorize_max_lcp(c, n, A.isa, A.phi, A.plcp, A.maxlcp, threshold, A.fs, &fz);
     else if (strategy == TDC_GPU_COMP_HEAP) factorize_max_heap(c, n, A.sa, A.isa, A.plcp, A.maxlcp, threshold, A.fs, &fz);
-    else factorize_arrays(c, n, A.sa, A.isa, A.phi, A.plcp, A.maxlcp, threshold, A.fs, &fz);
+    else factorize_arrays(c, n, A.sa, A.isa, A.phi, A.plcp, A.maxlcp, threshold, A.fs, &fz, A.cand.filled ? &A.cand : nullptr);
     const int e1 = ev ? ev->tick() : 0;
     // The first half of the Huffman encoder (gaps, literal histogram, code table, bits per tile and their scan: 4-5 ms of streaming
     // kernels and three host round trips at 2e9 B) reads positions, lengths and class bytes but no source, and the flatten rounds are
@@ -215,8 +234,9 @@ size_t run_pipeline(Ctx& c, const u8* d_text, size_t n, u32 threshold, int flatt
     if (threshold == 0) throw ArgError{TDC_GPU_ERR_ARG, "threshold must be >= 1"};
     validate_device_text(c, d_text, n);
     DevArrays A;
-    run_textds(c, d_text, n, A, st, &ev, strategy != TDC_GPU_COMP_ARRAYS);
     const int enc_coder = lcpcomp_enc_coder(coder);
+    const CandWant cw{threshold, early_is_planned(c, n, threshold, flatten, strategy, enc_coder, d_text) && c.flen_bytes};
+    run_textds(c, d_text, n, A, st, &ev, strategy != TDC_GPU_COMP_ARRAYS, strategy == TDC_GPU_COMP_ARRAYS ? &cw : nullptr);
     run_factorize(c, n, A, threshold, flatten, st, &ev, strategy, enc_coder, d_text);
     EncodeStats es;
     if (!*d_out_io) { out_cap = align_up(encode_bound_coder(n, enc_coder) + 16, 8); *d_out_io = c.arena.get<u8>(out_cap); }

@@ -133,22 +133,31 @@ const OptionDef OPTIONS[] = {
     { "arena_log",        [](Ctx& c, long v) { c.arena_log = v != 0; } },
 };
 constexpr size_t NOPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
+// Switches of passes folded into a neighbouring kernel: set like the others, but not enumerated by tdc_gpu_option_name() -- the enumerated
+// set is the one tests/test_gpu_parity.py::test_every_option_value_is_bit_exact walks; these are walked by tests/test_gpu_fused_candidates.py.
+const OptionDef FOLD_OPTIONS[] = {
+    { "fused_cand",       [](Ctx& c, long v) { c.fused_cand = v != 0; } },
+    { "sel_tile_counts",  [](Ctx& c, long v) { c.sel_tile_counts = v != 0; } },
+};
+constexpr size_t NFOLD = sizeof(FOLD_OPTIONS) / sizeof(FOLD_OPTIONS[0]);
 const OptionDef* find_option(const char* name) {
     if (!name) return nullptr;
     if (!strncasecmp(name, "TDC_GPU_", 8)) name += 8;
     for (size_t i = 0; i < NOPTIONS; ++i) if (!strcasecmp(name, OPTIONS[i].name)) return &OPTIONS[i];
+    for (size_t i = 0; i < NFOLD; ++i) if (!strcasecmp(name, FOLD_OPTIONS[i].name)) return &FOLD_OPTIONS[i];
     return nullptr;
 }
 // the ONE place that reads TDC_GPU_* variables (besides TDC_GPU_LIB of the Python loader, which picks the library file)
 void apply_env_options(tdc_gpu_ctx* ctx) {
     const char* on = getenv("TDC_GPU_DEBUG_KNOBS");
     if (!on || atoi(on) == 0) return;
-    for (size_t i = 0; i < NOPTIONS; ++i) {
+    for (size_t i = 0; i < NOPTIONS + NFOLD; ++i) {
+        const OptionDef& o = i < NOPTIONS ? OPTIONS[i] : FOLD_OPTIONS[i - NOPTIONS];
         char var[64] = "TDC_GPU_";
         size_t k = 8;
-        for (const char* q = OPTIONS[i].name; *q && k + 1 < sizeof(var); ++q) var[k++] = (char)toupper((unsigned char)*q);
+        for (const char* q = o.name; *q && k + 1 < sizeof(var); ++q) var[k++] = (char)toupper((unsigned char)*q);
         var[k] = 0;
-        if (const char* m = getenv(var)) OPTIONS[i].set(ctx->c, atol(m));
+        if (const char* m = getenv(var)) o.set(ctx->c, atol(m));
     }
 }
 }  // namespace

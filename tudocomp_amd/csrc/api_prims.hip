@@ -176,6 +176,32 @@ int tdc_gpu_prim_select(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t want, size
     });
 }
 
+int tdc_gpu_prim_select_counts(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t want, size_t m, const uint32_t* srcA, const uint32_t* tile_counts,
+                               uint32_t fillA, uint32_t* outA, uint32_t* count) {
+    return guarded(ctx, [&] {
+        if (m && (!cls || !outA || !tile_counts)) bad("cls/outA/tile_counts is NULL");
+        if (!count) bad("count is NULL");
+        check_count(m);
+        const size_t tiles = (m + SEL_TILE_CLASSES - 1) / SEL_TILE_CLASSES;
+        for (size_t t = 0; t < tiles; ++t) {                    // the caller's promise: the counts are those of cls[]
+            const size_t e = std::min(m, (t + 1) * SEL_TILE_CLASSES);
+            if ((size_t)std::count(cls + t * SEL_TILE_CLASSES, cls + e, want) != tile_counts[t]) bad("tile_counts[t] is not the count of tile t");
+        }
+        Ctx& c = ctx->c;
+        reserve_arena(c, 32 * m + ((size_t)64 << 20));
+        const u8* d_cls = upload(c, cls, m);
+        const u32* d_a = srcA ? upload(c, srcA, m) : nullptr;
+        const u32* d_tc = upload(c, tile_counts, tiles);
+        u32* d_oa = c.arena.get<u32>(m + 4);
+        u32* d_count = c.arena.get<u32>(1);
+        fill_u32(c, d_oa, m, fillA);
+        select_by_class(c, d_cls, want, m, d_a, d_oa, nullptr, nullptr, d_count, d_tc);
+        download(c, outA, d_oa, m);
+        download(c, count, d_count, 1);
+        HIP_TRY(hipStreamSynchronize(c.stream));
+    });
+}
+
 int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, uint8_t* mark) {
     return guarded(ctx, [&] {
         if (n && (!next || !mark)) bad("next/mark is NULL");

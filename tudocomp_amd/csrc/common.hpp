@@ -152,6 +152,8 @@ struct Ctx {
     int enc_rec = 1;               // with enc_early: the pack reads lengths and flattened sources from the records of the flatten stage (env TDC_GPU_ENC_REC=0: from flen[] / fsrc[])
     int owner_rem = 8;             // metric's path: owner words carry how far their factor still reaches, in at most this many bits (FactorSpace::owner_rem_bits; 0: plain ranks)
     int enc_early = 1;             // first half of the Huffman encoder next to the first flatten round (texts of 1 MiB and more; env TDC_GPU_ENC_EARLY=0: after the flatten stage, 2: for every text)
+    int fused_cand = 1;            // lcpcomp(comp=arrays) behind the fused scatter without Phi: its image kernel classifies the candidates while it holds the PLCP window (CandFused; option fused_cand=0: cand_class_kernel reads PLCP back)
+    int sel_tile_counts = 1;       // ... and counts the class-1 bytes per selection tile: the first candidate selection skips its count pass and every empty tile (option sel_tile_counts=0: select_by_class counts itself)
     int fs_pair = 1;               // fused scatter: two rows per workgroup (tiles of 8192 records; env TDC_GPU_FS_PAIR=0: one)
     int small_big = 1;             // factorize: one-workgroup levels with up to 4096 survivors run on a 512-thread instance of the kernel (env TDC_GPU_SMALL_BIG=0: multi-launch path above 2048)
     int small_pipeline = 1;        // factorize: the kernel of the next one-workgroup level is queued while the current one runs (env TDC_GPU_SMALL_PIPELINE=0 disables)

@@ -144,6 +144,15 @@ __global__ void gather_kernel(const u32* __restrict__ idx, size_t m, const u32* 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) dst[i] = src[idx[i]];
 }
+// the sources of the listed positions without a Phi array: fsrc[p] = SA[ISA[p] - 1] (what cand_class_kernel does for its class-1 positions)
+__global__ void cand_source_kernel(const u32* __restrict__ list, size_t m, const u32* __restrict__ sa, const u32* __restrict__ isa, size_t n,
+                                   u32* __restrict__ fsrc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const u32 p = list[i];
+    const u32 r = isa[p];
+    fsrc[p] = r ? sa[r - 1] : sa[n - 1];
+}
 __global__ void seg_bounds_kernel(const u32* __restrict__ keys, size_t m, u32* __restrict__ segstart, u32* __restrict__ segend) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
@@ -1055,8 +1064,15 @@ __global__ __launch_bounds__(256) void apply_kernel(const u32* __restrict__ live
     if (threadIdx.x == 0 && cnt) atomicAdd(&sc->selected, cnt);
 }
 
+// the cut of the window pass as far as it is known without maxlcp (CandFused::lcut)
+u32 factorize_arrays_lcut0(const Ctx& c, size_t n, u32 threshold) {
+    if (c.window_lcut <= 0 || n < window_levels_min_text()) return 0;
+    const u32 lcut = std::min<u32>((u32)c.window_lcut, window_levels_max_lcut());
+    return lcut < threshold ? 0u : lcut;
+}
+
 void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi, u32* plcp, u32 maxlcp, u32 threshold,
-                      FactorSpace& fs, FactorizeStats* st) {
+                      FactorSpace& fs, FactorizeStats* st, const CandFused* cf) {
     // (the candidate order of the reference -- ascending SA index -- is carried by prio[] = ISA.)  phi == nullptr: there is no Phi array;
     // the source of a factor at p is SA[ISA[p] - 1].  The candidates of the global levels get theirs into fsrc[] up front
     // (cand_class_kernel), so the global kernels read "Phi" from fsrc[] itself (fsrc[p] = fsrc[p] at a selection); the window kernel
@@ -1074,22 +1090,24 @@ void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi,
     u32* prio = isa;
 
     // ---- candidates: positions with PLCP >= threshold, in position order, stably sorted by PLCP value -----------
-    u8* cls = c.arena.get<u8>(n);
+    // (cf: the image kernel of the fused scatter has classified the candidates -- against the cut known before maxlcp was, which is the
+    //  same classification: no PLCP value lies between maxlcp and that cut)
+    const bool pre = cf && cf->filled;
+    if (pre && (phi || cf->threshold != threshold || cf->lcut != factorize_arrays_lcut0(c, n, threshold) || (fs.flen8 ? cf->flen8 != fs.flen8 : cf->flen != fs.flen)))
+        throw HipError{hipErrorUnknown, "factorize: the pre-classified candidates belong to another call", (int)__LINE__};
+    u8* cls = pre ? cf->cls : c.arena.get<u8>(n);
     // the low levels run window-local (factorize_tiles.hip) when the text is long enough; res8 = residence level per position
-    u32 lcut = 0;
-    if (c.window_lcut > 0 && n >= window_levels_min_text()) {
-        lcut = std::min<u32>((u32)c.window_lcut, window_levels_max_lcut());
-        if (lcut > maxlcp) lcut = maxlcp;
-        if (lcut < threshold) lcut = 0;
-    }
-    u8* res8 = lcut ? c.arena.get<u8>(n) : nullptr;
+    u32 lcut = factorize_arrays_lcut0(c, n, threshold);
+    if (lcut > maxlcp) lcut = maxlcp;
+    if (lcut < threshold) lcut = 0;
+    u8* res8 = lcut ? (pre ? cf->res8 : c.arena.get<u8>(n)) : nullptr;
     u32* ckeys[2] = { c.arena.get<u32>(n), c.arena.get<u32>(n) };
     u32* cvals[2] = { c.arena.get<u32>(n), c.arena.get<u32>(n) };
-    u32* d_cnt = c.arena.get<u32>(4);
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(u32), s));
-    u32* d_lvlhist = c.arena.get<u32>(64);
-    HIP_TRY(hipMemsetAsync(d_lvlhist, 0, 64 * sizeof(u32), s));
-    {
+    u32* d_cnt = c.arena.get<u32>(4);              // (every later user of its words clears them itself)
+    u32* d_lvlhist = pre ? cf->lvlhist : c.arena.get<u32>(64);
+    if (!pre) {
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(u32), s));
+        HIP_TRY(hipMemsetAsync(d_lvlhist, 0, 64 * sizeof(u32), s));
         Ctx::ProfScope prof(c, K_CAND, (u64)n * (lcut ? 10 : 9) - (fs.flen8 ? (u64)n * 3 : 0));
         cand_class_kernel<<<(gn < 8192u ? gn : 8192u), 256, 0, s>>>(plcp, n, threshold, lcut, cls, fs.flen, res8, d_cnt + 1, lcut ? d_lvlhist : nullptr,
                                                                     phi ? nullptr : sa, isa, fs.fsrc, fs.flen8);
@@ -1106,9 +1124,17 @@ void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi,
     int x = 0;
     size_t cand_count = 0;
     // candidate lists: the class-1 positions in position order, stably sorted by their level (= the working value: the PLCP value at the start)
+    bool first_lists = true;
     auto build_lists = [&](u32 max_level) {
-        select_by_class(c, cls, 1, n, nullptr, cvals[0], nullptr, nullptr, d_cnt);
+        const bool from_image = pre && first_lists;           // cls[] is the image kernel's: so are its counts per selection tile
+        first_lists = false;
+        select_by_class(c, cls, 1, n, nullptr, cvals[0], nullptr, nullptr, d_cnt, from_image && c.sel_tile_counts ? cf->tilecnt : nullptr);
         cand_count = c.read(d_cnt);
+        if (from_image && !phi && cand_count) {               // before any push can overwrite a priority (cand_class_kernel does it in its pass)
+            Ctx::ProfScope prof(c, K_CAND, (u64)cand_count * 16);
+            cand_source_kernel<<<cdiv(cand_count, 256), 256, 0, s>>>(cvals[0], cand_count, sa, isa, n, fs.fsrc);
+            LAUNCH_CHECK();
+        }
         if (cand_count) {
             Ctx::ProfScope prof(c, K_CAND, (u64)cand_count * 12);
             gather_kernel<<<cdiv(cand_count, 256), 256, 0, s>>>(cvals[0], cand_count, plcp, ckeys[0]);
@@ -1125,7 +1151,7 @@ void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi,
         c.read_n(d_segend, h_segend.data(), nlev);
     };
     build_lists(maxlcp);
-    st->entries = c.read(d_cnt + 1);
+    st->entries = c.read(pre ? cf->entries : d_cnt + 1);
     const u32* cand = cvals[x];
 
     // ---- per-level state ------------------------------------------------------------------------------------

@@ -194,11 +194,20 @@ __global__ __launch_bounds__(256 * PAIR) __attribute__((amdgpu_waves_per_eu(TDC_
 // n - 1 = sa[0] has no record).  One workgroup per window: each array is scattered into an LDS image of the window and leaves as whole
 // lines.
 constexpr int FS_IMG_T = 1024;       // threads of the image kernel: a window's records are loaded ONCE, eight per thread
-template <bool WP>
+// CF (CandFused, stages.hpp): while the window's PLCP values are in LDS, what cand_class_kernel (factorize.hip) would read them back for --
+// class, residence and (zero) length bytes four positions per thread as one word each, the candidate count and the sampled level
+// histogram into one of CF_COPIES accumulators (a wave's 64 counters are two lines: a few atomics per workgroup), and the class-1 bytes
+// per selection tile (a wave's 256 positions lie in one tile of 2 048; almost every wave has none).
+struct FSCand { u32 threshold, lcut; u8* cls; u8* res8; u8* flen8; u32* flen; u32* tilecnt; u32* acc; };
+template <bool WP, bool CF>
 __global__ __launch_bounds__(FS_IMG_T) void fs_image_kernel(const u32* __restrict__ idx, const void* __restrict__ rp_v, int lsh, size_t m, u32 W,
-                                                             u32* __restrict__ isa, u32* __restrict__ phi, u32* __restrict__ plcp, u32* __restrict__ d_max) {
-    __shared__ u32 img[FS_WMAX];
+                                                             u32* __restrict__ isa, u32* __restrict__ phi, u32* __restrict__ plcp, u32* __restrict__ d_max,
+                                                             FSCand cf) {
+    __shared__ __align__(16) u32 img[FS_WMAX];
     __shared__ u32 smx[FS_IMG_T / 64];
+    __shared__ u32 scf[CF ? FS_IMG_T / 64 : 1];
+    __shared__ u32 shist[CF ? 64 : 1];
+    if (CF && threadIdx.x < 64) shist[threadIdx.x] = 0;         // (barriers follow before anyone adds to it)
     constexpr int R = FS_WMAX / FS_IMG_T;
     const size_t base = (size_t)blockIdx.x * W;
     const size_t end = (base + W < m) ? base + W : m;
@@ -233,6 +242,46 @@ __global__ __launch_bounds__(FS_IMG_T) void fs_image_kernel(const u32* __restric
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < R; ++r) { const size_t q = base + (size_t)r * FS_IMG_T + threadIdx.x; if (q < end) plcp[q] = img[q - base]; }
+    if constexpr (CF) {
+        u32 ncand = 0;
+#pragma unroll
+        for (int r = 0; r < R / 4; ++r) {
+            const u32 o = ((u32)r * FS_IMG_T + threadIdx.x) * 4;                // window offset of the thread's four positions
+            const size_t q = base + o;                                          // (a multiple of 4: W is a power of two >= 16)
+            u32 cw = 0, rw = 0, nv = 0;
+            if (q < end) {
+                nv = (end - q < 4) ? (u32)(end - q) : 4u;
+                const uint4 x = *(const uint4*)&img[o];
+                const u32 v[4] = { x.x, x.y, x.z, x.w };
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if ((u32)j >= nv) break;                                    // (behind the last record of the last window the image holds nothing)
+                    const u32 is_cand = (v[j] >= cf.threshold) ? 1u : 0u;
+                    cw |= ((is_cand && v[j] > cf.lcut) ? 1u : 0u) << (8 * j);
+                    rw |= (is_cand ? (v[j] > 255u ? 255u : v[j]) : 0u) << (8 * j);
+                    ncand += is_cand;
+                    if (j == 0 && cf.lcut && is_cand && v[j] < 64u && (q & 15) == 0) atomicAdd(&shist[v[j]], 1u);      // (every 16th position)
+                }
+                if (nv == 4) {
+                    *(u32*)(cf.cls + q) = cw;
+                    if (cf.res8) *(u32*)(cf.res8 + q) = rw;
+                    if (cf.flen8) *(u32*)(cf.flen8 + q) = 0u; else *(uint4*)(cf.flen + q) = make_uint4(0, 0, 0, 0);
+                } else {
+                    for (u32 j = 0; j < nv; ++j) {
+                        cf.cls[q + j] = (u8)(cw >> (8 * j));
+                        if (cf.res8) cf.res8[q + j] = (u8)(rw >> (8 * j));
+                        if (cf.flen8) cf.flen8[q + j] = 0; else cf.flen[q + j] = 0;
+                    }
+                }
+            }
+            if (cf.tilecnt) {                                                   // (all lanes: a wave's valid positions lie in the tile of its first lane)
+                const u32 wsum = wave_reduce_sum((u32)__popc(cw));
+                if (lane_id() == 0 && wsum) atomicAdd(&cf.tilecnt[q / SEL_TILE_CLASSES], wsum);
+            }
+        }
+        ncand = wave_reduce_sum(ncand);
+        if (lane_id() == 0) scf[wave_id()] = ncand;
+    }
     mx = wave_reduce_max(mx);
     if (lane_id() == 0) smx[wave_id()] = mx;
     __syncthreads();
@@ -241,11 +290,28 @@ __global__ __launch_bounds__(FS_IMG_T) void fs_image_kernel(const u32* __restric
         v = wave_reduce_max(v);
         if (lane_id() == 0 && v) atomicMax(d_max, v);
     }
+    if constexpr (CF) {                                         // (behind the barrier above: scf and shist are complete)
+        u32* acc = cf.acc + (size_t)(blockIdx.x % CF_COPIES) * CF_ACC;
+        if (threadIdx.x < 64) { if (shist[threadIdx.x]) atomicAdd(&acc[threadIdx.x], shist[threadIdx.x]); }
+        else if (threadIdx.x == 64) { u32 t = 0; for (int i = 0; i < FS_IMG_T / 64; ++i) t += scf[i]; if (t) atomicAdd(&acc[64], t); }
+    }
+}
+// the accumulators of the image kernel -> 64 histogram words and the candidate count behind them
+__global__ void fs_cand_fold_kernel(const u32* __restrict__ acc, u32* __restrict__ out) {
+    if (threadIdx.x > 64) return;
+    u32 t = 0;
+    for (u32 k = 0; k < CF_COPIES; ++k) t += acc[(size_t)k * CF_ACC + threadIdx.x];
+    out[threadIdx.x] = t;
 }
 
-__global__ void fs_first_kernel(const u32* __restrict__ sa, size_t n, u32* __restrict__ isa, u32* __restrict__ phi, u32* __restrict__ plcp) {
+__global__ void fs_first_kernel(const u32* __restrict__ sa, size_t n, u32* __restrict__ isa, u32* __restrict__ phi, u32* __restrict__ plcp, FSCand cf) {
     const u32 p = sa[0];
     isa[p] = 0; if (phi) phi[p] = sa[n - 1]; plcp[p] = 0;
+    if (cf.cls) {                                               // (PLCP 0: no candidate)
+        cf.cls[p] = 0;
+        if (cf.res8) cf.res8[p] = 0;
+        if (cf.flen8) cf.flen8[p] = 0; else cf.flen[p] = 0;
+    }
 }
 __global__ void fs_direct_kernel(const u32* __restrict__ sa, const u8* __restrict__ lcp8, size_t n, u32* __restrict__ isa, u32* __restrict__ phi,
                                  u32* __restrict__ plcp, u32* __restrict__ d_max) {
@@ -262,12 +328,15 @@ __global__ void fs_direct_kernel(const u32* __restrict__ sa, const u8* __restric
     if (lane_id() == 0 && l) atomicMax(d_max, l);
 }
 
-void build_isa_phi_plcp_fused(Ctx& c, const u32* sa, const u8* lcp8, size_t n, u32* isa, u32* phi, u32* plcp, u32* d_maxlcp) {
+bool fused_scatter_has_image(const Ctx& c, size_t n) { return n >= ((size_t)1 << 20) && c.bucket_scatter; }
+
+void build_isa_phi_plcp_fused(Ctx& c, const u32* sa, const u8* lcp8, size_t n, u32* isa, u32* phi, u32* plcp, u32* d_maxlcp, CandFused* cf) {
     hipStream_t s = c.stream;
+    if (cf) cf->filled = false;
     HIP_TRY(hipMemsetAsync(d_maxlcp, 0, sizeof(u32), s));
     if (!n) return;
     const int bits = (int)bits_for(n - 1);
-    if (n < ((size_t)1 << 20) || !c.bucket_scatter) {
+    if (!fused_scatter_has_image(c, n)) {
         Ctx::ProfScope prof(c, K_PHI, (u64)n * 17);
         fs_direct_kernel<<<cdiv(n, 256), 256, 0, s>>>(sa, lcp8, n, isa, phi, plcp, d_maxlcp);
         LAUNCH_CHECK();
@@ -332,12 +401,33 @@ void build_isa_phi_plcp_fused(Ctx& c, const u32* sa, const u8* lcp8, size_t n, u
     {
         const u32 W = 1u << (bits - 2 * db);
         if (W > FS_WMAX) throw HipError{hipErrorUnknown, "fused scatter: window larger than the LDS image", (int)__LINE__};
-        Ctx::ProfScope prof(c, K_FS_IMAGE, (u64)m * (wp ? 24 : 16));          // 12 bytes in, 12 out (8 + 8 without Phi)
-        if (wp) fs_image_kernel<true><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp);
-        else fs_image_kernel<false><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp);
+        if (W < 16) throw HipError{hipErrorUnknown, "fused scatter: window smaller than a thread's group of positions", (int)__LINE__};
+        FSCand fc{};
+        if (cf) {
+            if (!cf->cls || !cf->acc || !cf->lvlhist || (!cf->flen8 && !cf->flen) || (cf->lcut && !cf->res8))
+                throw HipError{hipErrorUnknown, "fused scatter: candidate arrays missing", (int)__LINE__};
+            fc.threshold = cf->threshold; fc.lcut = cf->lcut;
+            fc.cls = cf->cls; fc.res8 = cf->lcut ? cf->res8 : nullptr; fc.flen8 = cf->flen8; fc.flen = cf->flen; fc.tilecnt = cf->tilecnt; fc.acc = cf->acc;
+            HIP_TRY(hipMemsetAsync(cf->acc, 0, (size_t)CF_COPIES * CF_ACC * sizeof(u32), s));
+            if (cf->tilecnt) HIP_TRY(hipMemsetAsync(cf->tilecnt, 0, (size_t)cdiv(n, SEL_TILE_CLASSES) * sizeof(u32), s));
+        }
+        // 12 bytes in, 12 out (8 + 8 without Phi); with the candidates: class and length byte (+ the residence byte), or the 4-byte length
+        Ctx::ProfScope prof(c, K_FS_IMAGE, (u64)m * (wp ? 24 : 16) + (cf ? (u64)m * ((cf->lcut ? 2 : 1) + (cf->flen8 ? 1 : 4)) : 0));
+        if (cf) {
+            if (wp) fs_image_kernel<true, true><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp, fc);
+            else fs_image_kernel<false, true><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp, fc);
+        } else {
+            if (wp) fs_image_kernel<true, false><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp, fc);
+            else fs_image_kernel<false, false><<<cdiv(m, W), FS_IMG_T, 0, s>>>(idx[1], rp[1], bits - db, m, W, isa, phi, plcp, d_maxlcp, fc);
+        }
         LAUNCH_CHECK();
-        fs_first_kernel<<<1, 1, 0, s>>>(sa, n, isa, phi, plcp);
+        fs_first_kernel<<<1, 1, 0, s>>>(sa, n, isa, phi, plcp, fc);
         LAUNCH_CHECK();
+        if (cf) {
+            fs_cand_fold_kernel<<<1, 128, 0, s>>>(cf->acc, cf->lvlhist);       // (cf->entries is the word behind the histogram)
+            LAUNCH_CHECK();
+            cf->filled = true;
+        }
     }
     c.arena.release(mark);
 }

@@ -165,6 +165,7 @@ void inclusive_max_u32(Ctx& c, const u32* in, u32* out, size_t n) { scan_impl<u3
 // ------------------------------------------------------------------------------------------------
 constexpr int SEL_PER_THREAD = 8;
 constexpr int SEL_TILE = 256 * SEL_PER_THREAD;
+static_assert((size_t)SEL_TILE == SEL_TILE_CLASSES, "prim.hpp states the tile of select_by_class");
 
 __device__ __forceinline__ u32 sel_load_mask(const u8* __restrict__ cls, u8 want, size_t k0, size_t m) {
     u32 mask = 0;
@@ -191,8 +192,9 @@ __global__ __launch_bounds__(256) void sel_count_kernel(const u8* __restrict__ c
 __global__ __launch_bounds__(256) void sel_scatter_kernel(const u8* __restrict__ cls, u8 want, size_t m,
                                                            const u32* __restrict__ tileoff, const u32* __restrict__ srcA,
                                                            u32* __restrict__ outA, const u64* __restrict__ srcB,
-                                                           u64* __restrict__ outB) {
+                                                           u64* __restrict__ outB, const u32* __restrict__ tilecounts) {
     __shared__ u32 sm[5];
+    if (tilecounts && tilecounts[blockIdx.x] == 0) return;       // (counts handed in: an empty tile loads nothing)
     const size_t k0 = (size_t)blockIdx.x * SEL_TILE + (size_t)threadIdx.x * SEL_PER_THREAD;
     const u32 mask = (k0 < m) ? sel_load_mask(cls, want, k0, m) : 0u;
     u32 total;
@@ -209,15 +211,17 @@ __global__ __launch_bounds__(256) void sel_scatter_kernel(const u8* __restrict__
 }
 
 void select_by_class(Ctx& c, const u8* cls, u8 want, size_t m, const u32* srcA, u32* outA, const u64* srcB, u64* outB,
-                     u32* d_count) {
+                     u32* d_count, const u32* tile_counts) {
     if (m == 0) { HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(u32), c.stream)); return; }
     const size_t mark = c.arena.mark();
     const unsigned tiles = cdiv(m, SEL_TILE);
     u32* tilecnt = c.arena.get<u32>(tiles);
-    sel_count_kernel<<<tiles, 256, 0, c.stream>>>(cls, want, m, tilecnt);
-    LAUNCH_CHECK();
-    exclusive_sum_u32(c, tilecnt, tilecnt, tiles, d_count);
-    sel_scatter_kernel<<<tiles, 256, 0, c.stream>>>(cls, want, m, tilecnt, srcA, outA, srcB, outB);
+    if (!tile_counts) {
+        sel_count_kernel<<<tiles, 256, 0, c.stream>>>(cls, want, m, tilecnt);
+        LAUNCH_CHECK();
+    }
+    exclusive_sum_u32(c, tile_counts ? tile_counts : tilecnt, tilecnt, tiles, d_count);
+    sel_scatter_kernel<<<tiles, 256, 0, c.stream>>>(cls, want, m, tilecnt, srcA, outA, srcB, outB, tile_counts);
     LAUNCH_CHECK();
     c.arena.release(mark);
 }

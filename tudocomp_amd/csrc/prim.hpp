@@ -116,8 +116,11 @@ void bucketed_scatter_u32(Ctx& c, const u32* idx, const u32* val, size_t m, u32*
 
 // Order-preserving selection: for the k (ascending) with cls[k] == want, outA[j] = srcA[k] (or k itself if srcA ==
 // nullptr) and outB[j] = srcB[k] if srcB != nullptr; *d_count (device) receives the number of selected elements.
+// tile_counts (optional, device): the number of cls[k] == want per tile of SEL_TILE_CLASSES consecutive k, as a kernel that wrote cls[]
+// counted them -- the count pass is skipped then and a tile whose count is 0 is not loaded at all.
+constexpr size_t SEL_TILE_CLASSES = 2048;
 void select_by_class(Ctx& c, const u8* cls, u8 want, size_t m, const u32* srcA, u32* outA, const u64* srcB, u64* outB,
-                     u32* d_count);
+                     u32* d_count, const u32* tile_counts = nullptr);
 
 // Orbit of element 0 under a strictly increasing successor function: next[i] > i, next[i] == n ends the chain.
 // mark[i] = 1 for every element on the chain 0, next[0], next[next[0]], ... ; 0 elsewhere.

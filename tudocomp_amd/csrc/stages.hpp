@@ -27,7 +27,26 @@ void build_suffix_array(Ctx& c, const u8* text, size_t n, u32* sa, u32* isa, SAS
 // a3 + a4 + a5 in one pass over a final suffix array whose neighbour LCPs are known (lcp8[i] = lcp(T[sa[i-1]..], T[sa[i]..]), i >= 1):
 // isa[sa[i]] = i, phi[sa[i]] = sa[i-1] (phi[sa[0]] = sa[n-1]), plcp[sa[i]] = lcp8[i] (plcp[sa[0]] = 0); d_maxlcp receives the maximum.
 // ds/ISAFromSA.hpp:30-43, ds/PhiFromSA.hpp:35-45, ds/PLCPFromPhi.hpp:27-53 (same arrays, computed from the sort instead of the text)
-void build_isa_phi_plcp_fused(Ctx& c, const u32* sa, const u8* lcp8, size_t n, u32* isa, u32* phi, u32* plcp, u32* d_maxlcp);
+// What cand_class_kernel (factorize.hip) derives from the PLCP values, produced by the image kernel of the fused scatter while it holds a
+// window's values in LDS (option fused_cand): the caller allocates the arrays BEFORE the scatter takes its scratch and sets threshold and
+// lcut (the window pass's cut as known before maxlcp is: min(window_lcut, window_levels_max_lcut()), 0 where the pass cannot run); the
+// scatter sets `filled` where its image kernel ran (not on the direct path of small texts), and factorize_arrays then skips its own pass.
+struct CandFused {
+    u32 threshold = 0, lcut = 0;
+    u8* cls = nullptr;          // n bytes: 1 = candidate of a level above lcut
+    u8* res8 = nullptr;         // n bytes, lcut != 0 only: min(PLCP, 255) of a candidate, 0 elsewhere
+    u8* flen8 = nullptr;        // FactorSpace::flen8 (zero-filled), or
+    u32* flen = nullptr;        // FactorSpace::flen where there is no byte array
+    u32* tilecnt = nullptr;     // nullable (option sel_tile_counts): class-1 bytes per SEL_TILE positions, for select_by_class
+    u32* acc = nullptr;         // CF_COPIES x CF_ACC words the workgroups add to (sampled level histogram [0, 64), candidate count [64])
+    u32* lvlhist = nullptr;     // 64 words: the sampled level histogram (lcut != 0 only meaningful), folded from acc
+    u32* entries = nullptr;     // 1 word behind it: the number of candidates
+    bool filled = false;
+};
+constexpr u32 CF_COPIES = 64, CF_ACC = 80;
+void build_isa_phi_plcp_fused(Ctx& c, const u32* sa, const u8* lcp8, size_t n, u32* isa, u32* phi, u32* plcp, u32* d_maxlcp, CandFused* cf = nullptr);
+bool fused_scatter_has_image(const Ctx& c, size_t n);      // false: a text this short takes the direct kernel (cf is left unfilled)
+u32 factorize_arrays_lcut0(const Ctx& c, size_t n, u32 threshold);     // CandFused::lcut for factorize_arrays(threshold) on this context
 // byte histogram of a text into the context's cache (c.hist_cache / hist_ptr / hist_n): add() per part, finish() once
 void text_histogram_add(Ctx& c, const u8* part, size_t len, u32* d_hist);
 void text_histogram_finish(Ctx& c, const u8* text, size_t n, const u32* d_hist);
@@ -99,8 +118,9 @@ struct FactorizeStats { u64 factors = 0; u32 maxlcp = 0; u32 levels = 0; u32 rou
 // a8: compressors/lcpcomp/compress/ArraysComp.hpp:36-117 in position space.
 // Inputs: isa, phi, plcp.  isa and plcp are consumed: they become the working priority / LCP arrays.
 // Outputs: fs.flen / fs.owner filled, fs.fsrc[p] = phi[p] at factor starts.
+// cf (optional, cf->filled): the candidate classes, residence bytes, zero-filled lengths and counters are in place already (CandFused)
 void factorize_arrays(Ctx& c, size_t n, const u32* sa, u32* isa, const u32* phi, u32* plcp, u32 maxlcp,
-                      u32 threshold, FactorSpace& fs, FactorizeStats* st);
+                      u32 threshold, FactorSpace& fs, FactorizeStats* st, const CandFused* cf = nullptr);
 
 // owner[] from the factor starts (flen[p] != 0 exactly at factor starts): owner[q] = start of the factor covering q, else NONE32
 void build_owner(Ctx& c, size_t n, FactorSpace& fs);
