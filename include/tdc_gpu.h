@@ -39,7 +39,7 @@ typedef enum {
 
 /* coder ids (option `coder`, etc/registry_config.py:28-31,138-142) */
 enum { TDC_GPU_CODER_HUFF = 0, TDC_GPU_CODER_GAMMA = 1, TDC_GPU_CODER_ARITH = 2, TDC_GPU_CODER_ASCII = 3, TDC_GPU_CODER_SLE = 4,
-       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw only */ };
+       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw, lzss_lcp */, TDC_GPU_CODER_DELTA = 6 /* EliasDeltaCoder: lzss_lcp */ };
 /* coder=sle(kmer=K) (coders/SLECoder.hpp:36-40; the reference's default is 3): the option travels in bits 8.. of `coder` */
 #define TDC_GPU_CODER_SLE_K(K) (TDC_GPU_CODER_SLE | ((K) << 8))
 /* factorization strategy of lcpcomp (option `comp`, LCPCompressor.hpp:87): ArraysComp or PLCPPeaksStrategy */
@@ -207,11 +207,29 @@ int tdc_gpu_device_count(void);
 int tdc_gpu_lz78_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, int coder, uint8_t** out, size_t* out_len,
                           tdc_gpu_stats* stats);
 
-/* ---- lzss_lcp (SURVEY.md 8a row a18 / 8f "next" #1): replaces LZSSLCPCompressor<HuffmanCoder>::compress
+/* ---- lzss_lcp (SURVEY.md 8a row a18 / 8f "next" #1): replaces LZSSLCPCompressor<coder>::compress
  * (compressors/LZSSLCPCompressor.hpp:41-123): greedy LZ77 parse via previous / next smaller values of the suffix array.
- * Same text contract as lcpcomp (escaped, 0-terminated); option threshold (default 3, :30). */
+ * Same text contract as lcpcomp (escaped, 0-terminated); option threshold (default 3, :30).
+ * coder: the reference's non-consuming coders (etc/registry_config.py:33-34) -- TDC_GPU_CODER_HUFF, TDC_GPU_CODER_BIT (BitCoder: every
+ * field v - min in bits_for(max - min) bits, a literal in 8), TDC_GPU_CODER_GAMMA / TDC_GPU_CODER_DELTA (every field and every literal
+ * as a self-delimiting code, the ranges ignored) or TDC_GPU_CODER_ASCII; anything else: TDC_GPU_ERR_UNSUPPORTED.  DESIGN.md 5.5. */
 int tdc_gpu_lzss_lcp_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold, int coder,
                               uint8_t** out, size_t* out_len, tdc_gpu_stats* stats);
+/* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small. */
+int tdc_gpu_lzss_lcp_compress_into(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold, int coder,
+                                   uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
+/* worst-case stream length for a text of n bytes (what an _into buffer needs at most, and what the call sizes its device buffer by);
+ * 0 for a coder lzss_lcp does not take */
+size_t tdc_gpu_lzss_lcp_bound(size_t n, int coder);
+/* LZSSLCPCompressor::decompress (:125-130) for a stream of one of the five coders.  huff: tdc_gpu_lcpcomp_decompress_coder.  bit, gamma,
+ * delta: streams of 1 MiB and more whose longest literal run is at most 512 are parsed ON THE DEVICE (option dec_parse = 2: every
+ * stream, 0: never; dec_lean, dec_seg as for lcpcomp), the others by the host loop tdc_lzss_decode restates; ascii: host parse,
+ * references resolved on the device.  tdc_gpu_ctx_last_decode_on_device tells which.  Malformed input: TDC_GPU_ERR_ARG.  _into:
+ * TDC_GPU_ERR_OOM if the text does not fit the caller's buffer. */
+int tdc_gpu_lzss_lcp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                                uint64_t* factors, uint32_t* rounds);
+int tdc_gpu_lzss_lcp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                     size_t* out_len, uint64_t* factors, uint32_t* rounds);
 /* the factor list of LZSSLCPCompressor.hpp:60-115 (sorted by pos), three malloc'd arrays */
 int tdc_gpu_lzss_lcp_factorize(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold,
                                uint32_t** pos, uint32_t** src, uint32_t** len, size_t* z);
@@ -278,7 +296,8 @@ int tdc_gpu_lcpcomp_decompress_coder(tdc_gpu_ctx* ctx, const uint8_t* stream, si
  * link's rate; the malloc'd variants pay for the page faults of a fresh buffer).  TDC_GPU_ERR_OOM if the text does not fit. */
 int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                     size_t* out_len, uint64_t* factors, uint32_t* rounds);
-/* 1 if the last tdc_gpu_lcpcomp_decompress / _decompress_coder / _decompress_into call on this context succeeded and parsed the token
+/* 1 if the last tdc_gpu_lcpcomp_decompress / _decompress_coder / _decompress_into (or tdc_gpu_lzss_lcp_decompress / _into, tdc_gpu_lzw_decompress /
+ * _into) call on this context succeeded and parsed the token
  * stream on the device (coder=huff and coder=sle streams of 1 MiB and more whose longest literal run is at most 512; option dec_parse =
  * 0 never / 2 every size; option dec_lean = 0: the general marking also for streams of short tokens -- tests), 0 if on the host. */
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx);
@@ -400,6 +419,12 @@ int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t
  * TDC_GPU_ERR_UNSUPPORTED): the specification of tdc_gpu_lzw_decompress and its path for small streams.  TDC_GPU_ERR_ARG for what that
  * call refuses, TDC_GPU_ERR_TOO_LARGE for a text of more than 2^32 - 2 bytes. */
 int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
+/* The same contract for the lzss token stream (decode_text_internal, LCPCompressor.hpp:23-76) of an lzss_lcp (or lcpcomp) stream written with
+ * TDC_GPU_CODER_HUFF, _BIT, _GAMMA, _DELTA or _ASCII (else TDC_GPU_ERR_UNSUPPORTED): the sequential loop, references resolved along their
+ * chains.  The specification of tdc_gpu_lzss_lcp_decompress and its path for small streams.  TDC_GPU_ERR_ARG for: a text length the
+ * stream cannot hold, more literals or a longer factor than the text has room for, src + len > n, len = 0, a unary prefix that runs
+ * into the end of the stream or is longer than 64, a delta width above 64, a length that does not add up to n. */
+int tdc_lzss_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
 
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,

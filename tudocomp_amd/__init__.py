@@ -16,7 +16,8 @@ CODER_GAMMA = 1
 CODER_ARITH = 2
 CODER_ASCII = 3
 CODER_SLE = 4            # coder=sle(kmer=k): CODER_SLE | (k << 8), k = 0 means the reference's default 3
-CODER_BIT = 5            # BitCoder: lzw only
+CODER_BIT = 5            # BitCoder: lzw, lzss_lcp
+CODER_DELTA = 6          # EliasDeltaCoder: lzss_lcp
 COMP_ARRAYS = 0
 COMP_PLCPPEAKS = 1
 COMP_MAXLCP = 2
@@ -180,6 +181,17 @@ def huff_decode_literals(data):
 def lzw_decode(data, coder=CODER_BIT):
     """LZWCompressor::decompress (lzw::decode_step restated) on the host"""
     return _host_decode("tdc_lzw_decode", data, int(coder))
+
+
+def lzss_decode(data, coder=CODER_HUFF):
+    """decode_text_internal (LCPCompressor.hpp:23-76) on an lzss_lcp / lcpcomp stream of coder huff, bit, gamma, delta or ascii, on the
+    host: the escaped, 0-terminated text"""
+    return _host_decode("tdc_lzss_decode", data, int(coder))
+
+
+def lzss_lcp_bound(n, coder=CODER_HUFF):
+    """worst-case length of an lzss_lcp stream for a text of n bytes (0: a coder lzss_lcp does not take)"""
+    return _native.load().tdc_gpu_lzss_lcp_bound(n, int(coder))
 
 
 def device_count():
@@ -366,12 +378,49 @@ class Context:
         return ol.value, st.as_dict()
 
     def lzss_lcp_compress(self, text, threshold=3, coder=CODER_HUFF):
-        """LZSSLCPCompressor<HuffmanCoder>::compress on an escaped + 0-terminated view.  Returns (stream, stats)."""
+        """LZSSLCPCompressor<coder>::compress on an escaped + 0-terminated view; coder: CODER_HUFF, _BIT, _GAMMA, _DELTA or _ASCII.
+        Returns (stream, stats)."""
         a = _u8(text)
         out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
         self._check(self._L.tdc_gpu_lzss_lcp_compress(self._h, _ptr(a), len(a), threshold, coder, ctypes.byref(out),
                                                       ctypes.byref(n), ctypes.byref(st)))
         return self._take(out, n.value), st.as_dict()
+
+    def lzss_lcp_compress_into(self, text, n, out, threshold=3, coder=CODER_HUFF):
+        """lzss_lcp_compress of the first n bytes of `text` into a caller-owned buffer (PinnedBuffer or writable uint8 array; lzss_lcp_bound
+        sizes it): returns (out_len, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the length."""
+        ta = text.a if isinstance(text, PinnedBuffer) else _u8(text)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_lzss_lcp_compress_into(self._h, _ptr(ta), n, threshold, coder, _ptr(oa), oa.size, ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
+
+    lzss_lcp_bound = staticmethod(lzss_lcp_bound)
+
+    def lzss_lcp_decompress(self, stream, coder=CODER_HUFF):
+        """LZSSLCPCompressor::decompress for the five coders: returns the escaped, 0-terminated text and {"factors", "rounds",
+        "device_parse"} (options dec_parse, dec_lean, dec_seg pick the path)."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_lzss_lcp_decompress(self._h, _ptr(a) if len(a) else None, len(a), coder, ctypes.byref(p), ctypes.byref(n),
+                                                        ctypes.byref(f), ctypes.byref(r)))
+        return self._take(p, n.value), {"factors": f.value, "rounds": r.value,
+                                        "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
+    def lzss_lcp_decompress_into(self, stream, out, coder=CODER_HUFF):
+        """lzss_lcp_decompress into a caller-owned buffer (a PinnedBuffer or a writable uint8 array): returns (text length, stats)."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n = ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.tdc_gpu_lzss_lcp_decompress_into(self._h, _ptr(a) if len(a) else None, len(a), coder, _ptr(oa), oa.size, ctypes.byref(n),
+                                                      ctypes.byref(f), ctypes.byref(r))
+        if rc:
+            self._raise_required(rc, n.value)
+        return n.value, {"factors": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
 
     def lzss_lcp_factorize(self, text, threshold=3):
         a = _u8(text)
@@ -897,15 +946,25 @@ class LZWCompressor:
 
 
 class LZSSLCPCompressor:
-    """Mirror of tdc::LZSSLCPCompressor<coder> (compressors/LZSSLCPCompressor.hpp:22-132): threshold defaults to 3."""
+    """Mirror of tdc::LZSSLCPCompressor<coder> (compressors/LZSSLCPCompressor.hpp:22-132) with the reference's non-consuming coders
+    huff, bit, gamma, delta, ascii; threshold defaults to 3.  dec="host": the sequential loop (lzss_decode); dec="gpu" (an addition,
+    as for lz78 / lzw): tdc_gpu_lzss_lcp_decompress."""
 
-    def __init__(self, ctx, coder="huff", threshold=3):
-        if coder != "huff":
+    _CODERS = {"huff": CODER_HUFF, "bit": CODER_BIT, "gamma": CODER_GAMMA, "delta": CODER_DELTA, "ascii": CODER_ASCII}
+
+    def __init__(self, ctx, coder="huff", threshold=3, dec="host"):
+        if coder not in self._CODERS:
             raise RuntimeError("No implementation found for compressor lzss_lcp(coder=%s)" % coder)
-        self.ctx, self.threshold = ctx, int(threshold)
+        if dec not in ("host", "gpu"):
+            raise RuntimeError("lzss_lcp: dec must be host or gpu")
+        self.ctx, self.coder, self.threshold, self.dec = ctx, self._CODERS[coder], int(threshold), dec
         self.last_stats = None
 
     def compress(self, data):
-        out, st = self.ctx.lzss_lcp_compress(escape(data), self.threshold)
+        out, st = self.ctx.lzss_lcp_compress(escape(data), self.threshold, self.coder)
         self.last_stats = st
         return out
+
+    def decompress(self, stream):
+        text = self.ctx.lzss_lcp_decompress(stream, self.coder)[0] if self.dec == "gpu" else lzss_decode(stream, self.coder)
+        return unescape(text) if text else b""

@@ -34,6 +34,7 @@ SYMBOLS = [
     "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
     "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
     "tdc_gpu_lzw_compress", "tdc_gpu_lzw_decompress", "tdc_gpu_lzw_decompress_into", "tdc_lzw_factors", "tdc_lzw_decode",
+    "tdc_gpu_lzss_lcp_compress_into", "tdc_gpu_lzss_lcp_bound", "tdc_gpu_lzss_lcp_decompress", "tdc_gpu_lzss_lcp_decompress_into", "tdc_lzss_decode",
 ]
 
 
@@ -99,6 +100,12 @@ def load():
     L.tdc_gpu_lcpcomp_compress_dev.argtypes = [vp, vp, sz, u32, i32, i32, vp, sz, psz, ctypes.POINTER(Stats)]
     L.tdc_gpu_lz78_compress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(Stats)]
     L.tdc_gpu_lzss_lcp_compress.argtypes = [vp, vp, sz, u32, i32, pvp, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_lzss_lcp_compress_into.argtypes = [vp, vp, sz, u32, i32, vp, sz, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_lzss_lcp_bound.argtypes = [sz, i32]
+    L.tdc_gpu_lzss_lcp_bound.restype = sz
+    L.tdc_gpu_lzss_lcp_decompress.argtypes = [vp, vp, sz, i32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lzss_lcp_decompress_into.argtypes = [vp, vp, sz, i32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_lzss_decode.argtypes = [vp, sz, i32, vp, sz, psz]
     L.tdc_gpu_lzss_lcp_factorize.argtypes = [vp, vp, sz, u32, pvp, pvp, pvp, psz]
     L.tdc_gpu_arena_bytes.argtypes = [sz]
     L.tdc_gpu_arena_bytes.restype = sz

@@ -486,5 +486,14 @@ int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_
     if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) return TDC_GPU_ERR_UNSUPPORTED;
     return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::lzw_decode(in, len, coder == TDC_GPU_CODER_BIT, s); });
 }
+int tdc_lzss_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (coder != TDC_GPU_CODER_HUFF && coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA &&
+        coder != TDC_GPU_CODER_ASCII) return TDC_GPU_ERR_UNSUPPORTED;
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) {
+        std::vector<uint8_t> text;
+        tdc_amd::lzss_decode_coder(in, len, coder, text);
+        for (uint8_t b : text) s.put(b);
+    });
+}
 
 }  // extern "C"

@@ -418,39 +418,67 @@ u8* run_lzss_lcp(Ctx& c, const uint8_t* text, size_t n, uint32_t threshold, DevA
     }
     return d_text;
 }
+
+// public coder id -> coder id of encode_stream for the coders LZSSLCPCompressor is registered with (etc/registry_config.py:33-34); -1: none
+int lzss_lcp_enc_coder(int coder) {
+    switch (coder) {
+        case TDC_GPU_CODER_HUFF: return 0;
+        case TDC_GPU_CODER_ASCII: return 2;
+        case TDC_GPU_CODER_BIT: return 4;
+        case TDC_GPU_CODER_GAMMA: return 5;
+        case TDC_GPU_CODER_DELTA: return 6;
+        default: return -1;
+    }
+}
+
+void lzss_lcp_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold, int coder, Sink s, tdc_gpu_stats* stats) {
+    const int enc = lzss_lcp_enc_coder(coder);
+    if (enc < 0) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss_lcp: coder must be huff, bit, gamma, delta or ascii"};
+    check_host_text(text, n);
+    sink_check(s, "out/out_len is NULL");
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    Events ev(c);
+    DevArrays A;
+    const int e0 = ev.tick();
+    const u8* d_text = run_lzss_lcp(c, text, n, threshold, A, stats, ev);
+    const size_t cap = tdc_gpu_lzss_lcp_bound(n, coder);                    // the stream's worst case is what the device buffer is sized by
+    u8* d_out = c.arena.get<u8>(cap);
+    EncodeStats es;
+    const int e1 = ev.tick();
+    const size_t len = encode_stream(c, d_text, n, A.fs, enc, d_out, cap, &es);
+    const int e2 = ev.tick();
+    *s.out_len = len;
+    sink_fit(s, len);
+    sink_download(c, s, d_out, len);
+    const int e3 = ev.tick();
+    if (stats) {
+        stats->out_len = len; stats->flen_min = es.flen_min; stats->flen_max = es.flen_max; stats->fdist_max = es.fdist_max;
+        stats->sigma = es.sigma; stats->arena_bytes = c.arena.high;
+        ev.span(&stats->ms_encode, e1, e2); ev.span(&stats->ms_d2h, e2, e3); ev.span(&stats->ms_total, e0, e3);
+    }
+    ev.finish();
+    sink_commit(s, len);
+}
 }  // namespace
 
 extern "C" {
 
+size_t tdc_gpu_lzss_lcp_bound(size_t n, int coder) {
+    const int enc = lzss_lcp_enc_coder(coder);
+    if (enc < 0) return 0;
+    if (enc >= 4) return align_up(encode_bound_uni(n, enc) + 16, 8);       // (encode.hip: the worst case per coder; + 16: the pack's last word)
+    return align_up(encode_bound_coder(n, enc) + 16, 8);
+}
+
 int tdc_gpu_lzss_lcp_compress(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold, int coder,
                               uint8_t** out, size_t* out_len, tdc_gpu_stats* stats) {
-    return guarded(ctx, [&] {
-        if (coder != TDC_GPU_CODER_HUFF) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss_lcp: only coder=huff is built"};
-        check_host_text(text, n);
-        Sink s = sink_malloc(out, out_len);
-        sink_check(s, "out/out_len is NULL");
-        Ctx& c = ctx->c;
-        if (stats) memset(stats, 0, sizeof(*stats));
-        Events ev(c);
-        DevArrays A;
-        const int e0 = ev.tick();
-        const u8* d_text = run_lzss_lcp(c, text, n, threshold, A, stats, ev);
-        const size_t cap = tdc_gpu_lcpcomp_bound(n);
-        u8* d_out = c.arena.get<u8>(cap);
-        EncodeStats es;
-        const int e1 = ev.tick();
-        const size_t len = encode_huff(c, d_text, n, A.fs, d_out, cap, &es);
-        const int e2 = ev.tick();
-        sink_download(c, s, d_out, len);
-        const int e3 = ev.tick();
-        if (stats) {
-            stats->out_len = len; stats->flen_min = es.flen_min; stats->flen_max = es.flen_max; stats->fdist_max = es.fdist_max;
-            stats->sigma = es.sigma; stats->arena_bytes = c.arena.high;
-            ev.span(&stats->ms_encode, e1, e2); ev.span(&stats->ms_d2h, e2, e3); ev.span(&stats->ms_total, e0, e3);
-        }
-        ev.finish();
-        sink_commit(s, len);
-    });
+    return guarded(ctx, [&] { lzss_lcp_compress(ctx, text, n, threshold, coder, sink_malloc(out, out_len), stats); });
+}
+
+int tdc_gpu_lzss_lcp_compress_into(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold, int coder,
+                                   uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { lzss_lcp_compress(ctx, text, n, threshold, coder, sink_into(out, out_cap, out_len), stats); });
 }
 
 int tdc_gpu_lzss_lcp_factorize(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, uint32_t threshold,

@@ -1,5 +1,10 @@
-// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp (also lzss_lcp streams), lz78 and lzw decompression.
+// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78 and lzw decompression.
 #include "api.hpp"
+#include "decode.hpp"
+#include "../host/tdc_coders.hpp"
+
+#include <stdexcept>
+#include <vector>
 
 using namespace tdc;
 
@@ -13,6 +18,36 @@ void lcpcomp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int
     DecodeStats ds;
     // (no `need`: a caller's buffer that is too small is reported as the decoder's allocation failure, without the required size)
     const size_t n = run_decoder(s, "lcpcomp: the stream decodes to too large a text", nullptr, [&] { return decode_lzss(ctx->c, stream, len, enc, s, &ds); });
+    if (factors) *factors = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+    ctx->last_decode_device = (int)ds.device_parse;
+    sink_commit(s, n);
+}
+
+// LZSSLCPCompressor::decompress for its five coders.  huff and ascii are lcpcomp's streams.  bit, gamma, delta: the device parse where
+// decode_lzss_uni takes the stream, else the host loop that is its specification (tdc_lzss_decode).
+void lzss_lcp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, uint64_t* factors, uint32_t* rounds) {
+    ctx->last_decode_device = 0;
+    if (coder == TDC_GPU_CODER_HUFF || coder == TDC_GPU_CODER_ASCII) { lcpcomp_decompress(ctx, stream, len, coder, std::move(s), factors, rounds); return; }
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA)
+        throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss_lcp: coder must be huff, bit, gamma, delta or ascii"};
+    if (!stream) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    DecodeStats ds;
+    size_t n = 0;
+    const int kind = coder == TDC_GPU_CODER_BIT ? 0 : coder == TDC_GPU_CODER_GAMMA ? 1 : 2;
+    const bool dev = run_decoder(s, "lzss_lcp: the stream decodes to too large a text", nullptr,
+                                 [&] { return (size_t)decode_lzss_uni(ctx->c, stream, len, kind, s, &ds, &n); }) != 0;
+    if (!dev) {
+        std::vector<uint8_t> text;
+        try { tdc_amd::lzss_decode_coder(stream, len, coder, text); }
+        catch (const std::runtime_error&) { throw ArgError{TDC_GPU_ERR_ARG, "lzss_lcp: corrupt stream"}; }
+        n = text.size();
+        sink_fit(s, n);
+        u8* dst = decode_dest(s, n);
+        if (n) memcpy(dst, text.data(), n);
+        ds = DecodeStats();
+    }
     if (factors) *factors = ds.factors;
     if (rounds) *rounds = ds.rounds;
     ctx->last_decode_device = (int)ds.device_parse;
@@ -62,6 +97,16 @@ int tdc_gpu_lcpcomp_decompress_coder(tdc_gpu_ctx* ctx, const uint8_t* stream, si
 int tdc_gpu_lcpcomp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                     size_t* out_len, uint64_t* factors, uint32_t* rounds) {
     return guarded(ctx, [&] { lcpcomp_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), factors, rounds); });
+}
+
+int tdc_gpu_lzss_lcp_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len,
+                                uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzss_lcp_decompress(ctx, stream, len, coder, sink_malloc(out, out_len, "NULL argument"), factors, rounds); });
+}
+
+int tdc_gpu_lzss_lcp_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
+                                     size_t* out_len, uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzss_lcp_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), factors, rounds); });
 }
 
 int tdc_gpu_ctx_last_decode_on_device(const tdc_gpu_ctx* ctx) { return ctx ? ctx->last_decode_device : 0; }

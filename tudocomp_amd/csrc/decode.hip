@@ -187,6 +187,41 @@ __device__ __forceinline__ u32 sle_code(const SleTab* T, u64 w, u32& rank) {
     rank = (u32)(b >> (64 - sb)); return 3 + sb;
 }
 
+// The universal coders of lzss_lcp streams (BitCoder, EliasGammaCoder, EliasDeltaCoder: no table, every integer field and every literal
+// read by the same rule), the third table type.  kind: UNI_BIT -- a field of `cap` bits; UNI_GAMMA -- b zeros, a one, b bits
+// (io/BitIStream.hpp:129-156); UNI_DELTA -- gamma(b), then b bits (:158-162).  `cap` of a gamma / delta field is bits_for() of the largest
+// value the header allows there (at most 32): a longer unary prefix or a wider value is no token, which bounds both the work of a
+// candidate at an arbitrary bit position and how far behind it it reads (la_bits of decode_lzss_device).
+constexpr u32 UNI_BIT = 0, UNI_GAMMA = 1, UNI_DELTA = 2;
+struct UniTab { u32 kind, pad[3]; };
+
+// one integer field from bit y on: bits used (0: no token), value.  A gamma / delta code may be longer than one 64-bit window (up to
+// 32 + 1 + 32 bits): the prefix and the value are peeked separately.
+template <typename Win>
+__device__ __forceinline__ u32 dec_field(const UniTab* T, const Win& bw, u64 y, u32 cap, u32& val) {
+    if (T->kind == UNI_BIT) { val = (u32)(bw.peek(y) >> (64 - cap)); return cap; }          // 1 <= cap <= 32
+    const u64 w = bw.peek(y);
+    if (!w) return 0u;                                                                       // zeros up to the window's or the stream's end
+    u32 b = (u32)__builtin_clzll(w), used = b + 1;
+    if (T->kind == UNI_DELTA) {
+        if (b > 32u - (u32)__builtin_clz(cap)) return 0u;                                    // gamma(width), width <= cap: at most bits_for(cap) <= 6 bits
+        const u32 width = b ? (u32)((w << (b + 1)) >> (64 - b)) : 0u;
+        used += b;
+        b = width;
+    }
+    if (b > cap) return 0u;
+    val = b ? (u32)(bw.peek(y + used) >> (64 - b)) : 0u;
+    return used + b;
+}
+// a literal: the same code of a byte (the host loop keeps the low 8 bits of whatever the code holds: uliteral_t)
+template <typename Win>
+__device__ __forceinline__ u32 dec_lit(const UniTab* T, const Win& bw, u64 y, u32& sym) {
+    u32 v = 0;
+    const u32 l = dec_field(T, bw, y, 8u, v);
+    sym = v & 0xFFu;
+    return l;
+}
+
 // What differs between the coders, one overload per table type:
 //   dec_run:   the r literals of a run from bit y on (false: no token).  `open`: the run ended inside a k-mer.  SLE only -- the
 //              Huffman run, one code per literal, stands in dec_token itself (its instances keep the code they had before SLE)
@@ -222,6 +257,10 @@ __device__ __forceinline__ u32 dec_len(const SleTab*, u64 v, u32 lbits, u32& val
 }
 __device__ __forceinline__ constexpr bool dec_ends(const DevTab*) { return true; }
 __device__ __forceinline__ constexpr bool dec_ends(const SleTab*) { return false; }
+__device__ __forceinline__ constexpr bool dec_ends(const UniTab*) { return true; }
+// (UniTab's dec_len needs the window, not one left-aligned word: the length field is a code of its own)
+template <typename Win>
+__device__ __forceinline__ u32 dec_len(const UniTab* T, const Win& bw, u64 y, u32 lbits, u32& val) { return dec_field(T, bw, y, lbits, val); }
 
 // The token that starts at bit x.  Returns 0: literals + factor, 1: literals, then the stream ends (:83-91), < 0: no token.
 // End of an SLE stream: SLECoder's eof() is false inside a k-mer (:358-366), so a last run that ends inside one is followed by a
@@ -259,11 +298,47 @@ __device__ __forceinline__ int dec_token(const Win& bw, u64 x, const ParseParams
     next = y;
     return 0;
 }
+// The same for the universal coders: the run length, the literals, src and len are all read through the table -- P.dbits / P.W / P.lbits
+// are the widths of the fields (bit) or the caps of their codes (gamma, delta).
+template <typename Win, typename Lit>
+__device__ __forceinline__ int dec_token(const Win& bw, u64 x, const ParseParams& P, const UniTab* T, Lit&& lit, u64& next, u32& r, u32& src, u32& len) {
+    r = 0; src = 0; len = 0; next = x;
+    if (x >= P.total) return -1;
+    const u64 w = bw.peek(x);
+    u64 y = x + 1;
+    if (w >> 63) {
+        const u32 u = dec_field(T, bw, y, P.dbits, r);
+        if (!u || r > P.fdist_max) { r = 0; return -2; }
+        y += u;
+        for (u32 i = 0; i < r; ++i) {
+            u32 sym = 0;
+            const u32 l = dec_lit(T, bw, y, sym);
+            if (!l) return -3;
+            lit(i, (u8)sym);
+            y += l;
+        }
+        if (dec_ends(T) && y > P.total) return -4;
+    }
+    if (y >= P.total) { next = y; return 1; }
+    const u32 us = dec_field(T, bw, y, P.W, src);
+    if (!us) return -5;
+    y += us;
+    u32 v = 0;
+    const u32 ul = dec_len(T, bw, y, P.lbits, v);
+    if (!ul) return -5;
+    y += ul;
+    const u64 l64 = P.flen_min + (u64)v;                      // (flen_min: 0 for gamma / delta, which write the length raw)
+    if (l64 > P.n || (dec_ends(T) && y > P.total)) return -5;
+    len = (u32)l64;
+    next = y;
+    return 0;
+}
 
 __device__ __forceinline__ void dec_tab_to_lds(const DevTab* g, DevTab* l) {
     const u32* a = (const u32*)g; u32* b = (u32*)l;
     for (u32 i = threadIdx.x; i < sizeof(DevTab) / 4; i += blockDim.x) b[i] = a[i];
 }
+__device__ __forceinline__ void dec_tab_to_lds(const UniTab* g, UniTab* l) { if (threadIdx.x == 0) *l = *g; }
 __device__ __forceinline__ void dec_tab_to_lds(const SleTab* g, SleTab* l) {           // the ranks in use only
     const u32* a = (const u32*)g; u32* b = (u32*)l;
     const u32 words = 4 + 2 * min(g->sigma, SLE_DEV_RANKS);
@@ -806,6 +881,8 @@ template <typename Tab> struct DevCoder {
     Tab tab;                                  // as the kernels read it
     u64 code_max = 0;                         // longest literal code (bits)
     u64 lenf_min = 0, lenf_max = 0;           // shortest / longest length field of a factor (bits)
+    u64 srcf_min = 0, srcf_max = 0;           // the same for its source field (the fixed-width coders: W)
+    u64 runf_max = 0;                         // longest run-length field behind the flag bit (the fixed-width coders: dbits)
 };
 static void dev_coder(const HuffHeader& H, DevCoder<DevTab>& D) {
     DevTab* t = &D.tab;
@@ -818,6 +895,7 @@ static void dev_coder(const HuffHeader& H, DevCoder<DevTab>& D) {
     }
     D.code_max = H.have_table ? H.longest : 8;
     D.lenf_min = D.lenf_max = H.lbits;
+    D.srcf_min = D.srcf_max = H.W; D.runf_max = H.dbits;
 }
 // (false: the ranking does not fit the device table)
 static bool dev_coder(const SleHeader& H, DevCoder<SleTab>& D) {
@@ -837,21 +915,72 @@ static bool dev_coder(const SleHeader& H, DevCoder<SleTab>& D) {
     D.code_max = sb < 4 ? sb : sb < 6 ? 1 + sb : sb == 6 ? 8 : 3 + sb;
     D.lenf_min = H.lbits <= 5 ? H.lbits : 5;                                     // MinDistributedRange, :425-444
     D.lenf_max = H.lbits <= 5 ? H.lbits : 2 + H.lbits;
+    D.srcf_min = D.srcf_max = H.W; D.runf_max = H.dbits;
     return true;
 }
 
-// lcpcomp(coder=huff | sle) with the token stream parsed on the device.  Returns false if this stream keeps the host parse (long
+// Header of an lzss_lcp(coder=bit | gamma | delta) stream: no coder header, the four fields of decode_text_internal each written like
+// every other integer.  W / lbits / dbits receive what dec_field takes as `cap`: the fields' widths (bit), or bits_for() of the largest
+// value the header allows in the field (gamma, delta: src < n, len <= flen_max, run <= fdist_max).
+// false: a header the device parse does not take -- the host loop (tdc_amd::decode_text) has the verdict on it.
+struct UniHeader : LzssFields { u32 kind = UNI_BIT; };
+static bool parse_uni_header(FastBits& bs, u32 kind, size_t len, UniHeader& H) {
+    H.kind = kind;
+    bool ok = true;
+    auto field = [&](unsigned width) -> u64 {
+        if (kind == UNI_BIT) return bs.read(width);
+        auto gamma = [&]() -> u64 {
+            unsigned b = 0;
+            while (ok && !bs.read(1)) { if (bs.eof() || ++b > 57) ok = false; }
+            return ok ? bs.read(b) : 0;
+        };
+        const u64 v = gamma();
+        if (kind == UNI_GAMMA || !ok) return v;
+        if (v > 57) { ok = false; return 0; }
+        return bs.read((unsigned)v);
+    };
+    H.n = field(32);
+    if (!ok || H.n == 0 || H.n >= 0x7FFFFFFFull) return false;
+    H.W = bits_for(H.n);
+    H.flen_min = field(H.W); H.flen_max = field(H.W); H.fdist_max = field(H.W);
+    if (!ok || bs.pos > bs.total) return false;
+    const u64 bits = (u64)len * 8;                                          // decode_text's plausibility check, with the coder's shortest factor
+    const u64 fmin = kind == UNI_BIT ? H.W : kind == UNI_GAMMA ? 4 : 5;
+    if (H.n > bits + (bits / fmin + 1) * (H.flen_max ? H.flen_max : 1)) return false;
+    if (kind == UNI_BIT) {
+        H.lbits = bits_for(H.flen_max >= H.flen_min ? H.flen_max - H.flen_min : 0);   // (decode_text: a range of max < min is taken as one value)
+        H.dbits = bits_for(H.fdist_max);
+    } else {
+        H.lbits = std::min(32u, bits_for(H.flen_max));
+        H.dbits = std::min(32u, bits_for(H.fdist_max));
+        H.flen_min = 0;                                                     // the length is written raw: the ranges are ignored
+    }
+    return true;
+}
+// longest / shortest code of a field whose cap is `cap` (dec_field)
+static u64 uni_field_max(u32 kind, u64 cap) { return kind == UNI_BIT ? cap : kind == UNI_GAMMA ? 2 * cap + 1 : 2 * bits_for(cap) + 1 + cap; }
+static void dev_coder(const UniHeader& H, DevCoder<UniTab>& D) {
+    D.tab = UniTab{ H.kind, {0, 0, 0} };
+    D.code_max = uni_field_max(H.kind, 8);
+    D.lenf_max = uni_field_max(H.kind, H.lbits); D.srcf_max = uni_field_max(H.kind, H.W); D.runf_max = uni_field_max(H.kind, H.dbits);
+    // the shortest factor token the encoder writes: flag + gamma(0 or 1) twice = 1 + 3 + 3, delta: 1 + 4 + 4.  (Codes with an empty
+    // value field are shorter and still read, as by the host loop; a stream that holds more tokens than this allows for is refused.)
+    D.lenf_min = H.kind == UNI_BIT ? H.lbits : H.kind == UNI_GAMMA ? 3 : 4;
+    D.srcf_min = H.kind == UNI_BIT ? H.W : H.kind == UNI_GAMMA ? 3 : 4;
+}
+
+// lcpcomp(coder=huff | sle) and lzss_lcp(coder=bit | gamma | delta) with the token stream parsed on the device.  Returns false if this stream keeps the host parse (long
 // literal runs); throws StreamFormatError for malformed input.
 template <typename Tab>
 static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssFields& H, const DevCoder<Tab>& D, u64 x0, u64 total,
                                Sink& out, DecodeStats* st) {
     if (H.fdist_max > DEC_MAX_RUN) return false;
-    const u64 la_bits = 1 + H.dbits + H.fdist_max * D.code_max + H.W + D.lenf_max;     // the longest token a candidate may read
+    const u64 la_bits = 1 + D.runf_max + H.fdist_max * D.code_max + D.srcf_max + D.lenf_max;     // the longest token a candidate may read
     const u32 nwords = (u32)((DEC_TILE + la_bits + 31) / 32 + 4);
     const size_t lds = sizeof(Tab) + (size_t)nwords * 4;
     if (lds > 60 * 1024) return false;
     const size_t n = (size_t)H.n;
-    const u64 min_tok = 1 + H.W + D.lenf_min;
+    const u64 min_tok = 1 + D.srcf_min + D.lenf_min;
     const size_t zmax = (size_t)((total - x0) / min_tok + 2);
     const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;                    // (tests shrink the segments)
     const size_t seg = (size_t)std::min<u64>(seg_bits, total - x0 + 1);
@@ -1096,6 +1225,23 @@ size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, Sink& out, D
     resolve_and_download(c, (size_t)n, d_text, d_ref, d_pos, d_src, d_len, z, d_changed, out, st);
     c.arena.release(mark);
     return (size_t)n;
+}
+
+
+// lzss_lcp(coder=bit | gamma | delta), kind = UNI_*: the token stream parsed on the device by the rule decode_lzss picks its path with.
+// false: the stream is left to the host loop (small, long literal runs, a header the device parse does not take, no room on the device).
+bool decode_lzss_uni(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, DecodeStats* st, size_t* n_out) {
+    *st = DecodeStats();
+    if (!c.dec_parse || (c.dec_parse < 2 && len < ((size_t)1 << 20))) return false;
+    FastBits bs(stream, len);
+    UniHeader H;
+    if (!parse_uni_header(bs, (u32)kind, len, H) || bs.pos >= bs.total) return false;
+    DevCoder<UniTab> D;
+    dev_coder(H, D);
+    if (!decode_lzss_device(c, stream, len, H, D, bs.pos, bs.total, out, st)) return false;
+    st->device_parse = 1;
+    *n_out = (size_t)H.n;
+    return true;
 }
 
 }  // namespace tdc

@@ -36,7 +36,19 @@ struct EncParams {
     u32 W, lbits, dbits, flen_min;
     u32 raw_literals;     // sigma <= 1: literals are written as 8 raw bits (HuffmanCoder.hpp:565-566)
     u32 ascii;            // ASCIICoder (coders/ASCIICoder.hpp:29-50): decimal integers + ':', '0'/'1', raw literals, no "- min"
+    u32 uni;              // 0, ENC_GAMMA or ENC_DELTA: every integer and every literal as a self-delimiting code, no "- min"
 };
+// what the kernels are instantiated for: a code table or raw literals with fixed-width fields (HuffmanCoder, ArithmeticCoder, BitCoder),
+// ASCIICoder, EliasGammaCoder (coders/EliasGammaCoder.hpp:26-29), EliasDeltaCoder (coders/EliasDeltaCoder.hpp:26-29)
+constexpr int ENC_TAB = 0, ENC_ASCII = 1, ENC_GAMMA = 2, ENC_DELTA = 3;
+
+// io/BitOStream.hpp:105-135 -- gamma(v): bits_for(v) zeros, a one, v in bits_for(v) bits; delta(v): gamma(bits_for(v)), then v in
+// bits_for(v) bits.  bits_for(0) = 1.  v < 2^31: gamma takes at most 63 bits, delta 11 + 31
+__device__ __forceinline__ u32 uni_bits_for(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 1u; }
+template <int KIND> __device__ __forceinline__ u32 uni_cost(u32 v) {
+    const u32 b = uni_bits_for(v);
+    return KIND == ENC_GAMMA ? 2u * b + 1u : 2u * uni_bits_for(b) + 1u + b;
+}
 
 // number of characters ASCIICoder writes for an integer: its decimal digits and the ':'
 __device__ __forceinline__ u32 ascii_int_chars(u32 v) {
@@ -150,11 +162,16 @@ __global__ __launch_bounds__(256) void literal_hist_cls_kernel(const u8* __restr
 }
 
 // bits contributed by position p (see file header)
-template <bool ASCII>
+template <int KIND>
 __device__ __forceinline__ u32 position_cost(u32 own, u32 own_prev, bool first, u32 fl, u8 ch, u32 p, const u8* __restrict__ clen,
                                              const u32* __restrict__ fsrc,
                                              const EncParams& P, const ArithDev& A) {
-    if (ASCII) {
+    if (KIND == ENC_GAMMA || KIND == ENC_DELTA) {          // the cost of a position is a function of the values it writes
+        if (own == NONE32) return uni_cost<KIND>(ch) + (fl ? 1u + uni_cost<KIND>(fl) : 0u);
+        if (first || own != own_prev) return ((first || own_prev != NONE32) ? 1u : 0u) + uni_cost<KIND>(fsrc[p]) + uni_cost<KIND>(fl);
+        return 0u;
+    }
+    if (KIND == ENC_ASCII) {
         if (own == NONE32) return 8u + (fl ? 8u * (1u + ascii_int_chars(fl)) : 0u);
         if (first || own != own_prev) return ((first || own_prev != NONE32) ? 8u : 0u) + 8u * (ascii_int_chars(fsrc[p]) + ascii_int_chars(fl));
         return 0u;
@@ -188,7 +205,7 @@ __device__ __forceinline__ u32 position_cost_cls(u32 cl, u32 prevcl, bool first,
     return 0u;
 }
 
-template <bool ASCII>
+template <int KIND>
 __global__ __launch_bounds__(256) void tile_bits_kernel(const u8* __restrict__ text, const u32* __restrict__ owner,
                                                          const u32* __restrict__ flen, const u32* __restrict__ fsrc, size_t n, CodeTable tab, EncParams P,
                                                          ArithDev A, u64* __restrict__ tile_bits) {
@@ -207,7 +224,7 @@ __global__ __launch_bounds__(256) void tile_bits_kernel(const u8* __restrict__ t
         for (int j = 0; j < ENC_PER_THREAD; ++j) {
             const size_t p = p0 + j;
             if (p < n) {
-                sum += position_cost<ASCII>(own[j], prev, p == 0, fl[j], ch[j], (u32)p, clen, fsrc, P, A);
+                sum += position_cost<KIND>(own[j], prev, p == 0, fl[j], ch[j], (u32)p, clen, fsrc, P, A);
                 prev = own[j];
             }
         }
@@ -296,7 +313,13 @@ __device__ __forceinline__ void append_ascii_int(BitSink& sink, u32 v) {
     sink.append(':', 8);
 }
 
-template <bool ASCII>
+template <int KIND> __device__ __forceinline__ void append_uni(BitSink& sink, u32 v) {
+    const u32 b = uni_bits_for(v);
+    if (KIND == ENC_GAMMA) sink.append((1ull << b) | v, 2u * b + 1u);                 // b zeros, the one, v: one field of at most 63 bits
+    else { const u32 bb = uni_bits_for(b); sink.append((1ull << bb) | b, 2u * bb + 1u); sink.append(v, b); }
+}
+
+template <int KIND>
 __global__ __launch_bounds__(256) void pack_kernel(const u8* __restrict__ text, const u32* __restrict__ owner,
                                                     const u32* __restrict__ flen, const u32* __restrict__ fsrc, size_t n,
                                                     CodeTable tab, EncParams P, ArithDev A, const u64* __restrict__ tile_off,
@@ -320,7 +343,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const u8* __restrict__ text, 
         for (int j = 0; j < ENC_PER_THREAD; ++j) {
             const size_t p = p0 + j;
             if (p < n) {
-                sum += position_cost<ASCII>(own[j], prev, p == 0, fl[j], ch[j], (u32)p, clen, fsrc, P, A);
+                sum += position_cost<KIND>(own[j], prev, p == 0, fl[j], ch[j], (u32)p, clen, fsrc, P, A);
                 prev = own[j];
             }
         }
@@ -339,7 +362,16 @@ __global__ __launch_bounds__(256) void pack_kernel(const u8* __restrict__ text, 
         const size_t p = p0 + j;
         if (p < n) {
             const u32 o = own[j];
-            if (ASCII) {
+            if (KIND == ENC_GAMMA || KIND == ENC_DELTA) {
+                if (o == NONE32) {
+                    if (fl[j]) { sink.append(1, 1); append_uni<KIND>(sink, fl[j]); }     // LZSSCoding.hpp:62-68, :83-86
+                    append_uni<KIND>(sink, ch[j]);
+                } else if (p == 0 || o != prev) {
+                    if (p == 0 || prev != NONE32) sink.append(0, 1);                      // :57-59
+                    append_uni<KIND>(sink, fsrc[p]);                                      // :77
+                    append_uni<KIND>(sink, fl[j]);                                        // :78, the range ignored: no "- flen_min"
+                }
+            } else if (KIND == ENC_ASCII) {
                 if (o == NONE32) {
                     if (fl[j]) { sink.append('1', 8); append_ascii_int(sink, fl[j]); }
                     sink.append(ch[j], 8);
@@ -368,7 +400,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const u8* __restrict__ text, 
     sink.flush();
 }
 
-// pack_kernel<false> on the class bytes of FactorSpace::cls instead of owner[] (3 bytes less per position in each of the two passes of a tile).
+// pack_kernel<ENC_TAB> on the class bytes of FactorSpace::cls instead of owner[] (3 bytes less per position in each of the two passes of a tile).
 // REC: length and final source of a factor come from the records of the flatten stage (flatten.hip: {pos, len, original source, final
 // source}, indexed by the factor's rank in position order; the rank of a tile's first factor from the scanned start counts of
 // tile_bits_cls_kernel, inside the tile by the scan that also gives the bit offsets), and the length of a literal run from the position
@@ -471,6 +503,17 @@ __global__ void terminator_kernel(u8* out, u64 total_bits) {
 // and a ranking header of at most 1024 symbols of 10 bytes
 size_t encode_bound(size_t n) { return 12 * n + 4096; }
 size_t encode_bound_coder(size_t n, int coder) { return ((coder & 0xFF) == 2 ? 24 : 12) * n + ((coder & 0xFF) == 3 ? 32768 : 4096); }
+// The universal coders of lzss_lcp (coder 4 = BitCoder, 5 = EliasGammaCoder, 6 = EliasDeltaCoder), whole bytes per text position.  Every
+// value is below 2^31, so a fixed-width field takes at most 31 bits, gamma(v) at most 2 * 31 + 1 = 63 and delta(v) at most gamma(31) + 31
+// = 11 + 31 = 42.  The two candidates for the costliest position are a factor of length 1 behind another factor (threshold = 1: flag,
+// src, len) and a run of one literal (flag, run length 1, the literal):
+//   bit    1 + 31 + 31 = 63 bits (the length field is wide if some other factor is long)   |  1 + 31 + 8  = 40 bits    ->  8 bytes
+//   gamma  1 + 63 + gamma(1) = 1 + 63 + 3 = 67                                             |  1 + 3 + 17  = 21         ->  9 bytes
+//   delta  1 + 42 + delta(1) = 1 + 42 + 4 = 47                                             |  1 + 4 + 17  = 22         ->  6 bytes
+// (a literal: gamma / delta of a byte, 2 * 8 + 1 = 7 + 8 + 2 = 17 bits at most; a longer factor or run spreads the same fields over more
+// positions).  + 64: the header -- n and three fields, at most 63 + 3 * 65 bits (gamma: the zero-factor stream writes 2^32 - 1 in 65
+// bits) = 33 bytes -- and the terminator byte.
+size_t encode_bound_uni(size_t n, int coder) { return (coder == 4 ? 8 : coder == 5 ? 9 : 6) * n + 64; }
 
 size_t encode_huff(Ctx& c, const u8* text, size_t n, FactorSpace fs, u8* d_out, size_t out_cap, EncodeStats* st) {
     return encode_stream(c, text, n, fs, 0, d_out, out_cap, st, nullptr);
@@ -594,8 +637,8 @@ static void encode_step_b(Ctx& c, const u8* text, size_t n, FactorSpace& fs, int
     HuffTable& ht = E.ht;
     HostBitWriter& hw = E.hw;
     E.A = { nullptr, nullptr, nullptr, 0, 0 };
-    if (coder == 2) {
-        memset(&ht, 0, sizeof(ht));                                        // ASCIICoder writes no header
+    if (coder == 2 || coder >= 4) {
+        memset(&ht, 0, sizeof(ht));                                        // ASCIICoder, BitCoder, EliasGammaCoder, EliasDeltaCoder write no header
     } else if (coder == 0) {
         if (!c.huff_ok)
             throw HipError{hipErrorUnknown, "Huffman self-check failed: this C++ library breaks ties differently from the reference build, coder=huff streams would differ", (int)__LINE__};
@@ -616,7 +659,15 @@ static void encode_step_b(Ctx& c, const u8* text, size_t n, FactorSpace& fs, int
     P.flen_min = h_sc.flen_min;
     P.raw_literals = (ht.sigma <= 1) ? 1u : 0u;
     P.ascii = (coder == 2) ? 1u : 0u;
-    if (coder == 2) {
+    P.uni = coder == 5 ? (u32)ENC_GAMMA : coder == 6 ? (u32)ENC_DELTA : 0u;
+    if (P.uni) {                                       // every field as a code of its own; the zero-factor stream's flen_min = 2^32 - 1: 65 bits under gamma
+        const u64 fields[4] = { (u64)n, h_sc.flen_min, h_sc.flen_max, h_sc.fdist_max };
+        auto gamma = [&](u64 v) { const unsigned b = bits_for(v); hw.write_int(0, b); hw.write_bit(true); hw.write_int(v, b); };
+        for (u64 v : fields) {
+            if (P.uni == (u32)ENC_GAMMA) gamma(v);
+            else { gamma(bits_for(v)); hw.write_int(v, bits_for(v)); }
+        }
+    } else if (coder == 2) {
         const u64 fields[4] = { (u64)n, h_sc.flen_min, h_sc.flen_max, h_sc.fdist_max };
         for (u64 v : fields) {
             char tmp[24]; int k = 0;
@@ -639,9 +690,11 @@ static void encode_step_b(Ctx& c, const u8* text, size_t n, FactorSpace& fs, int
     u64* tile_bits = E.tile_bits;
     {
         Ctx::ProfScope prof(c, K_ENC_TILE_BITS, (u64)n * 9);
-        if (P.ascii) tile_bits_kernel<true><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
+        if (P.uni == (u32)ENC_GAMMA) tile_bits_kernel<ENC_GAMMA><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
+        else if (P.uni == (u32)ENC_DELTA) tile_bits_kernel<ENC_DELTA><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
+        else if (P.ascii) tile_bits_kernel<ENC_ASCII><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
         else if (fs.have_cls) tile_bits_cls_kernel<<<tiles, 256, 0, s>>>(text, fs.cls, n, E.tab, P, E.A, tile_bits, E.tile_rank);
-        else         tile_bits_kernel<false><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
+        else         tile_bits_kernel<ENC_TAB><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, E.tab, P, E.A, tile_bits);
         LAUNCH_CHECK();
     }
     exclusive_sum_u64(c, tile_bits, tile_bits, tiles, E.d_tp);
@@ -734,10 +787,12 @@ size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder
         size_t copied = 0;
         for (u32 q = 0; q < (overlap ? CH : 1u); ++q) {
             const u32 t0 = overlap ? (u32)((u64)tiles * q / CH) : 0u, t1 = overlap ? (u32)((u64)tiles * (q + 1) / CH) : tiles;
-            if (P.ascii) pack_kernel<true><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+            if (P.uni == (u32)ENC_GAMMA) pack_kernel<ENC_GAMMA><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+            else if (P.uni == (u32)ENC_DELTA) pack_kernel<ENC_DELTA><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+            else if (P.ascii) pack_kernel<ENC_ASCII><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
             else if (fs.have_cls && E.rec) pack_cls_kernel<true><<<t1 - t0, 256, 0, s>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, E.rec, E.tile_rank, (u32)E.z_rec);
             else if (fs.have_cls) pack_cls_kernel<false><<<t1 - t0, 256, 0, s>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, nullptr, nullptr, 0u);
-            else         pack_kernel<false><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+            else         pack_kernel<ENC_TAB><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
             LAUNCH_CHECK();
             if (overlap && q + 1 < CH) {
                 const size_t safe = (size_t)((base_bits + h_end[q]) / 64) * 8;          // bytes in front of the word the next chunk may still touch

@@ -162,6 +162,8 @@ struct EncodeStats { u64 factors = 0; u64 flen_min = 0, flen_max = 0, fdist_max 
 size_t encode_huff(Ctx& c, const u8* text, size_t n, FactorSpace fs, u8* d_out, size_t out_cap, EncodeStats* st);
 // the same with a selectable coder: 0 = HuffmanCoder, 1 = ArithmeticCoder (a15: coders/ArithmeticCoder.hpp:35-177),
 // 2 = ASCIICoder (coders/ASCIICoder.hpp:29-50; every integer and bit of the token stream as text)
+// 4 = BitCoder (the raw-literal stream of coder 0 without its table bit), 5 = EliasGammaCoder, 6 = EliasDeltaCoder (every field and
+// every literal as a self-delimiting code; factor spaces without class bytes only: lzss_lcp)
 // `early`: the first half (everything in front of the pack: gaps, histogram, coder header, bits per tile and their scan -- none of
 // it reads the factors' sources) has already run, see encode_early_*
 struct EncodeEarly;
@@ -180,6 +182,7 @@ void encode_early_free(EncodeEarly* e);
 // worst-case output size of encode_huff for a text of n bytes
 size_t encode_bound(size_t n);
 size_t encode_bound_coder(size_t n, int coder);    // coder as in encode_stream (2 = ASCIICoder needs twice as much)
+size_t encode_bound_uni(size_t n, int coder);      // coder 4 / 5 / 6 (lzss_lcp's BitCoder, EliasGammaCoder, EliasDeltaCoder)
 
 struct LzssStats { u64 factors = 0; };
 // a18: compressors/LZSSLCPCompressor.hpp:60-115 (lzss_lcp): greedy LZ77 parse from the previous / next smaller values of
@@ -212,6 +215,9 @@ struct Sink {
 };
 // the same for streams written with another coder: 0 = HuffmanCoder, 2 = ASCIICoder, 3 | kmer << 8 = SLECoder
 size_t decode_lzss(Ctx& c, const u8* stream, size_t len, int coder, Sink& out, DecodeStats* st);
+// lzss_lcp streams of the universal coders (kind 0 = BitCoder, 1 = EliasGammaCoder, 2 = EliasDeltaCoder) parsed on the device; false:
+// this stream keeps the host loop (tdc_coders.hpp decode_text), nothing has been written.  *n_out: the text length.
+bool decode_lzss_uni(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, DecodeStats* st, size_t* n_out);
 // LZ78Compressor::decompress (compressors/LZ78Compressor.hpp:142-160) for coder=gamma, parsed on the device (lz78_decode.hip).
 // Returns the text length; *need (nullable) receives it as soon as it is known -- also when out.into is too small (HipError
 // hipErrorOutOfMemory).  Malformed input: StreamFormatError; a text of more than 2^32 - 2 bytes: DecodeTooLarge.

@@ -374,17 +374,24 @@ public:
     }
 };
 
-// tdc::LZSSLCPCompressor<HuffmanCoder>  (compressors/LZSSLCPCompressor.hpp:22-132): threshold defaults to 3.
+// tdc::LZSSLCPCompressor<coder>  (compressors/LZSSLCPCompressor.hpp:22-132) with the coders the reference registers it with
+// (etc/registry_config.py:33-34: ascii, bit, gamma, delta, huff); threshold defaults to 3.
 class LZSSLCPCompressor : public Compressor {
     AlgorithmValue m_opts;
     std::shared_ptr<GpuContext> m_ctx;
     int m_device = 0;
+    int m_coder = TDC_GPU_CODER_HUFF;
 public:
     tdc_gpu_stats last_stats{};
     void set_device(int d) { m_device = d; }
     LZSSLCPCompressor(AlgorithmValue opts, std::shared_ptr<GpuContext> ctx) : m_opts(std::move(opts)), m_ctx(std::move(ctx)) {
         const std::string coder = m_opts.get("coder", "");
-        if (coder != "huff") throw std::runtime_error("No implementation found for compressor lzss_lcp(coder=" + coder + ")");
+        if (coder == "huff") m_coder = TDC_GPU_CODER_HUFF;
+        else if (coder == "bit") m_coder = TDC_GPU_CODER_BIT;
+        else if (coder == "gamma") m_coder = TDC_GPU_CODER_GAMMA;
+        else if (coder == "delta") m_coder = TDC_GPU_CODER_DELTA;
+        else if (coder == "ascii") m_coder = TDC_GPU_CODER_ASCII;
+        else throw std::runtime_error("No implementation found for compressor lzss_lcp(coder=" + coder + ")");   // Registry.hpp:214
     }
     InputRestrictions input_restrictions() const override { return {true, true}; }
     void compress(Input& input, Output& output) override {
@@ -392,13 +399,29 @@ public:
         const bytes view = input.as_view();
         uint8_t* out = nullptr; size_t out_len = 0;
         const int rc = tdc_gpu_lzss_lcp_compress(m_ctx->h, view.data(), view.size(), (uint32_t)m_opts.get_int("threshold", 3),
-                                                 TDC_GPU_CODER_HUFF, &out, &out_len, &last_stats);
+                                                 m_coder, &out, &out_len, &last_stats);
         if (rc == TDC_GPU_ERR_NO_SENTINEL) throw std::logic_error(tdc_gpu_strerror(rc));
         if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
-    void decompress(Input& input, Output& output) override { lzss_huff_decode(input, output); }   // :125-130 (DecodeBackBuffer)
+    // :125-130 (DecodeBackBuffer): the host loop decode_text with the coder's Decoder, which needs no device; dec=gpu (an addition, as
+    // for lz78 / lzw): tdc_gpu_lzss_lcp_decompress.  The stream is the same either way.
+    void decompress(Input& input, Output& output) override {
+        const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_lzss_lcp_decompress(m_ctx->h, in.data(), in.size(), m_coder, &out, &out_len, nullptr, nullptr);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
+        bytes text;
+        lzss_decode_coder(in.data(), in.size(), m_coder, text);
+        output.write(text.data(), text.size());
+    }
 };
 
 // tdc::LZ78Compressor<EliasGammaCoder, trie>  (compressors/LZ78Compressor.hpp:45-161): no input restrictions.
@@ -673,6 +696,8 @@ inline std::vector<std::string> registered_algorithms() {
              "lcpcomp(coder=..., comp=heap, ...)                                          [MI355X, sequential replay of the reference's heap: a parity row, about a minute per MiB -- inputs of a few hundred KiB at most]",
              "lcpcomp(coder=arithmetic, comp=arrays, threshold=5, flatten=1)              [MI355X, compress only]",
              "lzss_lcp(coder=huff, threshold=3)                                           [MI355X, libtdc_gpu.so]",
+             "lzss_lcp(coder=bit | gamma | delta | ascii, threshold=3)                    [MI355X: the position-space encoder with fixed-width fields / self-delimiting codes]",
+             "lzss_lcp(coder=huff | bit | gamma | delta, dec=gpu)                         [decompression parsed on the MI355X for streams of 1 MiB and more; ascii: host parse]",
              "lz78(coder=gamma)                                                           [host parse + MI355X gamma packer]",
              "lz78(coder=gamma, dec=gpu)                                                  [decompression parsed and expanded on the MI355X]",
              "lzw(coder=bit)                                                              [host parse + MI355X packer from closed-form bit offsets]",
@@ -722,7 +747,7 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
         return s;
     }
     if (av.name == "lzss_lcp") {
-        auto z = std::make_unique<LZSSLCPCompressor>(parse_algorithm_id(id, {"coder", "textds"}), std::move(ctx));
+        auto z = std::make_unique<LZSSLCPCompressor>(parse_algorithm_id(id, {"coder", "textds", "threshold", "dec"}), std::move(ctx));
         z->set_device(device);
         s.restrictions = z->input_restrictions();
         s.compressor = std::move(z);

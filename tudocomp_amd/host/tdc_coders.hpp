@@ -7,6 +7,8 @@
 //   HuffmanCoder::{Encoder,Decoder}       coders/HuffmanCoder.hpp:521-613           -> tdc_amd::HuffmanCoder::{Encoder,Decoder}
 //   EliasGammaCoder::{Encoder,Decoder}    coders/EliasGammaCoder.hpp:20-43          -> tdc_amd::EliasGammaCoder::...
 //   ASCIICoder::{Encoder,Decoder}         coders/ASCIICoder.hpp:26-84               -> tdc_amd::ASCIICoder::...
+//   BitCoder::{Encoder,Decoder}           coders/BitCoder.hpp                       -> tdc_amd::BitCoder::...
+//   EliasDeltaCoder::{Encoder,Decoder}    coders/EliasDeltaCoder.hpp:20-43          -> tdc_amd::EliasDeltaCoder::...
 //   lzss::encode_text / decode_text_internal  compressors/lzss/LZSSCoding.hpp:18-92, LCPCompressor.hpp:23-76
 //
 // As in the reference, overload resolution on the STATIC type of the range tag selects the literal coder (LiteralRange ->
@@ -102,6 +104,7 @@ public:
     }
     template <typename T> void write_unary(T v) { uint64_t x = (uint64_t)v; while (x--) write_bit(0); write_bit(1); }
     template <typename T> void write_elias_gamma(T v) { write_unary(coder_bits_for((uint64_t)v)); write_int((uint64_t)v, coder_bits_for((uint64_t)v)); }
+    template <typename T> void write_elias_delta(T v) { write_elias_gamma(coder_bits_for((uint64_t)v)); write_int((uint64_t)v, coder_bits_for((uint64_t)v)); }   // :131-135
 };
 
 // ---- io/BitIStream.hpp:16-195 ------------------------------------------------------------------------------------
@@ -137,6 +140,8 @@ public:
     }
     uint64_t read_unary() { uint64_t v = 0; while (!read_bit()) { if (eof() || ++v > 64) throw std::runtime_error("corrupt unary code"); } return v; }
     uint64_t read_elias_gamma() { const unsigned b = (unsigned)read_unary(); return read_int(b); }
+    // io/BitIStream.hpp:158-162; a width above 64 (the reference would shift out of range) is refused
+    uint64_t read_elias_delta() { const uint64_t b = read_elias_gamma(); if (b > 64) throw std::runtime_error("corrupt delta code"); return read_int((unsigned)b); }
 };
 
 // ---- Coder.hpp:14-151 -----------------------------------------------------------------------------------------------
@@ -155,6 +160,8 @@ protected:
 public:
     explicit Decoder(std::shared_ptr<BitIStream> in) : m_in(std::move(in)) {}
     bool eof() const { return m_in->eof(); }
+    // the fewest bits a factor (src, len) of a text of n positions takes: decode_text's plausibility check of a header
+    static unsigned min_factor_bits(size_t n) { return coder_bits_for(n); }
     template <typename value_t> value_t decode(const Range& r) { return (value_t)(r.min() + m_in->read_int(coder_bits_for(r.max() - r.min()))); }
     template <typename value_t> value_t decode(const BitRange&) { return (value_t)m_in->read_bit(); }
     const std::shared_ptr<BitIStream>& stream() { return m_in; }
@@ -247,7 +254,31 @@ struct EliasGammaCoder {
         using tdc_amd::Decoder::Decoder;
         using tdc_amd::Decoder::decode;
         template <typename value_t> value_t decode(const Range&) { return (value_t)m_in->read_elias_gamma(); }
+        static unsigned min_factor_bits(size_t) { return 4; }                 // the ranges are ignored: "1" (an empty field, src = 0) + gamma(1)
     };
+};
+
+// ---- coders/EliasDeltaCoder.hpp:20-43: as EliasGammaCoder with delta(v) = gamma(bits_for(v)), then v in bits_for(v) bits ------------
+struct EliasDeltaCoder {
+    class Encoder : public tdc_amd::Encoder {
+    public:
+        using tdc_amd::Encoder::Encoder;
+        using tdc_amd::Encoder::encode;
+        template <typename value_t> void encode(value_t v, const Range&) { m_out->write_elias_delta((uint64_t)v); }
+    };
+    class Decoder : public tdc_amd::Decoder {
+    public:
+        using tdc_amd::Decoder::Decoder;
+        using tdc_amd::Decoder::decode;
+        template <typename value_t> value_t decode(const Range&) { return (value_t)m_in->read_elias_delta(); }
+        static unsigned min_factor_bits(size_t) { return 5; }                 // "1" + delta(1)
+    };
+};
+
+// ---- coders/BitCoder.hpp: nothing but the default binary coding of Coder.hpp:60-77 (a literal is a TypeRange<uliteral_t>: 8 bits) -----
+struct BitCoder {
+    class Encoder : public tdc_amd::Encoder { public: using tdc_amd::Encoder::Encoder; };
+    class Decoder : public tdc_amd::Decoder { public: using tdc_amd::Decoder::Decoder; };
 };
 
 // ---- coders/ASCIICoder.hpp:26-84 -------------------------------------------------------------------------------------
@@ -327,9 +358,9 @@ inline void decode_text(decoder_t& decoder, std::vector<uint8_t>& text) {
     const size_t flen_max = decoder.template decode<size_t>(text_r);
     const size_t fdist_max = decoder.template decode<size_t>(text_r);
     {   // plausibility (corrupt headers would otherwise ask for gigabytes): a literal costs at least one bit, a factor at least
-        // bits_for(n) and covers at most flen_max positions
+        // bits_for(n) (the universal codes: a few bits) and covers at most flen_max positions
         const size_t bits = decoder.stream()->size_bytes() * 8;
-        if (n > bits + (bits / coder_bits_for(n) + 1) * (flen_max ? flen_max : 1)) throw std::runtime_error("corrupt stream: text length");
+        if (n > bits + (bits / decoder_t::min_factor_bits(n) + 1) * (flen_max ? flen_max : 1)) throw std::runtime_error("corrupt stream: text length");
     }
     const MinDistributedRange flen_r(flen_min, flen_max >= flen_min ? flen_max : flen_min);
     const Range fdist_r(fdist_max);
@@ -338,11 +369,11 @@ inline void decode_text(decoder_t& decoder, std::vector<uint8_t>& text) {
     size_t p = 0;
     while (!decoder.eof()) {
         size_t num = decoder.template decode<bool>(bit_r) ? decoder.template decode<size_t>(fdist_r) : 0;
-        if (p + num > n) throw std::runtime_error("corrupt stream: too many literals");
+        if (num > n - p) throw std::runtime_error("corrupt stream: too many literals");    // (p <= n; a gamma / delta field holds up to 64 bits)
         while (num--) text[p++] = decoder.template decode<uliteral_t>(literal_r);
         if (!decoder.eof()) {
             const size_t src = decoder.template decode<size_t>(text_r), len = decoder.template decode<size_t>(flen_r);
-            if (len == 0 || p + len > n || src + len > n) throw std::runtime_error("corrupt stream: factor out of range");
+            if (len == 0 || len > n - p || src > n || len > n - src) throw std::runtime_error("corrupt stream: factor out of range");
             for (size_t j = 0; j < len; ++j) ref[p + j] = (uint32_t)(src + j);
             p += len;
         }
@@ -358,6 +389,20 @@ inline void decode_text(decoder_t& decoder, std::vector<uint8_t>& text) {
             stack.push_back(q); q = ref[q];
         }
         for (uint32_t r : stack) { text[r] = text[q]; ref[r] = 0xFFFFFFFFu; }
+    }
+}
+
+// ---- the host loop behind tdc_lzss_decode (C ABI): decode_text with the Decoder of one of the five lzss_lcp coders (public coder ids).
+// The specification of the device decoder for these streams and its path for small ones.  false: no such coder.
+inline bool lzss_decode_coder(const uint8_t* in, size_t n, int coder, std::vector<uint8_t>& text) {
+    auto bits = std::make_shared<BitIStream>(in, n);
+    switch (coder) {
+        case TDC_GPU_CODER_HUFF:  { HuffmanCoder::Decoder d(bits); decode_text(d, text); return true; }
+        case TDC_GPU_CODER_GAMMA: { EliasGammaCoder::Decoder d(bits); decode_text(d, text); return true; }
+        case TDC_GPU_CODER_ASCII: { ASCIICoder::Decoder d(bits); decode_text(d, text); return true; }
+        case TDC_GPU_CODER_BIT:   { BitCoder::Decoder d(bits); decode_text(d, text); return true; }
+        case TDC_GPU_CODER_DELTA: { EliasDeltaCoder::Decoder d(bits); decode_text(d, text); return true; }
+        default: return false;
     }
 }
 
