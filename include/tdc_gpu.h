@@ -86,6 +86,8 @@ typedef struct {
     uint32_t pipe_dev;          /* tdc_gpu_pipeline_decompress_stats: bit i = stage i was decoded (bwt: inverted) on the device      */
     uint64_t pipe_len[8];       /* ... the length in bytes behind stage i, ...                                                      */
     float    pipe_ms[8];        /* ... and what stage i took (host clock around a synchronisation; only with option pipe_log)       */
+    uint32_t ranges_early;      /* tdc_gpu_lcpcomp_compress_into: rank ranges of the flatten stage whose pack was enqueued before the stage returned (flatten_chunks) */
+    uint32_t reserved0;
 } tdc_gpu_stats;
 
 /* ---- context -------------------------------------------------------------------------------------------- */
@@ -97,7 +99,8 @@ void tdc_gpu_ctx_destroy(tdc_gpu_ctx* ctx);
  * tdc_gpu_ctx_create() applies every TDC_GPU_<OPTION NAME IN UPPER CASE> variable through this same function (development aid,
  * tools/ab.sh).  `name`: an option name (README.md lists them; "wsort_min" and "TDC_GPU_WSORT_MIN" are the same option); out-of-range
  * values are clamped.  TDC_GPU_ERR_ARG for an unknown name.  tdc_gpu_option_count / _name enumerate the table -- all of it but
- * the switches of folded passes (fused_cand, sel_tile_counts: README.md), which this function accepts like any other. */
+ * the switches of folded passes (fused_cand, sel_tile_counts: README.md) and flatten_chunks (the flatten stage in rank ranges, with pack
+ * and download behind each range: README.md), which this function accepts like any other. */
 int tdc_gpu_ctx_set_option(tdc_gpu_ctx* ctx, const char* name, long value);
 int tdc_gpu_option_count(void);
 const char* tdc_gpu_option_name(int i);

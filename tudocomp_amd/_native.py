@@ -50,7 +50,8 @@ class Stats(ctypes.Structure):
                                         "sa_key_words", "sa_text_rounds", "sa_mode", "sa_overlapped", "eager_levels", "eager_phases", "sa_star_chains",
                                         "probes", "max_push_targets")] +
         [("d2h_early", ctypes.c_uint64)] +
-        [("pipe_stages", ctypes.c_uint32), ("pipe_dev", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8)])
+        [("pipe_stages", ctypes.c_uint32), ("pipe_dev", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8),
+         ("ranges_early", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)])
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}

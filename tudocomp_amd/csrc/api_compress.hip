@@ -78,6 +78,11 @@ void run_textds(Ctx& c, const u8* d_text, size_t n, DevArrays& A, tdc_gpu_stats*
     }
 }
 
+// flatten in rank ranges on the path that overlaps pack and download (option flatten_chunks = 0): factors per range at least, ranges at most
+// (2e9 B of English, 150 M factors, gains with 8 ranges; 256 MiB, 20 M factors, gains nothing with 2 or 4)
+constexpr size_t FLAT_CHUNK_MIN = (size_t)16 << 20;
+constexpr size_t FLAT_CHUNK_MAX = 8;
+
 void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, tdc_gpu_stats* st, Events* ev, int strategy,
                    int enc_coder, const u8* d_text) {
     if (!A.fs.flen) A.fs.flen = c.arena.get<u32>(n);          // (either length array may be in place already: run_textds, CandFused)
@@ -106,13 +111,21 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
     if (!early) expand_flen8(c, n, A.fs);                  // (planned, but there is no factor list to run it on: everybody else reads the dense array)
     if (early) {
         A.early = encode_early_reserve(c, n, c.enc_rec ? A.fs.nfact : 0);
+        // Where pack and download overlap (a host buffer of the caller's, records kept), the rounds run on rank ranges and each range's
+        // tiles are packed and sent while the next range is flattened.  Auto: a range holds at least FLAT_CHUNK_MIN
+        // factors, below that its later rounds no longer fill the device.
+        u32 K = c.flatten_chunks ? (u32)c.flatten_chunks : (u32)std::min<size_t>(A.fs.nfact / FLAT_CHUNK_MIN, FLAT_CHUNK_MAX);
+        K = flatten_chunk_count(K, A.fs.nfact);
+        const bool packed = K >= 2 && encode_early_chunks(c, n, A.fs, A.early, K, align_up(encode_bound_coder(n, enc_coder) + 16, 8));
+        if (!packed && c.flatten_chunks < 2) K = 1;                        // (forced ranges run without a consumer)
         c.wait_for(c.copy_stream, c.stream);                               // the factors are in place
         // one step per round (the host never waits for the copy stream while a round needs it), the rest when the rounds are over
         flatten_factors(c, n, A.fs, &fl, [&](int round) {
             StreamSwap sw(c, c.copy_stream);
             if (round == 1 || round == 2) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, false);
             else if (round == 0) encode_early_run(c, d_text, n, A.fs, enc_coder, A.early, true);
-        }, c.enc_rec ? encode_early_rec(A.early) : nullptr);
+        }, c.enc_rec ? encode_early_rec(A.early) : nullptr, K,
+        packed ? std::function<void(u32, size_t)>([&](u32 k, size_t) { encode_early_chunk_done(c, d_text, n, A.fs, A.early, k); }) : std::function<void(u32, size_t)>());
     } else if (flatten) {
         flatten_factors(c, n, A.fs, &fl);
     } else {
@@ -124,6 +137,7 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
         st->levels = fz.levels; st->mis_rounds = fz.rounds; st->small_levels = fz.small_levels; st->purges = fz.purges; st->window_pass = fz.window_pass; st->window_lcut = fz.window_lcut; st->eager_levels = fz.eager_levels; st->eager_phases = fz.eager_phases;
         st->probes = fz.probes; st->max_push_targets = fz.max_push_targets;
         st->num_flattened = fl.num_flattened; st->max_depth_lb = fl.max_depth_lb; st->flatten_rounds = fl.rounds;
+        st->ranges_early = A.early ? encode_early_packed(A.early) : 0u;
         if (ev) { ev->span(&st->ms_factorize, e0, e1); ev->span(&st->ms_flatten, e1, e2); }
     }
 }
@@ -239,6 +253,7 @@ size_t run_pipeline(Ctx& c, const u8* d_text, size_t n, u32 threshold, int flatt
     run_textds(c, d_text, n, A, st, &ev, strategy != TDC_GPU_COMP_ARRAYS, strategy == TDC_GPU_COMP_ARRAYS ? &cw : nullptr);
     run_factorize(c, n, A, threshold, flatten, st, &ev, strategy, enc_coder, d_text);
     EncodeStats es;
+    if (!*d_out_io && A.early) *d_out_io = encode_early_out(A.early, &out_cap);       // (reserved in front of the flatten ranges, whose packs wrote it)
     if (!*d_out_io) { out_cap = align_up(encode_bound_coder(n, enc_coder) + 16, 8); *d_out_io = c.arena.get<u8>(out_cap); }
     u8* d_out = *d_out_io;
     const int e0 = ev.tick();
@@ -313,7 +328,10 @@ void compress_host(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, bool raw, ui
     const size_t done = c.d2h_done <= len ? c.d2h_done : 0;                 // (0 unless the sink is the caller's buffer)
     if (stats) stats->d2h_early = done;
     HIP_TRY(hipMemcpyAsync(sink_host(s, len) + done, d_out + done, len - done, hipMemcpyDeviceToHost, c.stream));
-    if (done) c.wait_for(c.stream, c.copy_stream);                          // the front part travels on the copy stream
+    if (done) {                                                             // the front part travels on a side stream
+        c.wait_for(c.stream, c.copy_stream);
+        if (c.aux_stream) c.wait_for(c.stream, c.aux_stream);
+    }
     const int e3 = ev.tick();
     if (stats) { ev.span(&stats->ms_d2h, e2, e3); ev.span(&stats->ms_total, e0, e3); }
     ev.finish();

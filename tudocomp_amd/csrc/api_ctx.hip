@@ -135,9 +135,11 @@ const OptionDef OPTIONS[] = {
 constexpr size_t NOPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
 // Switches of passes folded into a neighbouring kernel: set like the others, but not enumerated by tdc_gpu_option_name() -- the enumerated
 // set is the one tests/test_gpu_parity.py::test_every_option_value_is_bit_exact walks; these are walked by tests/test_gpu_fused_candidates.py.
+// flatten_chunks (a schedule, not a fold) sits here for the same reason; tests/test_gpu_flatten_chunks.py walks it.
 const OptionDef FOLD_OPTIONS[] = {
     { "fused_cand",       [](Ctx& c, long v) { c.fused_cand = v != 0; } },
     { "sel_tile_counts",  [](Ctx& c, long v) { c.sel_tile_counts = v != 0; } },
+    { "flatten_chunks",   [](Ctx& c, long v) { c.flatten_chunks = clampi(v, 0, (long)FLATTEN_MAX_CHUNKS); } },
 };
 constexpr size_t NFOLD = sizeof(FOLD_OPTIONS) / sizeof(FOLD_OPTIONS[0]);
 const OptionDef* find_option(const char* name) {

@@ -206,6 +206,7 @@ struct Ctx {
     int upload_chunks = 16;        // chunks of the overlapped upload (4 .. 24; option upload_chunks)
     int flatten_steps = 1;         // flatten: chain steps per factor in the first round (0: unlimited; measured: 1,2,4,.. 8.5 ms; unlimited 11.2 ms)
     int flatten_growth = 8;        // ... and the factor the budget grows by per round (measured at 256 MiB: x2 8.4 ms, x4 7.4 ms, x8 7.0 ms)
+    int flatten_chunks = 0;        // flatten: rank ranges the rounds run on one after the other (flatten.hip).  0: ranges only where pack and download follow them (host-buffer calls that overlap the two; api_compress.hip picks the count), 1: never, k >= 2: k ranges wherever flatten_factors runs
     int sa_init_syms = 0;          // classic suffix sort: cap on the symbols of the initial key (0: as many as 64 bits hold; tuning)
     int dec_done = 1;              // decompression: final-bit mask in the pointer-jumping rounds (0: A/B switch)
     int dec_log = 0, bwt_log = 0, pipe_log = 0, level_log = 0, wsort_log = 0, eager_dump = 0, small_prof = 0, arena_log = 0;   // diagnostics on stderr
@@ -311,6 +312,10 @@ struct Ctx {
         u32* dst = zc_dev + (size_t)block * ZC_WORDS;
         publish_words_kernel<<<1, 64, 0, stream>>>((const u32*)dptr, (u32)(bytes / 4), dst, dst + 1024, seq);
         return hipGetLastError() == hipSuccess ? seq : 0;
+    }
+    // has the read-back `seq` of publish_async arrived?  (never waits: publish_wait returns at once after a true)
+    bool publish_test(u32 seq, u32 block) const {
+        return zc_host && __atomic_load_n((const u32*)(zc_host + (size_t)block * ZC_WORDS + 1024), __ATOMIC_ACQUIRE) == seq;
     }
     void publish_wait(u32 seq, void* out, size_t bytes, u32 block = 0) {
         volatile u32* flag = zc_host + (size_t)block * ZC_WORDS + 1024;

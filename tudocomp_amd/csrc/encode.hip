@@ -483,10 +483,16 @@ __global__ __launch_bounds__(256) void pack_cls_kernel(const u8* __restrict__ te
     sink.flush();
 }
 
-// out[q] = excl[(tiles * (q + 1)) / parts] for q < parts - 1 (bit offset at which chunk q of the pack ends), out[parts - 1] unused
-__global__ void pick_u64_kernel(const u64* __restrict__ excl, u32 tiles, u32 parts, u64* __restrict__ out) {
+// out[q] = excl[b.end[q]] for q < parts - 1 (bit offset at which chunk q of the pack ends: its last tile is b.end[q] - 1), the others unused
+struct PackBounds { u32 end[16]; };
+__global__ void pick_u64_kernel(const u64* __restrict__ excl, PackBounds b, u32 parts, u64* __restrict__ out) {
     const u32 q = threadIdx.x;
-    if (q < parts) out[q] = (q + 1 < parts) ? excl[(u32)((u64)tiles * (q + 1) / parts)] : 0ull;
+    if (q < parts) out[q] = (q + 1 < parts) ? excl[b.end[q]] : 0ull;
+}
+// tile that holds the first factor of rank range k + 1 of K (flatten_chunk_start), k < K - 1
+__global__ void range_tiles_kernel(const u32* __restrict__ fpos, u32 z, u32 K, u32* __restrict__ out) {
+    const u32 k = threadIdx.x;
+    if (k + 1 < K) out[k] = fpos[(u32)((u64)z * (k + 1) / K)] / (u32)ENC_TILE;
 }
 
 // io/BitOStream.hpp:53-64 : u = bits used in the last byte; u <= 5: OR u into that byte, else append a byte holding u.
@@ -574,6 +580,9 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
 #define TDC_PACK_CH 16     // (8: 0.3 ms more behind the last chunk at 2e9 B, 32: the same as 16)
 #endif
 constexpr u32 PACK_CH = TDC_PACK_CH;
+constexpr u32 PACK_AHEAD = 4;
+static_assert(2 * PACK_CH <= Ctx::CHUNK_EVENTS, "a chunk-done and a download event per chunk of the pack");
+static_assert(PACK_CH <= 16 && FLATTEN_MAX_CHUNKS <= PACK_CH, "PackBounds holds 16 chunk ends; a rank range of the flatten stage is a chunk of the pack");
 struct EncodeEarly {
     // scratch; reserved ahead of the flatten stage when the first half runs inside it (arena order: these, then flatten's lists)
     u32* d_hist = nullptr; u64* tile_bits = nullptr; u64* d_tp = nullptr;   // d_hist: 256 counters + the EncScalars; d_tp: total, then PACK_CH chunk ends
@@ -599,6 +608,17 @@ struct EncodeEarly {
     size_t out_len = 0;
     bool overlap = false;
     u64 h_end[PACK_CH];
+    // the second half in nb chunks: chunk q ends in front of tile end.end[q] (encode_reserve: equal shares of the tiles; by_rank: the tiles
+    // in front of rank range q + 1 of the flatten stage, encode_early_chunks -- neighbouring ends may coincide)
+    u32 nb = PACK_CH;
+    PackBounds end;
+    bool by_rank = false;
+    u8* d_out = nullptr; size_t out_cap = 0;     // by_rank: the stream's buffer, reserved in front of flatten's lists
+    // progress of the second half (by_rank: it starts inside the flatten stage)
+    bool begun = false;            // the buffer is cleared and the header on its way
+    u32 q_ready = 0, q_done = 0;   // chunks whose sources are final / whose pack is enqueued
+    size_t copied = 0;             // bytes of the stream already on their way to the host
+    u32 ncopy = 0;                 // by_rank: downloads submitted so far (download i records ev_chunk[PACK_CH + i] behind itself)
 };
 
 static void encode_reserve(Ctx& c, size_t n, EncodeEarly& E, size_t z_rec = 0) {
@@ -611,7 +631,10 @@ static void encode_reserve(Ctx& c, size_t n, EncodeEarly& E, size_t z_rec = 0) {
     E.d_hist = c.arena.get<u32>(256 + 4);
     E.tile_bits = c.arena.get<u64>(E.tiles + 1);
     E.d_tp = c.arena.get<u64>(1 + PACK_CH);
+    for (u32 q = 0; q < PACK_CH; ++q) E.end.end[q] = (u32)((u64)E.tiles * (q + 1) / PACK_CH);
 }
+
+static bool may_overlap(const Ctx& c, const EncodeEarly& E) { return c.d2h_host && E.tiles >= 64 * PACK_CH; }
 
 // Blocks 1 and 2 of the mapped host area carry the read-backs of steps A and B (free here: they belong to the one-workgroup levels of the
 // factorizer), so a step never waits for the step before it unless it has to.
@@ -701,8 +724,8 @@ static void encode_step_b(Ctx& c, const u8* text, size_t n, FactorSpace& fs, int
     if (E.tile_rank) exclusive_sum_u32(c, E.tile_rank, E.tile_rank, tiles, nullptr);
     // With a host destination (end-to-end entry point) the pack runs in PACK_CH chunks of tiles (second half): the bit offsets at
     // which the chunks end travel with the total
-    E.may_overlap = c.d2h_host && tiles >= 64 * PACK_CH;
-    pick_u64_kernel<<<1, 64, 0, s>>>(tile_bits, tiles, PACK_CH, E.d_tp + 1);
+    E.may_overlap = may_overlap(c, E);
+    pick_u64_kernel<<<1, 64, 0, s>>>(tile_bits, E.end, E.nb, E.d_tp + 1);
     LAUNCH_CHECK();
     E.seq_b = c.publish_async(E.d_tp, (1 + PACK_CH) * sizeof(u64), 2);
     E.step = 2;
@@ -738,6 +761,95 @@ void* encode_early_rec(EncodeEarly* E) { return E->rec; }
 void encode_early_run(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder, EncodeEarly* E, bool finish) { encode_first_half(c, text, n, fs, coder, *E, finish); }
 void encode_early_free(EncodeEarly* E) { delete E; }
 
+// ---- the second half: the buffer cleared and the header sent (pack_begin), the tiles packed chunk by chunk (pack_upto), on stream ps ----
+static void pack_begin(Ctx& c, hipStream_t ps, EncodeEarly& E, u8* d_out) {
+    if (E.begun) return;
+    const HostBitWriter& hw = E.hw;
+    HIP_TRY(hipMemsetAsync(d_out, 0, align_up(E.out_len + 8, 8), ps));
+    if (c.pinned_hdr && hw.bytes.size() <= Ctx::PINNED_HDR) {        // (through the context's page-locked block: a copy from pageable memory drains the stream)
+        memcpy(c.pinned_hdr, hw.bytes.data(), hw.bytes.size());
+        HIP_TRY(hipMemcpyAsync(d_out, c.pinned_hdr, hw.bytes.size(), hipMemcpyHostToDevice, ps));
+    } else HIP_TRY(hipMemcpyAsync(d_out, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, ps));
+    E.begun = true;
+}
+// chunks [E.q_done, upto) in one launch (none if they hold no tile); with the overlapped download the bytes they complete follow on cs
+static void pack_upto(Ctx& c, hipStream_t ps, hipStream_t cs, const u8* text, size_t n, const FactorSpace& fs, EncodeEarly& E, u8* d_out, u32 upto) {
+    if (upto <= E.q_done) return;
+    const EncParams& P = E.P;
+    const ArithDev& A = E.A;
+    const CodeTable& tab = E.tab;
+    const u64 base_bits = E.base_bits;
+    const u64* tile_bits = E.tile_bits;
+    const u32 t0 = E.q_done ? E.end.end[E.q_done - 1] : 0u, t1 = upto == E.nb ? E.tiles : E.end.end[upto - 1];
+    if (t1 > t0) {
+        if (P.uni == (u32)ENC_GAMMA) pack_kernel<ENC_GAMMA><<<t1 - t0, 256, 0, ps>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+        else if (P.uni == (u32)ENC_DELTA) pack_kernel<ENC_DELTA><<<t1 - t0, 256, 0, ps>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+        else if (P.ascii) pack_kernel<ENC_ASCII><<<t1 - t0, 256, 0, ps>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+        else if (fs.have_cls && E.rec) pack_cls_kernel<true><<<t1 - t0, 256, 0, ps>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, E.rec, E.tile_rank, (u32)E.z_rec);
+        else if (fs.have_cls) pack_cls_kernel<false><<<t1 - t0, 256, 0, ps>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, nullptr, nullptr, 0u);
+        else         pack_kernel<ENC_TAB><<<t1 - t0, 256, 0, ps>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
+        LAUNCH_CHECK();
+    }
+    E.q_done = upto;
+    if (E.overlap && upto < E.nb) {
+        const size_t safe = (size_t)((base_bits + E.h_end[upto - 1]) / 64) * 8;          // bytes in front of the word the next chunk may still touch
+        // by_rank: at most PACK_AHEAD downloads submitted and not finished, as the upload does (TextUpload::send) -- with step B's words
+        // late, all the deferred ranges come at once.  A download that has to stay back is not lost: its bytes leave with the next one.
+        bool room = true;
+        if (E.by_rank && E.ncopy >= PACK_AHEAD) room = hipEventQuery(c.ev_chunk[PACK_CH + E.ncopy - PACK_AHEAD]) == hipSuccess;
+        if (safe > E.copied && room) {
+            c.wait_for(cs, ps);
+            HIP_TRY(hipMemcpyAsync(c.d2h_host + E.copied, d_out + E.copied, safe - E.copied, hipMemcpyDeviceToHost, cs));
+            if (E.by_rank) {
+                HIP_TRY(hipEventRecord(c.ev_chunk[PACK_CH + E.ncopy++], cs));
+                (void)hipStreamQuery(cs);                               // (submit now: the next one may be a whole range away)
+            }
+            E.copied = safe;
+        }
+    }
+}
+
+// ---- pack and download behind the rank ranges of a chunked flatten (stages.hpp) -------------------------------------------------------
+bool encode_early_chunks(Ctx& c, size_t n, const FactorSpace& fs, EncodeEarly* e, u32 K, size_t out_cap) {
+    EncodeEarly& E = *e;
+    const size_t z = fs.nfact;
+    if (K < 2 || K > FLATTEN_MAX_CHUNKS || K > z || !fs.have_list || !E.rec || E.z_rec != z || E.step != 0 || !c.aux_stream || !c.pinned_hdr || !may_overlap(c, E)) return false;
+    E.d_out = c.arena.get<u8>(out_cap);
+    E.out_cap = out_cap;
+    u32 h[FLATTEN_MAX_CHUNKS] = { 0 };
+    const size_t mark = c.arena.mark();
+    u32* d_b = c.arena.get<u32>(FLATTEN_MAX_CHUNKS);
+    range_tiles_kernel<<<1, 64, 0, c.stream>>>(fs.fpos, (u32)z, K, d_b);
+    LAUNCH_CHECK();
+    c.read_n(d_b, h, K - 1);
+    c.arena.release(mark);
+    for (u32 k = 0; k + 1 < K; ++k) E.end.end[k] = std::min<u32>(h[k], E.tiles);     // (positions ascend with the rank: so do the ends)
+    for (u32 k = K - 1; k < PACK_CH; ++k) E.end.end[k] = E.tiles;
+    E.nb = K;
+    E.by_rank = true;
+    return true;
+}
+u8* encode_early_out(EncodeEarly* e, size_t* out_cap) { if (e->d_out && out_cap) *out_cap = e->out_cap; return e->d_out; }
+u32 encode_early_packed(const EncodeEarly* e) { return e->by_rank ? e->q_done : 0u; }
+
+// range k of the flatten stage is final and c.stream (the compute stream) stands behind its last round
+void encode_early_chunk_done(Ctx& c, const u8* text, size_t n, const FactorSpace& fs, EncodeEarly* e, u32 k) {
+    EncodeEarly& E = *e;
+    if (!E.by_rank || k >= E.nb) return;
+    HIP_TRY(hipEventRecord(c.ev_chunk[k], c.stream));
+    E.q_ready = k + 1;
+    // The host does not wait here: if the bit offsets of step B have not arrived, this range's tiles are issued with the next one's (and
+    // whatever is left when the ranges are over with encode_stream, behind the first half's last step).
+    if (E.step == 2 && E.seq_b && c.publish_test(E.seq_b, 2)) encode_step_c(c, E);
+    if (!E.done || align_up(E.out_len + 8, 8) > E.out_cap) return;
+    if (E.q_ready == E.nb) return;                     // (the last range: encode_stream is about to pack it, with the terminator behind)
+    const hipStream_t ps = c.copy_stream, cs = c.aux_stream;
+    pack_begin(c, ps, E, E.d_out);
+    HIP_TRY(hipStreamWaitEvent(ps, c.ev_chunk[k], 0));
+    for (u32 q = E.q_done + 1; q <= E.q_ready; ++q) pack_upto(c, ps, cs, text, n, fs, E, E.d_out, q);     // (deferred ranges one by one: the first one's bytes leave while the next is packed)
+    (void)hipStreamQuery(ps);
+}
+
 size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder, u8* d_out, size_t out_cap, EncodeStats* st, EncodeEarly* early) {
     EncodeStats local;
     if (!st) st = &local;
@@ -759,54 +871,31 @@ size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder
     EncodeEarly& E = *early;
     const size_t z = E.z;
     const EncScalars h_sc = E.sc;
-    const EncParams P = E.P;
-    const ArithDev A = E.A;
-    const CodeTable& tab = E.tab;
-    HostBitWriter& hw = E.hw;
-    const u64 base_bits = E.base_bits, total_bits = E.total_bits;
-    const unsigned tiles = E.tiles;
-    const u64* tile_bits = E.tile_bits;
+    const u64 total_bits = E.total_bits;
     const size_t out_len = E.out_len;
     const size_t padded = align_up(out_len + 8, 8);
     if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "encode: output buffer too small", (int)__LINE__};
 
     // ---- pass 2: pack ----------------------------------------------------------------------------------------
-    HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
-    if (c.pinned_hdr && hw.bytes.size() <= Ctx::PINNED_HDR) {        // (through the context's page-locked block: a copy from pageable memory drains the stream)
-        memcpy(c.pinned_hdr, hw.bytes.data(), hw.bytes.size());
-        HIP_TRY(hipMemcpyAsync(d_out, c.pinned_hdr, hw.bytes.size(), hipMemcpyHostToDevice, s));
-    } else HIP_TRY(hipMemcpyAsync(d_out, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, s));
+    // (by_rank: the front chunks were enqueued inside the flatten stage, on the copy stream with their downloads on the aux stream; what
+    //  is left follows them there)
+    if (E.by_rank && d_out != E.d_out) throw HipError{hipErrorUnknown, "encode: the pack behind the flatten ranges writes the buffer reserved for it", (int)__LINE__};
+    const hipStream_t ps = E.by_rank ? c.copy_stream : s, cs = E.by_rank ? c.aux_stream : c.copy_stream;
+    pack_begin(c, ps, E, d_out);
     {
-        Ctx::ProfScope prof(c, K_ENC_PACK, (u64)n * 9 + (u64)z * 4 + out_len);
-        // in PACK_CH chunks of tiles when the stream goes to the host: once a chunk is done the bytes in front of its last
+        StreamSwap on_ps(c, ps);                        // (the profile's events go where the pack runs)
+        // (by_rank: the ranges packed inside the flatten stage are not in this scope, nor are their bytes)
+        const u32 t_left = E.tiles - (E.q_done ? E.end.end[E.q_done - 1] : 0u);
+        Ctx::ProfScope prof(c, K_ENC_PACK, E.tiles ? (u64)((double)((u64)n * 9 + (u64)z * 4 + out_len) * t_left / E.tiles) : 0);
+        // in chunks of tiles when the stream goes to the host: once a chunk is done the bytes in front of its last
         // (possibly shared) 64-bit word are final and start their way to the host on the copy stream, while the next chunk is
         // being packed.
-        constexpr u32 CH = PACK_CH;
-        const bool overlap = E.overlap;
-        const u64* h_end = E.h_end;
-        size_t copied = 0;
-        for (u32 q = 0; q < (overlap ? CH : 1u); ++q) {
-            const u32 t0 = overlap ? (u32)((u64)tiles * q / CH) : 0u, t1 = overlap ? (u32)((u64)tiles * (q + 1) / CH) : tiles;
-            if (P.uni == (u32)ENC_GAMMA) pack_kernel<ENC_GAMMA><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
-            else if (P.uni == (u32)ENC_DELTA) pack_kernel<ENC_DELTA><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
-            else if (P.ascii) pack_kernel<ENC_ASCII><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
-            else if (fs.have_cls && E.rec) pack_cls_kernel<true><<<t1 - t0, 256, 0, s>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, E.rec, E.tile_rank, (u32)E.z_rec);
-            else if (fs.have_cls) pack_cls_kernel<false><<<t1 - t0, 256, 0, s>>>(text, fs.cls, fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0, nullptr, nullptr, 0u);
-            else         pack_kernel<ENC_TAB><<<t1 - t0, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, n, tab, P, A, tile_bits, base_bits, (u64*)d_out, t0);
-            LAUNCH_CHECK();
-            if (overlap && q + 1 < CH) {
-                const size_t safe = (size_t)((base_bits + h_end[q]) / 64) * 8;          // bytes in front of the word the next chunk may still touch
-                if (safe > copied) {
-                    c.wait_for(c.copy_stream, s);
-                    HIP_TRY(hipMemcpyAsync(c.d2h_host + copied, d_out + copied, safe - copied, hipMemcpyDeviceToHost, c.copy_stream));
-                    copied = safe;
-                }
-            }
-        }
-        c.d2h_done = copied;
+        for (u32 q = E.overlap ? E.q_done + 1 : E.nb; q <= E.nb; ++q) pack_upto(c, ps, cs, text, n, fs, E, d_out, q);
+        c.d2h_done = E.copied;
     }
-    terminator_kernel<<<1, 64, 0, s>>>(d_out, total_bits);
+    terminator_kernel<<<1, 64, 0, ps>>>(d_out, total_bits);
     LAUNCH_CHECK();
+    if (ps != s) c.wait_for(s, ps);
     HIP_TRY(hipStreamSynchronize(s));      // hw.bytes must outlive the async copy
 
     st->factors = z;

@@ -352,7 +352,7 @@ __global__ void sources_fill_pos_kernel(const u32* __restrict__ flen, size_t n, 
     if (p < n && flen[p]) fsrc[p] = lazy_source(src_prio, src_sa, src_n, fsrc, (u32)p);
 }
 
-// One round over the still-waiting factors.  FIRST: every factor, state taken from its record; else the items of `work`.
+// One round over the still-waiting factors.  FIRST: the nwork factors from rank `first` on, state taken from their records; else the items of `work`.
 // A thread walks FL_K chains side by side: per step first the owner[] words of all of them, then the records -- FL_K independent
 // scattered loads in flight per thread instead of one.  The factors of a workgroup that have to wait are appended to the next
 // list with ONE atomic per workgroup (per wave it would be millions of atomics on one address: ~25 ns each, serialised).
@@ -362,7 +362,7 @@ __global__ void sources_fill_pos_kernel(const u32* __restrict__ flen, size_t n, 
 constexpr int FL_K = TDC_FL_K;
 template <bool FIRST, bool REM>    // REM: owner words carry rem_bits remainder bits above the rank (FactorSpace::owner_rem_bits >= 1)
 __global__ __launch_bounds__(256) void flatten_round_kernel(const uint4* __restrict__ work, u32 nwork, size_t n, const u32* __restrict__ owner,
-                                                             uint4* rec, uint4* __restrict__ next, FlattenScalars* __restrict__ sc, u32 max_steps, u32 rem_bits) {
+                                                             uint4* rec, uint4* __restrict__ next, FlattenScalars* __restrict__ sc, u32 max_steps, u32 rem_bits, u32 first) {
     const u32 rsh = 32u - rem_bits, qmax = (1u << rem_bits) - 1u, rmask = REM ? ((1u << rsh) - 1u) : 0xFFFFFFFFu;
     __shared__ u32 sm[5];
     __shared__ u32 s_base;
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void flatten_round_kernel(const uint4* __restr
         const u32 j = base + (u32)r * 256u + threadIdx.x;
         fi[r] = 0; len[r] = 0; src[r] = 0; dep[r] = 0;
         if (j < nwork) {
-            if (FIRST) { const uint4 me = rec[j]; fi[r] = j; len[r] = me.y; src[r] = me.z; }
+            if (FIRST) { const uint4 me = rec[first + j]; fi[r] = first + j; len[r] = me.y; src[r] = me.z; }
             else { const uint4 it = work[j]; fi[r] = it.x; len[r] = it.y; src[r] = it.z; dep[r] = it.w; }
             valid |= 1u << r;
         }
@@ -477,7 +477,13 @@ void materialize_sources(Ctx& c, size_t n, FactorSpace& fs) {
     fs.src_prio = nullptr;
 }
 
-void flatten_factors(Ctx& c, size_t n, FactorSpace fs, FlattenStats* st, const std::function<void(int)>& between, void* rec_keep) {
+// Rank ranges (chunks > 1): a chain step that lands in factor s takes the FINAL source of s only if s has a lower rank than the walking
+// factor, and the original one otherwise -- the final source of rank i depends on final sources of ranks < i alone.  With every record
+// initialised, the round loop may therefore run on [r_0, r_1), then on [r_1, r_2), ... (r_k = z k / K) and each range is final when its own
+// rounds are over, whatever lies behind it: what reads the front of the list (the pack, api_compress.hip) starts while the back is
+// still being flattened.  Every range starts with the first-round budget again.
+void flatten_factors(Ctx& c, size_t n, FactorSpace fs, FlattenStats* st, const std::function<void(int)>& between, void* rec_keep,
+                     u32 chunks, const std::function<void(u32, size_t)>& chunk_done) {
     if (fs.src_prio && !rec_keep) materialize_sources(c, n, fs);       // (the commit pass only writes the sources that moved)
     FlattenStats local;
     if (!st) st = &local;
@@ -488,54 +494,61 @@ void flatten_factors(Ctx& c, size_t n, FactorSpace fs, FlattenStats* st, const s
     u32* fpos = fs.have_list ? fs.fpos : c.arena.get<u32>(n);
     const size_t z = fs.have_list ? fs.nfact : extract_factors(c, n, fs, fpos, nullptr, nullptr, n);
     if (z == 0) { if (between) between(0); c.arena.release(mark); return; }
+    const u32 K = flatten_chunk_count(chunks ? chunks : (u32)c.flatten_chunks, z);
     uint4* rec = rec_keep ? (uint4*)rec_keep : (uint4*)c.arena.alloc(z * sizeof(uint4));
     FlattenScalars* d_sc = (FlattenScalars*)c.arena.alloc(sizeof(FlattenScalars));
     HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(FlattenScalars), s));
     const unsigned gz = cdiv(z, 256);
     // (lazy sources are only left to this kernel by a caller that keeps the records: nothing is written back into fsrc[] then)
+    // One launch over all z records, chunked or not: chain steps read pos, len and the original source of later factors too
     flatten_init_kernel<<<gz, 256, 0, s>>>(fpos, z, fs.flen, fs.fsrc, rec, fs.have_list ? fs.flenl : nullptr, fs.src_prio, fs.src_sa, fs.src_n);
     LAUNCH_CHECK();
-    // work lists of the still-waiting factors (the first round visits every factor)
-    uint4* work[2] = { (uint4*)c.arena.alloc(z * sizeof(uint4)), nullptr };
-    u32 waiting = (u32)z;
-    int cur_w = -1;                               // -1: every factor (first round)
-    // steps per round: few in the first rounds (most chains are short; the lanes of a wave wait for the longest one),
-    // growing afterwards
-    u32 max_steps = (u32)c.flatten_steps;   // (option flatten_steps; measured: 1,2,4,.. 8.5 ms; unlimited 11.2 ms)
-    if (max_steps == 0) max_steps = 1u << 30;
+    // work lists of the still-waiting factors (the first round of a range visits every factor of it): one pair for the largest range
+    const size_t cmax = (z + K - 1) / K;
+    uint4* work[2] = { (uint4*)c.arena.alloc(cmax * sizeof(uint4)), nullptr };
     // budget growth per round (measured at 256 MiB: x2 8.4 ms, x4 7.4 ms, x8 7.0 ms)
     u32 flat_growth = (u32)c.flatten_growth;
     if (flat_growth < 2) flat_growth = 2;
-    u32 stalled = 0;
-    while (waiting) {
-        const int nxt = cur_w < 0 ? 0 : (cur_w ^ 1);
-        if (!work[nxt]) work[nxt] = (uint4*)c.arena.alloc((size_t)waiting * sizeof(uint4));   // (the second list: at most the survivors of round 1)
-        HIP_TRY(hipMemsetAsync(&d_sc->waiting, 0, sizeof(u32), s));
-        {   // per waiting factor: its item (16) + one chain step (owner word + record: 20) + item / final source out (16)
-            Ctx::ProfScope prof(c, K_FLATTEN_ROUND, (u64)waiting * 52);
-            const u32 rb = fs.owner_rem_bits;
-            const unsigned g = cdiv(waiting, 256 * FL_K);
-            if (cur_w < 0) { if (rb) flatten_round_kernel<true, true><<<g, 256, 0, s>>>(nullptr, waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, rb);
-                             else flatten_round_kernel<true, false><<<g, 256, 0, s>>>(nullptr, waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, 0u); }
-            else { if (rb) flatten_round_kernel<false, true><<<g, 256, 0, s>>>(work[cur_w], waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, rb);
-                   else flatten_round_kernel<false, false><<<g, 256, 0, s>>>(work[cur_w], waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, 0u); }
-            LAUNCH_CHECK();
+    for (u32 k = 0; k < K; ++k) {
+        const size_t r0 = flatten_chunk_start(z, k, K), r1 = flatten_chunk_start(z, k + 1, K);
+        u32 waiting = (u32)(r1 - r0);
+        int cur_w = -1;                               // -1: every factor of the range (first round)
+        // steps per round: few in the first rounds (most chains are short; the lanes of a wave wait for the longest one),
+        // growing afterwards
+        u32 max_steps = (u32)c.flatten_steps;   // (option flatten_steps; measured: 1,2,4,.. 8.5 ms; unlimited 11.2 ms)
+        if (max_steps == 0) max_steps = 1u << 30;
+        u32 stalled = 0;
+        while (waiting) {
+            const int nxt = cur_w < 0 ? 0 : (cur_w ^ 1);
+            if (!work[nxt]) work[nxt] = (uint4*)c.arena.alloc((K == 1 ? (size_t)waiting : cmax) * sizeof(uint4));   // (the second list; one range: at most the survivors of round 1)
+            HIP_TRY(hipMemsetAsync(&d_sc->waiting, 0, sizeof(u32), s));
+            {   // per waiting factor: its item (16) + one chain step (owner word + record: 20) + item / final source out (16)
+                Ctx::ProfScope prof(c, K_FLATTEN_ROUND, (u64)waiting * 52);
+                const u32 rb = fs.owner_rem_bits;
+                const unsigned g = cdiv(waiting, 256 * FL_K);
+                if (cur_w < 0) { if (rb) flatten_round_kernel<true, true><<<g, 256, 0, s>>>(nullptr, waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, rb, (u32)r0);
+                                 else flatten_round_kernel<true, false><<<g, 256, 0, s>>>(nullptr, waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, 0u, (u32)r0); }
+                else { if (rb) flatten_round_kernel<false, true><<<g, 256, 0, s>>>(work[cur_w], waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, rb, 0u);
+                       else flatten_round_kernel<false, false><<<g, 256, 0, s>>>(work[cur_w], waiting, n, fs.owner, rec, work[nxt], d_sc, max_steps, 0u, 0u); }
+                LAUNCH_CHECK();
+            }
+            // (this round is on its way: 150 M factors in the first one at 2e9 B, 55 M in the second, 9 M in the third; the later ones are too
+            //  short to hide anything behind)
+            if (between) between((int)st->rounds + 1);
+            const u32 now = c.read(&d_sc->waiting);
+            st->rounds++;
+            if (c.level_log) {
+                const FlattenScalars hs = c.read(d_sc);
+                fprintf(stderr, "flatten round %u (range %u of %u): %u waiting -> %u (budget %u steps; cumulative: %llu visits, %llu of them waits)\n", st->rounds, k + 1, K, waiting, now, max_steps, hs.steps, hs.waits);
+            }
+            stalled = (now == waiting) ? stalled + 1 : 0;         // (a round with a small budget may finish nothing; never many in a row)
+            if (now > waiting || (now == waiting && max_steps >= (1u << 30)) || stalled > 40)
+                throw HipError{hipErrorUnknown, "flatten: rounds made no progress", (int)__LINE__};
+            waiting = now;
+            cur_w = nxt;
+            if (max_steps < (1u << 30)) max_steps = (max_steps > (1u << 30) / flat_growth) ? (1u << 30) : max_steps * flat_growth;
         }
-        // (this round is on its way: 150 M factors in the first one at 2e9 B, 55 M in the second, 9 M in the third; the later ones are too
-        //  short to hide anything behind)
-        if (between) between((int)st->rounds + 1);
-        const u32 now = c.read(&d_sc->waiting);
-        st->rounds++;
-        if (c.level_log) {
-            const FlattenScalars hs = c.read(d_sc);
-            fprintf(stderr, "flatten round %u: %u waiting -> %u (budget %u steps; cumulative: %llu visits, %llu of them waits)\n", st->rounds, waiting, now, max_steps, hs.steps, hs.waits);
-        }
-        stalled = (now == waiting) ? stalled + 1 : 0;         // (a round with a small budget may finish nothing; never many in a row)
-        if (now > waiting || (now == waiting && max_steps >= (1u << 30)) || stalled > 40)
-            throw HipError{hipErrorUnknown, "flatten: rounds made no progress", (int)__LINE__};
-        waiting = now;
-        cur_w = nxt;
-        if (max_steps < (1u << 30)) max_steps = (max_steps > (1u << 30) / flat_growth) ? (1u << 30) : max_steps * flat_growth;
+        if (chunk_done) chunk_done(k, r1);            // (the host has read this range's last count: ranks < r1 are final)
     }
     if (between) between(0);
     if (!rec_keep) {                                   // (a caller that keeps the records reads the final sources there)

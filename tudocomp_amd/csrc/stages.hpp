@@ -140,14 +140,22 @@ void factorize_max_lcp(Ctx& c, size_t n, u32* isa, const u32* phi, u32* plcp, u3
 void factorize_max_heap(Ctx& c, size_t n, const u32* sa, const u32* isa, const u32* plcp, u32 maxlcp, u32 threshold, FactorSpace& fs,
                         FactorizeStats* st);
 
-struct FlattenStats { u64 num_flattened = 0; u64 max_depth_lb = 0; u32 rounds = 0; };
+struct FlattenStats { u64 num_flattened = 0; u64 max_depth_lb = 0; u32 rounds = 0; };      // rounds: summed over the rank ranges of a chunked run
+// Rank ranges of a chunked flatten (option flatten_chunks): K = want clamped to [1, min(z, FLATTEN_MAX_CHUNKS)] ranges of equal counts,
+// range k = [z k / K, z (k + 1) / K).  The pack that follows the ranges (encode_early_chunks) takes its bounds from the same two functions.
+constexpr u32 FLATTEN_MAX_CHUNKS = 16;
+inline u32 flatten_chunk_count(u32 want, size_t z) { return (u32)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(want, FLATTEN_MAX_CHUNKS), z)); }
+inline size_t flatten_chunk_start(size_t z, u32 k, u32 K) { return (size_t)((u64)z * k / K); }
 // a10: compressors/lzss/LZSSFactors.hpp:79-132 ; rewrites fs.fsrc in place.
 // `between` (optional) is called with r = 1, 2, ... once round r has been enqueued and before the host waits for its count, and with 0
 // when the rounds are over: the place for work that does not need the flattened sources (api_compress.hip runs the first half of the encoder
-// there, step by step on another stream).  Whatever it takes from the arena is gone when flatten_factors returns.
+// there, step by step on another stream), whatever range the round belongs to.  Whatever it takes from the arena is gone when flatten_factors returns.
 // rec_keep (optional, room for 16 bytes per factor): the records {pos, len, original source, final source} in position order are built
 // there and stay valid for the caller; fs.fsrc is NOT rewritten then.
-void flatten_factors(Ctx& c, size_t n, FactorSpace fs, FlattenStats* st, const std::function<void(int)>& between = {}, void* rec_keep = nullptr);
+// chunks: rank ranges the rounds run on one after the other (flatten.hip; 0: what option flatten_chunks forces, else one); chunk_done(k, r)
+// (optional) is called when the last round of range k is over, with c.stream behind it: the final sources of ranks < r stand in the records.
+void flatten_factors(Ctx& c, size_t n, FactorSpace fs, FlattenStats* st, const std::function<void(int)>& between = {}, void* rec_keep = nullptr,
+                     u32 chunks = 0, const std::function<void(u32, size_t)>& chunk_done = {});
 
 // a9: extract the factor list sorted by pos (LZSSFactors.hpp:69-76): pos[], src[], len[] (z entries each,
 // arrays caller-provided with capacity cap).  Returns z.
@@ -178,6 +186,16 @@ void* encode_early_rec(EncodeEarly* e);
 // Only the last one waits for the device if the steps are spread over time (their read-backs travel through the mapped host area).
 void encode_early_run(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder, EncodeEarly* e, bool finish = true);
 void encode_early_free(EncodeEarly* e);
+// Pack and download behind the rank ranges of a chunked flatten (K >= 2 ranges of fs.nfact factors; call it between _reserve and
+// flatten_factors).  false: this call does not overlap pack and download (no host buffer of the caller's, a text of fewer than
+// 64 * PACK_CH tiles, no records, no second side stream) -- nothing was taken, flatten in one range.  true: the output buffer is reserved
+// (encode_early_out), the pack's chunks end at the tiles that hold the first factor of every range, and encode_early_chunk_done -- from
+// flatten_factors' chunk_done, c.stream being the compute stream -- packs the tiles in front of range k + 1 on the copy stream and sends
+// their bytes to the host on the aux stream, as soon as the first half's results are there; encode_stream does what is left.
+bool encode_early_chunks(Ctx& c, size_t n, const FactorSpace& fs, EncodeEarly* e, u32 K, size_t out_cap);
+void encode_early_chunk_done(Ctx& c, const u8* text, size_t n, const FactorSpace& fs, EncodeEarly* e, u32 k);
+u8* encode_early_out(EncodeEarly* e, size_t* out_cap);      // the buffer encode_early_chunks reserved and its size (NULL: none, *out_cap untouched)
+u32 encode_early_packed(const EncodeEarly* e);              // ranges whose pack has been enqueued so far
 
 // worst-case output size of encode_huff for a text of n bytes
 size_t encode_bound(size_t n);
