@@ -367,7 +367,7 @@ int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len
 int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
                               uint32_t* lf, uint64_t* heads, uint32_t* launches);
 
-/* ---- rle, mtf, encode(huff) and chains of them behind bwt: the reference's `bwtzip = bwt:rle:mtf:encode(huff)`
+/* ---- rle, mtf, encode(huff), encode(sle) and chains of them behind bwt: the reference's `bwtzip = bwt:rle:mtf:encode(huff)`
  * (etc/compare-suites/default.suite).  A pipeline is a sequence of 1 .. 8 stages; every stage's whole output is the
  * next stage's input (tudocomp_driver/ChainCompressor.hpp: `a:b:c` = chain(chain(a, b), c)) and stays in device memory, only the last
  * one is downloaded.  One stage alone is a valid pipeline: that is how the three single compressors are reached.
@@ -380,11 +380,17 @@ int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, 
  *                       in mid-stream, which the reference's decoder decodes.
  *   TDC_GPU_STAGE_MTF   MTFCompressor::compress (compressors/MTFCompressor.hpp:16-33): move-to-front ranks, list 0 .. 255 at the start.
  *   TDC_GPU_STAGE_HUFF  LiteralEncoder<HuffmanCoder>::compress (compressors/LiteralEncoder.hpp:23-32): the algorithm `encode(huff)`.
+ *   TDC_GPU_STAGE_SLE   LiteralEncoder<SLECoder>::compress (the same with coders/SLECoder.hpp): the algorithm `encode(sle)`, param = its
+ *                       option `kmer`: 1 .. 7, 0 means the reference's default 3.  The stream is the ranking -- the bytes and the eta most
+ *                       frequent k-byte windows of the input in Counter::getSorted order --, one class code per symbol (a k-mer symbol stands
+ *                       for k bytes) and the bit stream's terminator.  The k-mer count of kmer 4 .. 7 sorts the
+ *                       windows of the whole input: about 38 bytes of arena per input byte, TDC_GPU_ERR_OOM before anything is written if the
+ *                       device cannot hold that.
  * Inputs of up to 2^32 - 2 bytes (bwt: < 2^31 - 1); a stage whose output would be longer fails with TDC_GPU_ERR_TOO_LARGE before it writes.
- * 0 or more than 8 stages, an unknown kind, bwt behind the first stage, an rle offset above 2^62: TDC_GPU_ERR_ARG. */
-enum { TDC_GPU_STAGE_BWT = 0, TDC_GPU_STAGE_RLE = 1, TDC_GPU_STAGE_MTF = 2, TDC_GPU_STAGE_HUFF = 3 };
+ * 0 or more than 8 stages, an unknown kind, bwt behind the first stage, an rle offset above 2^62, a kmer above 7: TDC_GPU_ERR_ARG. */
+enum { TDC_GPU_STAGE_BWT = 0, TDC_GPU_STAGE_RLE = 1, TDC_GPU_STAGE_MTF = 2, TDC_GPU_STAGE_HUFF = 3, TDC_GPU_STAGE_SLE = 4 };
 #define TDC_GPU_PIPELINE_MAX_STAGES 8
-typedef struct { int kind; uint64_t param; } tdc_gpu_stage;      /* param: rle offset, 0 for the other kinds */
+typedef struct { int kind; uint64_t param; } tdc_gpu_stage;      /* param: rle offset, sle kmer, 0 for the other kinds */
 /* worst-case output length of the pipeline on n input bytes (what an _into buffer needs at most); 0 for an invalid pipeline or one
  * whose worst case passes 2^32 - 2 bytes */
 size_t tdc_gpu_pipeline_bound(const tdc_gpu_stage* stages, int nstages, size_t n);
@@ -396,7 +402,7 @@ int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
  * on the copy stream (page-locked memory -- tdc_gpu_host_alloc -- receives it at the host link's rate). */
 int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
                                    size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
-/* Inverse, stage by stage from the last one, on the device: one upload of the stream, the decoders of rle, mtf and encode(huff)
+/* Inverse, stage by stage from the last one, on the device: one upload of the stream, the decoders of rle, mtf, encode(huff) and encode(sle)
  * (csrc/bytestages_decode.hip) and the inverse of a leading bwt work from buffer to buffer in the arena, one download (*out then holds the
  * escaped, 0-terminated text if the pipeline starts with bwt).  Option dec_parse picks the path once per call from the stream's length:
  * 1 (default) = the device for streams of 1 MiB and more, 2 = the device for every stream, 0 = the host loops below, which are the
@@ -418,6 +424,13 @@ int tdc_gpu_pipeline_decompress_stats(tdc_gpu_ctx* ctx, const tdc_gpu_stage* sta
 int tdc_rle_decode(const uint8_t* in, size_t len, uint64_t offset, uint8_t* out, size_t out_cap, size_t* out_len);
 int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
 int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len);
+/* The same contract for LiteralEncoder::decompress with SLECoder::Decoder (coders/SLECoder.hpp:311-416), kmer as TDC_GPU_STAGE_SLE's
+ * param: the specification of the device decoder of encode(sle), the host path of the pipeline calls and the path for small streams.
+ * TDC_GPU_ERR_ARG for: a kmer above 7, an empty stream, a ranking that does not end inside the stream, a ranking of more than 1024
+ * symbols, a ranking entry that is neither a byte nor a k-mer of this kmer (marker byte 0xFF, zero bytes between the marker and the k
+ * bytes), a rank outside the ranking (the reference reads out of bounds there), a code cut off by the end of the stream (the reference
+ * reads zeros there).  TDC_GPU_ERR_TOO_LARGE for a text of more than 2^32 - 2 bytes. */
+int tdc_sle_decode(const uint8_t* in, size_t len, uint32_t kmer, uint8_t* out, size_t out_cap, size_t* out_len);
 /* The same contract for LZWCompressor::decompress (lzw::decode_step restated; coder TDC_GPU_CODER_BIT or TDC_GPU_CODER_GAMMA, else
  * TDC_GPU_ERR_UNSUPPORTED): the specification of tdc_gpu_lzw_decompress and its path for small streams.  TDC_GPU_ERR_ARG for what that
  * call refuses, TDC_GPU_ERR_TOO_LARGE for a text of more than 2^32 - 2 bytes. */

@@ -26,6 +26,7 @@ STAGE_BWT = 0            # stages of a pipeline (tdc_gpu_stage.kind): a stage is
 STAGE_RLE = 1
 STAGE_MTF = 2
 STAGE_HUFF = 3
+STAGE_SLE = 4            # encode(sle): STAGE_SLE or (STAGE_SLE, kmer), kmer 1 .. 7 (0 = the reference's default 3)
 
 
 class TdcGpuError(RuntimeError):
@@ -176,6 +177,11 @@ def mtf_decode(data):
 def huff_decode_literals(data):
     """LiteralEncoder<HuffmanCoder>::decompress (compressors/LiteralEncoder.hpp:34-41) on the host"""
     return _host_decode("tdc_huff_decode_literals", data)
+
+
+def sle_decode_literals(data, kmer=3):
+    """LiteralEncoder<SLECoder>::decompress (compressors/LiteralEncoder.hpp:34-41, coders/SLECoder.hpp:311-416) on the host"""
+    return _host_decode("tdc_sle_decode", data, ctypes.c_uint32(int(kmer)))
 
 
 def lzw_decode(data, coder=CODER_BIT):
@@ -834,11 +840,12 @@ class BWTCompressor:
 
 def parse_chain(spec):
     """`a:b:c` (util/algorithm_parser/AlgorithmAST.hpp:119-129: chain(chain(a, b), c)) -> stage list; a, b, c out of bwt, rle,
-    rle(offset=N), mtf, encode(huff)"""
+    rle(offset=N), mtf, encode(huff), encode(sle), encode(sle(kmer=K)), encode(coder=sle(kmer=K))"""
     import re
     stages = []
     for part in str(spec).replace(" ", "").split(":"):
         m = re.fullmatch(r"rle(?:\((?:offset=(\d+))?\))?", part)
+        sle = re.fullmatch(r"encode\((?:coder=)?sle(?:\((?:kmer=(-?\d+))?\))?\)", part)
         if m:
             stages.append((STAGE_RLE, int(m.group(1) or 0)))
         elif part in ("bwt", "bwt()"):
@@ -847,13 +854,18 @@ def parse_chain(spec):
             stages.append((STAGE_MTF, 0))
         elif part in ("encode(huff)", "encode(coder=huff)", "encode"):
             stages.append((STAGE_HUFF, 0))
+        elif sle:
+            kmer = sle.group(1)
+            if kmer is not None and not 1 <= int(kmer) <= 7:
+                raise RuntimeError("sle: kmer must be in 1..7, not %s" % kmer)
+            stages.append((STAGE_SLE, int(kmer or 3)))
         else:
             raise RuntimeError("No implementation found for compressor %s" % part)
     return stages
 
 
 class ChainCompressor:
-    """Mirror of tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) for chains of bwt, rle, mtf and encode(huff), e.g. the
+    """Mirror of tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) for chains of bwt, rle, mtf, encode(huff) and encode(sle), e.g. the
     reference's bwtzip = "bwt:rle:mtf:encode(huff)": every stage's whole output is the next stage's input, on the device.  Only a
     leading bwt has input restrictions: its input is escaped + 0-terminated, and unescaped again on the way back."""
 
@@ -889,12 +901,20 @@ class MTFCompressor(ChainCompressor):
 
 
 class LiteralEncoder(ChainCompressor):
-    """Mirror of tdc::LiteralEncoder<coder> (compressors/LiteralEncoder.hpp:11-42), the algorithm `encode(coder)`; coder huff only"""
+    """Mirror of tdc::LiteralEncoder<coder> (compressors/LiteralEncoder.hpp:11-42), the algorithm `encode(coder)`; coder huff, or sle
+    with its option kmer (1 .. 7).  dec="gpu": decompress() through the pipeline (the device for streams of 1 MiB and more, option
+    dec_parse); dec="host": the host loop, which needs no context."""
 
-    def __init__(self, ctx, coder="huff"):
-        if coder != "huff":
-            raise RuntimeError("No implementation found for compressor encode(coder=%s)" % coder)
-        ChainCompressor.__init__(self, ctx, "encode(huff)")
+    def __init__(self, ctx, coder="huff", kmer=3, dec="gpu"):
+        if coder not in ("huff", "sle") or dec not in ("gpu", "host"):
+            raise RuntimeError("No implementation found for compressor encode(coder=%s, dec=%s)" % (coder, dec))
+        self.coder, self.kmer, self.dec = coder, int(kmer), dec
+        ChainCompressor.__init__(self, ctx, "encode(huff)" if coder == "huff" else "encode(sle(kmer=%d))" % int(kmer))
+
+    def decompress(self, stream):
+        if self.dec == "host":
+            return huff_decode_literals(stream) if self.coder == "huff" else sle_decode_literals(stream, self.kmer)
+        return ChainCompressor.decompress(self, stream)
 
 
 class LZ78Compressor:

@@ -32,7 +32,7 @@ SYMBOLS = [
     "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
     "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
     "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
-    "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals",
+    "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals", "tdc_sle_decode",
     "tdc_gpu_lzw_compress", "tdc_gpu_lzw_decompress", "tdc_gpu_lzw_decompress_into", "tdc_lzw_factors", "tdc_lzw_decode",
     "tdc_gpu_lzss_lcp_compress_into", "tdc_gpu_lzss_lcp_bound", "tdc_gpu_lzss_lcp_decompress", "tdc_gpu_lzss_lcp_decompress_into", "tdc_lzss_decode",
 ]
@@ -61,7 +61,7 @@ class Stats(ctypes.Structure):
 
 
 class Stage(ctypes.Structure):
-    """tdc_gpu_stage: kind (STAGE_BWT / _RLE / _MTF / _HUFF) and param (the rle offset)"""
+    """tdc_gpu_stage: kind (STAGE_BWT / _RLE / _MTF / _HUFF / _SLE) and param (the rle offset, the sle kmer)"""
     _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_uint64)]
 
 
@@ -163,6 +163,7 @@ def load():
     L.tdc_rle_decode.argtypes = [vp, sz, ctypes.c_uint64, vp, sz, psz]
     L.tdc_mtf_decode.argtypes = [vp, sz, vp, sz, psz]
     L.tdc_huff_decode_literals.argtypes = [vp, sz, vp, sz, psz]
+    L.tdc_sle_decode.argtypes = [vp, sz, ctypes.c_uint32, vp, sz, psz]
     L.tdc_gpu_lcpcomp_decompress_coder.argtypes = [vp, vp, sz, ctypes.c_int, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_encode_arith.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]
     L.tdc_gpu_encode_ascii.argtypes = [vp, vp, sz, vp, vp, vp, sz, pvp, psz]

@@ -1,5 +1,6 @@
-// api_chain.hip -- C ABI (include/tdc_gpu.h): bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip), the byte stages rle, mtf and encode(huff)
-// (bytestages.hip, bytestages_decode.hip) and chains of them, with the host decoders of the byte stages.
+// api_chain.hip -- C ABI (include/tdc_gpu.h): bwt (BWTCompressor.hpp, ds/bwt.hpp; bwt.hip), the byte stages rle, mtf, encode(huff) and
+// encode(sle) (bytestages.hip, encode.hip, bytestages_decode.hip) and chains of them (DESIGN.md sections 5.3 and 5.6), with the host
+// decoders of the byte stages.
 #include "api.hpp"
 #include "bytestages.hpp"
 #include "../host/tdc_coders.hpp"
@@ -122,19 +123,27 @@ namespace {
 bool pipeline_valid(const tdc_gpu_stage* st, int k) {
     if (!st || k < 1 || k > TDC_GPU_PIPELINE_MAX_STAGES) return false;
     for (int i = 0; i < k; ++i) {
-        if (st[i].kind < TDC_GPU_STAGE_BWT || st[i].kind > TDC_GPU_STAGE_HUFF) return false;
+        if (st[i].kind < TDC_GPU_STAGE_BWT || st[i].kind > TDC_GPU_STAGE_SLE) return false;
         if (st[i].kind == TDC_GPU_STAGE_BWT && i) return false;
         if (st[i].kind == TDC_GPU_STAGE_RLE && st[i].param > ((u64)1 << 62)) return false;
+        if (st[i].kind == TDC_GPU_STAGE_SLE && st[i].param > 7) return false;               // kmer: 0 = 3 (SLECoder.hpp:12,38)
     }
     return true;
 }
 // worst-case output of one stage on n bytes
 u64 stage_worst(const tdc_gpu_stage& st, u64 n) {
-    return st.kind == TDC_GPU_STAGE_RLE ? rle_bound(n, st.param) : st.kind == TDC_GPU_STAGE_HUFF ? huff_literals_bound(n) : n;
+    return st.kind == TDC_GPU_STAGE_RLE ? rle_bound(n, st.param) : st.kind == TDC_GPU_STAGE_HUFF ? huff_literals_bound(n) :
+           st.kind == TDC_GPU_STAGE_SLE ? sle_literals_bound(n) : n;
+}
+// the scratch it takes besides
+u64 stage_scratch(const tdc_gpu_stage& st, u64 n) {
+    return st.kind == TDC_GPU_STAGE_SLE ? sle_literals_scratch_bound(n, st.param ? (u32)st.param : 3u) : stage_scratch_bound(n);
 }
 // what the arena holds for it (a stage that would write more than STAGE_MAX_BYTES fails before it writes)
 u64 stage_bound(const tdc_gpu_stage& st, u64 n) { return std::min<u64>(stage_worst(st, n), STAGE_MAX_BYTES); }
-const char* stage_name(int kind) { return kind == TDC_GPU_STAGE_BWT ? "bwt" : kind == TDC_GPU_STAGE_RLE ? "rle" : kind == TDC_GPU_STAGE_MTF ? "mtf" : "encode(huff)"; }
+const char* stage_name(int kind) {
+    return kind == TDC_GPU_STAGE_BWT ? "bwt" : kind == TDC_GPU_STAGE_RLE ? "rle" : kind == TDC_GPU_STAGE_MTF ? "mtf" : kind == TDC_GPU_STAGE_SLE ? "encode(sle)" : "encode(huff)";
+}
 
 
 void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t n, Sink s, tdc_gpu_stats* stats) {
@@ -142,7 +151,7 @@ void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k
     if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
     if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
         for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage (its input is the escaped, 0-terminated view)"};
-    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle (offset <= 2^62), mtf or encode(huff)"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle (offset <= 2^62), mtf, encode(huff) or encode(sle) (kmer 1 .. 7)"};
     if (n > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the input must not be longer than 2^32 - 2 bytes"};
     const bool lead_bwt = stages[0].kind == TDC_GPU_STAGE_BWT;
     Ctx& c = ctx->c;
@@ -159,7 +168,7 @@ void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k
     };
     // the arena for the whole call: what the suffix array needs, or every intermediate at its worst case with the stages' scratch
     u64 need = 0, len = n;
-    for (int i = lead_bwt ? 1 : 0; i < k; ++i) { need += stage_scratch_bound(len) + stage_bound(stages[i], len) + 4096; len = stage_bound(stages[i], len); }
+    for (int i = lead_bwt ? 1 : 0; i < k; ++i) { need += stage_scratch(stages[i], len) + stage_bound(stages[i], len) + 4096; len = stage_bound(stages[i], len); }
     need += n + 4096;
     if (lead_bwt) {
         check_text_args(in, n);                               // (before the arena is sized from n)
@@ -188,6 +197,7 @@ void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k
                 }
                 case TDC_GPU_STAGE_RLE: cur = rle_encode_device(c, cur.d, cur.len, stages[i].param); break;
                 case TDC_GPU_STAGE_MTF: cur = mtf_encode_device(c, cur.d, cur.len); break;
+                case TDC_GPU_STAGE_SLE: cur = sle_literals_device(c, cur.d, cur.len, (u32)stages[i].param); break;
                 default: cur = huff_literals_device(c, cur.d, cur.len); break;
             }
         } catch (const StageTooLarge&) {
@@ -228,6 +238,7 @@ void host_stage_decode(const tdc_gpu_stage& st, const std::vector<uint8_t>& in, 
         tdc_amd::ByteSink sink(o, cap);
         if (st.kind == TDC_GPU_STAGE_RLE) tdc_amd::rle_decode(in.data(), in.size(), st.param, sink);
         else if (st.kind == TDC_GPU_STAGE_MTF) tdc_amd::mtf_decode(in.data(), in.size(), sink);
+        else if (st.kind == TDC_GPU_STAGE_SLE) tdc_amd::sle_decode_literals(in.data(), in.size(), st.param ? (unsigned)st.param : 3u, sink);
         else tdc_amd::huff_decode_literals(in.data(), in.size(), sink);
         return sink.n;
     };
@@ -241,6 +252,8 @@ void host_stage_decode(const tdc_gpu_stage& st, const std::vector<uint8_t>& in, 
         run(out.data(), out.size());
     } catch (const std::runtime_error&) {
         throw ArgError{TDC_GPU_ERR_ARG, "pipeline: malformed stream"};
+    } catch (const std::length_error&) {                          // (sle_decode_literals)
+        throw ArgError{TDC_GPU_ERR_ARG, "pipeline: a stage decodes to more than 2^32 - 2 bytes"};
     }
 }
 
@@ -336,6 +349,7 @@ bool pipeline_decompress_device(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, i
                     switch (stages[i].kind) {
                         case TDC_GPU_STAGE_RLE: cur = rle_decode_device(c, cur.d, (size_t)cur.len, stages[i].param); break;
                         case TDC_GPU_STAGE_MTF: cur = mtf_decode_device(c, cur.d, (size_t)cur.len); break;
+                        case TDC_GPU_STAGE_SLE: cur = sle_decode_device(c, cur.d, (size_t)cur.len, (u32)stages[i].param); break;
                         default: cur = huff_decode_device(c, cur.d, (size_t)cur.len); break;
                     }
                 } catch (const StageHostOnly&) {                 // this one stage through its host loop
@@ -400,7 +414,7 @@ void pipeline_decompress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
     sink_check(s, "NULL argument");
     if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
         for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage"};
-    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf or encode(huff)"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle, mtf, encode(huff) or encode(sle) (kmer 1 .. 7)"};
     if (len > STAGE_MAX_BYTES) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline: the stream must not be longer than 2^32 - 2 bytes"};
     Ctx& c = ctx->c;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -481,6 +495,10 @@ int tdc_mtf_decode(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, 
 }
 int tdc_huff_decode_literals(const uint8_t* in, size_t len, uint8_t* out, size_t out_cap, size_t* out_len) {
     return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::huff_decode_literals(in, len, s); });
+}
+int tdc_sle_decode(const uint8_t* in, size_t len, uint32_t kmer, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (kmer > 7) return TDC_GPU_ERR_ARG;
+    return host_decode_entry(in, len, out, out_cap, out_len, [&](tdc_amd::ByteSink& s) { tdc_amd::sle_decode_literals(in, len, kmer ? kmer : 3u, s); });
 }
 int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
     if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) return TDC_GPU_ERR_UNSUPPORTED;

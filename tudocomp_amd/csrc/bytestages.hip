@@ -352,6 +352,7 @@ u64 rle_bound(u64 n, u64 offset) { return n ? 1 + (n - 1) * (u64)(1 + vbyte_len(
 // a code is at most 64 bits long (the packer's word; 2^32 symbols reach 46), the header at most 2 + 2 * 256 + 256 + 4 bytes
 u64 huff_literals_bound(u64 n) { return 8 * n + 1024; }
 // tile tables of 8 bytes per 4096, or mtf's rows: 2 x 256 bytes per chunk of 1024 and their counts, the levels above, the tile lists
+// (encode(sle) states its own: sle_literals_scratch_bound in encode.hip -- up to 38 bytes per input byte for the k-mer count at k = 7)
 u64 stage_scratch_bound(u64 n) { return n / 2 + n / 64 + ((u64)1 << 20); }
 
 StageOut rle_encode_device(Ctx& c, const u8* d_in, size_t n, u64 offset) {

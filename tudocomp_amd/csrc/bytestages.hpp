@@ -3,6 +3,8 @@
 //   rle           compressors/RunLengthEncoder.hpp:15-32 + util/vbyte.hpp:28-37
 //   mtf           compressors/MTFCompressor.hpp:16-33
 //   encode(huff)  compressors/LiteralEncoder.hpp:23-32 with coders/HuffmanCoder.hpp
+//   encode(sle)   compressors/LiteralEncoder.hpp:23-32 with coders/SLECoder.hpp (encode.hip, next to lcpcomp's SLE encoder whose
+//                 count, selection, fill scan and class codes it shares)
 // Every function reads a device buffer of n bytes (n <= 2^32 - 2, at least 16 readable bytes behind it), takes its output buffer from
 // the arena once the output length is known, and enqueues on c.stream.  An output of more than 2^32 - 2 bytes: StageTooLarge, thrown
 // before anything of it is written.
@@ -25,13 +27,16 @@ constexpr u32 HUFF_PER_THREAD = 16, HUFF_TILE = 256 * HUFF_PER_THREAD;
 // worst-case output lengths (64-bit: they may pass STAGE_MAX_BYTES)
 u64 rle_bound(u64 n, u64 offset);
 u64 huff_literals_bound(u64 n);
-// device scratch a stage takes from the arena besides its output
+u64 sle_literals_bound(u64 n);
+// device scratch a stage takes from the arena besides its output: rle, mtf and encode(huff); encode(sle) with its k-mer count
 u64 stage_scratch_bound(u64 n);
+u64 sle_literals_scratch_bound(u64 n, u32 kmer);
 
 struct StageOut { u8* d = nullptr; u64 len = 0; };
 StageOut rle_encode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
 StageOut mtf_encode_device(Ctx& c, const u8* d_in, size_t n);
 StageOut huff_literals_device(Ctx& c, const u8* d_in, size_t n);
+StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 kmer);      // kmer 0 = 3; 1 .. 7
 
 // The decoders (bytestages_decode.hip): the host loops of host/tdc_coders.hpp are their specification, including what they refuse.
 // d_in: n bytes in the arena (256-byte aligned, 64 allocated bytes behind them).  The output comes from the bottom of the arena, scratch
@@ -44,5 +49,6 @@ u64 stage_decode_scratch_bound(u64 n, u64 out);
 StageOut rle_decode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
 StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n);
 StageOut huff_decode_device(Ctx& c, const u8* d_in, size_t n);
+StageOut sle_decode_device(Ctx& c, const u8* d_in, size_t n, u32 kmer);
 
 }  // namespace tdc

@@ -1,5 +1,5 @@
-// bytestages_decode.hip -- the decoders of rle, mtf and encode(huff) on the device.  The host loops of
-// host/tdc_coders.hpp (rle_decode, mtf_decode, huff_decode_literals) are the specification, including what they refuse.
+// bytestages_decode.hip -- the decoders of rle, mtf, encode(huff) and encode(sle) on the device.  The host loops of
+// host/tdc_coders.hpp (rle_decode, mtf_decode, huff_decode_literals, sle_decode_literals) are the specification, including what they refuse.
 //   mtf:  the moves of a chunk of ranks do not depend on what the list holds.  Run on the identity list, a chunk of 1 KiB yields its
 //         permutation (the list it leaves behind, 256 bytes) and for every rank the index into the list the chunk STARTS from.
 //         Permutations compose associatively, (a o b)[j] = a[b[j]]: reduced over groups of 256 on three levels, brought back down as the
@@ -7,6 +7,8 @@
 //   huff: next(x) = x + length of the code at bit x.  A chain can enter a tile of 2048 bit positions only within the first `longest`
 //         offsets: per tile "where does the chain that enters at offset o leave" (computed in LDS), composed over groups of 512 tiles on
 //         three levels, every tile gets its entry, then codes per tile -> 64-bit scan -> one byte per code.  No per-bit array in HBM.
+//   sle:  encode(sle) is a prefix code as well, and the length of a code follows from its first three bits: the tile scheme of huff
+//         without a table in the exit pass; a code stands for 1 or k bytes, so the count pass adds up bytes, not codes.
 //   rle:  the parse carries one bit of state ("this data byte equals the previous data byte": a vbyte follows), a token is at most 1 + 10
 //         bytes long: the same tile scheme with the 2 x 11 states (offset, eq).  Run lengths -> 64-bit scan; every token writes its bytes
 //         up to the next 256-byte border of the output itself and leaves (end, byte) at the first border it covers; a maximum scan over
@@ -341,6 +343,88 @@ int hd_parse_header(const u8* pre, size_t pre_len, bool whole, u64 total, HuffDe
     return 2;
 }
 
+// ---- encode(sle) ------------------------------------------------------------------------------------------------------------------------
+// A pure prefix-code stream behind the ranking: the length of a code follows from its first three bits and sigma_bits
+// (tdc_amd::sle_code_len), so next(x) needs no table; a rank stands for 1 or k bytes.  The tile scheme of encode(huff) with the same
+// tile and chunk sizes; the states are the first LA = longest code (at most 13) offsets of a tile.
+struct SleDecTab {
+    u64 ent[tdc_amd::SLE_MAX_SIGMA];                         // rank -> its bytes (first byte most significant) | their number << 56
+    u32 sigma, sb, pad0, pad1;
+};
+static_assert(sizeof(SleDecTab) % 4 == 0, "copied word by word");
+
+__global__ void __launch_bounds__(256) sd_exit_kernel(const u32* __restrict__ s32, u64 nw32, u64 hb, u64 total, u32 sb, u32 LA, u32 nchunks, u32 ntiles,
+                                                      u16* __restrict__ exit0) {
+    __shared__ u32 sw[HD_CH / 32 + 16];
+    __shared__ u8 nxl[HD_CH];                                  // next(x) - x; 0: the code at x is cut off by the end of the stream
+    for (u32 chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        __syncthreads();
+        const u64 a0 = hb + (u64)chunk * HD_CH;
+        const u64 kb = a0 >> 5;
+        for (u32 k = threadIdx.x; k < HD_CH / 32 + 16; k += 256) sw[k] = kb + k < nw32 ? __builtin_bswap32(s32[kb + k]) : 0u;
+        __syncthreads();
+        const BitWin bw{sw, kb, total};
+        for (u32 i = threadIdx.x; i < HD_CH; i += 256) {
+            u32 d = 0;
+            if (a0 + i < total) {
+                d = tdc_amd::sle_code_len(sb, (u32)(bw.peek(a0 + i) >> 61));
+                if (a0 + i + d > total) d = 0;
+            }
+            nxl[i] = (u8)d;
+        }
+        __syncthreads();
+        constexpr u32 TPW = HD_CH / HD_T;
+        for (u32 w = threadIdx.x; w < TPW * LA; w += 256) {
+            const u32 tt = w / LA, o = w - tt * LA;
+            const u32 tile = chunk * TPW + tt;
+            if (tile >= ntiles) continue;
+            const u32 tend = (tt + 1) * HD_T;
+            u32 e = tt * HD_T + o, res = DX_NONE;
+            for (u32 guard = 0; guard <= HD_T; ++guard) {
+                if (e >= tend) { res = e - tend; break; }
+                const u32 d = nxl[e];
+                if (!d) break;
+                e += d;
+            }
+            exit0[(size_t)tile * LA + o] = (u16)res;
+        }
+    }
+}
+
+// the codes of every tile from its entry: EMIT = false adds up the bytes they stand for (tcount[t]; *err |= 1 for a code that is cut off
+// or whose rank lies outside the ranking), EMIT = true: tcount[] holds the exclusive sums, 1 or k bytes per code
+template <bool EMIT>
+__global__ void __launch_bounds__(256) sd_walk_kernel(const u32* __restrict__ s32, u64 hb, u64 total, const SleDecTab* __restrict__ gT,
+                                                      const u16* __restrict__ tile_entry, u32 ntiles, u64* __restrict__ tcount, u8* __restrict__ out,
+                                                      u32* __restrict__ err) {
+    __shared__ SleDecTab T;
+    for (u32 k = threadIdx.x; k < sizeof(SleDecTab) / 4; k += blockDim.x) ((u32*)&T)[k] = ((const u32*)gT)[k];
+    __syncthreads();
+    const BitWinG bw{s32, total};
+    const u32 sb = T.sb, sigma = T.sigma;
+    for (u32 t = blockIdx.x * 256 + threadIdx.x; t < ntiles; t += gridDim.x * 256) {
+        const u32 e = tile_entry[t];
+        u64 cnt = 0;
+        if (e != DX_NONE) {
+            u64 x = hb + (u64)t * HD_T + e;
+            const u64 tile_end = min(hb + (u64)(t + 1) * HD_T, total);
+            u8* dst = EMIT ? out + tcount[t] : nullptr;
+            for (u32 guard = 0; x < tile_end && guard <= HD_T; ++guard) {
+                const u64 w = bw.peek(x);
+                const u32 d = tdc_amd::sle_code_len(sb, (u32)(w >> 61));
+                const u32 rank = tdc_amd::sle_code_rank(sb, d, (u32)(w >> (64 - d)));
+                if (x + d > total || rank >= sigma) { if (!EMIT) atomicOr(err, 1u); break; }
+                const u64 ent = T.ent[rank];
+                const u32 m = (u32)(ent >> 56);
+                if (EMIT) for (u32 j = 0; j < m; ++j) dst[cnt + j] = (u8)(ent >> (8 * (m - 1 - j)));
+                cnt += m;
+                x += d;
+            }
+        }
+        if (!EMIT) tcount[t] = cnt;
+    }
+}
+
 // ---- rle --------------------------------------------------------------------------------------------------------------------------------
 constexpr u32 RLD_T = 512;                  // input bytes per tile
 constexpr u32 RLD_TOK = 11;                 // longest token: the data byte and a vbyte of ten
@@ -468,7 +552,8 @@ __global__ void __launch_bounds__(256) rld_fill_kernel(const u32* __restrict__ h
 
 }  // namespace
 
-// rows of 256 bytes per chunk and their lists, the levels above; tile tables of huff (<= 2 x 255 + 10 bytes per 2048 bits) and rle
+// rows of 256 bytes per chunk and their lists, the levels above; tile tables of huff (<= 2 x 255 + 10 bytes per 2048 bits), sle (2 x 13 + 10)
+// and rle
 u64 stage_decode_scratch_bound(u64 n, u64 out) { return n / 2 + n / 8 + out / 16 + ((u64)4 << 20); }
 
 StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n) {
@@ -552,6 +637,54 @@ StageOut huff_decode_device(Ctx& c, const u8* d_in, size_t n) {
     if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
     r.d = stage_out(c, r.len);
     hd_walk_kernel<true><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, r.d, d_err);
+    LAUNCH_CHECK();
+    return r;
+}
+
+StageOut sle_decode_device(Ctx& c, const u8* d_in, size_t n, u32 kmer) {
+    const StreamFormatError bad{"pipeline: malformed stream"};
+    if (!n) throw bad;
+    if (kmer == 0) kmer = 3;
+    hipStream_t s = c.stream;
+    constexpr size_t PRE = 16384;                               // the longest ranking tdc_amd::sle_parse_ranking accepts ends in front of it
+    static_assert(PRE >= tdc_amd::SLE_MAX_HEADER_BYTES + 16, "the ranking is parsed from the first PRE bytes");
+    std::vector<u8> pre(std::min(n, PRE));
+    u8 last = 0;
+    HIP_TRY(hipMemcpyAsync(pre.data(), d_in, pre.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&last, d_in + n - 1, 1, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    tdc_amd::SleRanking R;
+    try { tdc_amd::sle_parse_ranking(pre.data(), pre.size(), tdc_amd::sle_total_bits(n, last), kmer, R); }
+    catch (const std::runtime_error&) { throw bad; }
+    const u64 total = R.total, hb = R.body;
+    const u32* s32 = (const u32*)d_in;                          // (arena allocations are 256-byte aligned, 64 bytes of slack behind n)
+    StageOut r;
+    const u64 m = total - hb;
+    if (m == 0) { r.d = stage_out(c, 0); return r; }
+    std::vector<SleDecTab> tab(1);
+    memset(&tab[0], 0, sizeof(SleDecTab));
+    for (u32 i = 0; i < R.sigma; ++i) tab[0].ent[i] = R.ent[i];
+    tab[0].sigma = R.sigma; tab[0].sb = R.sb;
+    const u32 LA = tdc_amd::sle_code_len(R.sb, 7);              // the longest code
+    const u32 ntiles = cdiv(m, HD_T), nchunks = cdiv(m, HD_CH);
+    SleDecTab* d_tab = (SleDecTab*)c.arena.alloc_top(sizeof(SleDecTab));
+    u32* d_err = (u32*)c.arena.alloc_top(256);
+    u64* tcount = (u64*)c.arena.alloc_top(((size_t)ntiles + 1) * 8);
+    u16* exit0 = (u16*)c.arena.alloc_top((size_t)ntiles * LA * 2);
+    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(SleDecTab), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
+    sd_exit_kernel<<<std::min<u32>(nchunks, DEC_MAX_BLOCKS), 256, 0, s>>>(s32, ((u64)n + 60) / 4, hb, total, R.sb, LA, nchunks, ntiles, exit0);
+    LAUNCH_CHECK();
+    const u16* entry = dx_entries(c, exit0, ntiles, LA);
+    sd_walk_kernel<false><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, nullptr, d_err);
+    LAUNCH_CHECK();
+    exclusive_sum_u64(c, tcount, tcount, ntiles, tcount + ntiles);
+    const u32 err = c.read(d_err);                              // (synchronises: the table lives on this frame)
+    r.len = c.read(tcount + ntiles);
+    if (err) throw bad;
+    if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
+    r.d = stage_out(c, r.len);
+    sd_walk_kernel<true><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, r.d, d_err);
     LAUNCH_CHECK();
     return r;
 }

@@ -16,7 +16,11 @@
 //   covered, not start: nothing
 // Two tiled passes: (1) bits per 2048-position tile, exclusive scan of the tile sums (u64);
 // (2) recompute the costs, scan inside the workgroup, OR the bits into the zeroed output (big-endian 64-bit words).
+//
+// At the end of the file: encode(sle) = LiteralEncoder<SLECoder> as a byte stage (sle_literals_device, declared in bytestages.hpp),
+// the owner-less use of the SLE machinery below.
 #include "stages.hpp"
+#include "bytestages.hpp"
 #include "prim.hpp"
 #include "huffman_host.hpp"
 #include "arith.hpp"
@@ -938,23 +942,42 @@ __device__ __forceinline__ u64 sle_key(const u8* __restrict__ text, size_t p, u3
     return x;
 }
 
-// Encoder ctor :96-120: every k-mer window that lies inside one literal run is counted
+// Encoder ctor :96-120: every k-mer window that lies inside one literal run is counted.  OWNED = false (encode(sle), the whole text is
+// one literal run): owner[] is not read, here and in the kernels below.
+// A text's hot k-mers (English: a few trigrams hold a percent of the windows each) would serialise on their counters: every workgroup
+// counts the first SLE_CNT_SLOTS distinct keys it meets in LDS and adds those sums once; the others go to the table directly.
+constexpr u32 SLE_CNT_SLOTS = 4096;
+template <bool OWNED>
 __global__ __launch_bounds__(256) void sle_kmer_count_kernel(const u8* __restrict__ text, const u32* __restrict__ owner, size_t n, u32 k,
                                                               u32* __restrict__ cnt) {
+    __shared__ u32 ckey[SLE_CNT_SLOTS];
+    __shared__ u32 cval[SLE_CNT_SLOTS];
+    for (u32 i = threadIdx.x; i < SLE_CNT_SLOTS; i += blockDim.x) { ckey[i] = NONE32; cval[i] = 0; }      // (a key has at most 24 bits)
+    __syncthreads();
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x + (k - 1); p < n; p += stride) {
         bool ok = true;
-        for (u32 j = 0; j < k; ++j) ok = ok && owner[p - j] == NONE32;
-        if (ok) atomicAdd(&cnt[sle_key(text, p, k)], 1u);
+        if (OWNED) for (u32 j = 0; j < k; ++j) ok = ok && owner[p - j] == NONE32;
+        if (!ok) continue;
+        const u32 key = (u32)sle_key(text, p, k);
+        const u32 slot = (key * 2654435761u) >> 20;              // 12 bits
+        const u32 seen = atomicCAS(&ckey[slot], NONE32, key);
+        if (seen == NONE32 || seen == key) atomicAdd(&cval[slot], 1u);
+        else atomicAdd(&cnt[key], 1u);
     }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < SLE_CNT_SLOTS; i += blockDim.x) if (cval[i]) atomicAdd(&cnt[ckey[i]], cval[i]);
 }
-// k > 3 (no 256^k table): the windows themselves, to be sorted and run-length counted
+// k > 3 (no 256^k table): the windows themselves, to be sorted and run-length counted.  OWNED = false: window p lands at p - (k - 1),
+// nothing is selected and *d_count is not touched
+template <bool OWNED>
 __global__ __launch_bounds__(256) void sle_kmer_keys_kernel(const u8* __restrict__ text, const u32* __restrict__ owner, size_t n, u32 k,
                                                              u64* __restrict__ keys, u32* __restrict__ d_count) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t p0 = (size_t)blockIdx.x * blockDim.x + (k - 1); p0 < n; p0 += stride) {
         const size_t p = p0 + threadIdx.x;
         bool ok = p < n;
+        if (!OWNED) { if (ok) keys[p - (k - 1)] = sle_key(text, p, k); continue; }
         for (u32 j = 0; j < k && ok; ++j) ok = owner[p - j] == NONE32;
         const u64 m = __ballot(ok);
         if (m == 0) continue;
@@ -1000,6 +1023,7 @@ __global__ __launch_bounds__(256) void sle_kmer_compact_kernel(const u32* __rest
 }
 
 // per position: literal? is the k-mer ending here ranked (and which rank)?
+template <bool OWNED>
 __global__ __launch_bounds__(256) void sle_minfo_kernel(const u8* __restrict__ text, const u32* __restrict__ owner, size_t n, SleDev D,
                                                          u16* __restrict__ minfo) {
     __shared__ u64 kv[SLE_MAX_KMERS];
@@ -1009,7 +1033,7 @@ __global__ __launch_bounds__(256) void sle_minfo_kernel(const u8* __restrict__ t
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
         u16 v = 0;
-        if (owner[p] == NONE32) {
+        if (!OWNED || owner[p] == NONE32) {
             v = SLE_LIT;
             if (D.nk && p + 1 >= D.k) {
                 const u64 key = sle_key(text, p, D.k);
@@ -1200,19 +1224,52 @@ __global__ __launch_bounds__(256) void sle_stream_kernel(const u8* __restrict__ 
     sink.flush();
 }
 
-static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k, u8* d_out, size_t out_cap, EncodeStats* st) {
-    if (k == 0) k = 3;                                                       // option "kmer", SLECoder.hpp:38
-    if (k > 7) throw HipError{hipErrorInvalidValue, "sle: kmer must be in 1..7 (SLECoder.hpp:12)", -1};
-    hipStream_t s = c.stream;
-    const size_t mark = c.arena.mark();
-    EncPrelude pre;
-    encode_prelude(c, text, n, fs, pre);
-    const size_t z = pre.z;
+// encode(sle): every position is a literal, its cost is the symbol that starts there (nothing inside a fired k-mer)
+template <bool PACK>
+__global__ __launch_bounds__(256) void sle_lit_stream_kernel(const u8* __restrict__ text, const u16* __restrict__ minfo, size_t n, SleDev D,
+                                                              u64* __restrict__ tile_bits, u64 base_bits, u64* __restrict__ out) {
+    __shared__ u16 rank_byte[256];
+    __shared__ u32 sm[5];
+    rank_byte[threadIdx.x] = D.rank_byte[threadIdx.x];
+    __syncthreads();
+    const size_t p0 = (size_t)blockIdx.x * ENC_TILE + (size_t)threadIdx.x * ENC_PER_THREAD;
+    u64 code[ENC_PER_THREAD];
+    u32 clen[ENC_PER_THREAD];
+    u32 sum = 0;
+#pragma unroll
+    for (int j = 0; j < ENC_PER_THREAD; ++j) {
+        const size_t p = p0 + j;
+        code[j] = 0; clen[j] = 0;
+        if (p < n) { sle_literal(minfo, p, n, text[p], rank_byte, D, code[j], clen[j]); sum += clen[j]; }
+    }
+    if (!PACK) {
+        sum = wave_reduce_sum(sum);
+        if (lane_id() == 0) sm[wave_id()] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_bits[blockIdx.x] = (u64)sm[0] + sm[1] + sm[2] + sm[3];
+        return;
+    }
+    u32 total;
+    const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
+    if (p0 >= n) return;
+    BitSink sink;
+    sink.out = out;
+    sink.pos = base_bits + tile_bits[blockIdx.x] + excl;
+    sink.acc = 0;
+    sink.cnt = 0;
+#pragma unroll
+    for (int j = 0; j < ENC_PER_THREAD; ++j) sink.append(code[j], clen[j]);
+    sink.flush();
+}
 
-    // ---- alphabet (Encoder ctor :96-160) ---------------------------------------------------------------------
-    struct Ent { u64 sym, cnt; };
-    std::vector<Ent> alpha;
-    for (u32 ch = 0; ch < 256; ++ch) if (pre.hist[ch]) alpha.push_back({ (u64)ch, (u64)pre.hist[ch] });
+struct SleEnt { u64 sym, cnt; };
+
+// The alphabet (Encoder ctor :96-160): the bytes of `hist` and the eta most frequent k-mers of the literal runs, in rank order
+// (Counter::getSorted :44-57).  owner == nullptr: the whole text is one literal run.  Returns sigma_bits.
+static u32 sle_alphabet(Ctx& c, const u8* text, const u32* owner, size_t n, u32 k, const u32* hist, std::vector<SleEnt>& alpha) {
+    hipStream_t s = c.stream;
+    alpha.clear();
+    for (u32 ch = 0; ch < 256; ++ch) if (hist[ch]) alpha.push_back({ (u64)ch, (u64)hist[ch] });
     size_t sigma = alpha.size();
     u32 sb = bits_for(sigma - 1);
     if (k > 1) {
@@ -1228,7 +1285,8 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
             HIP_TRY(hipMemsetAsync(cnt, 0, tsize * sizeof(u32), s));
             if (n >= k) {
                 unsigned g = cdiv(n, 256 * 8); if (g > 8192) g = 8192; if (g == 0) g = 1;
-                sle_kmer_count_kernel<<<g, 256, 0, s>>>(text, plain_owner(fs), n, k, cnt);
+                if (owner) sle_kmer_count_kernel<true><<<g, 256, 0, s>>>(text, owner, n, k, cnt);
+                else sle_kmer_count_kernel<false><<<g, 256, 0, s>>>(text, nullptr, n, k, cnt);
                 LAUNCH_CHECK();
             }
             const size_t cap = std::min(tsize, n) + 64;
@@ -1254,10 +1312,11 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
             u32* vals[2] = { c.arena.get<u32>(n), c.arena.get<u32>(n) };
             {
                 unsigned g = cdiv(n, 256 * 8); if (g > 8192) g = 8192; if (g == 0) g = 1;
-                sle_kmer_keys_kernel<<<g, 256, 0, s>>>(text, plain_owner(fs), n, k, keys[0], d_count);
+                if (owner) sle_kmer_keys_kernel<true><<<g, 256, 0, s>>>(text, owner, n, k, keys[0], d_count);
+                else sle_kmer_keys_kernel<false><<<g, 256, 0, s>>>(text, nullptr, n, k, keys[0], d_count);
                 LAUNCH_CHECK();
             }
-            const size_t windows = c.read(d_count);
+            const size_t windows = owner ? (size_t)c.read(d_count) : n - (k - 1);
             if (windows) {
                 const int w = radix_sort_pairs_u64(c, keys, vals, windows, 0, 8 * (int)k);
                 u8* head = c.arena.get<u8>(windows);
@@ -1286,14 +1345,16 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
         sigma = alpha.size();
         sb = bits_for(sigma - 1);
     }
-    std::sort(alpha.begin(), alpha.end(), [](const Ent& a, const Ent& b) {     // Counter::getSorted :44-57 (a total order)
+    std::sort(alpha.begin(), alpha.end(), [](const SleEnt& a, const SleEnt& b) {     // Counter::getSorted :44-57 (a total order)
         return a.cnt != b.cnt ? a.cnt > b.cnt : a.sym < b.sym;
     });
-    HostBitWriter hw;
-    hw.write_compressed_int(sigma);                                           // :155-158
-    for (const Ent& e : alpha) hw.write_compressed_int(e.sym);
+    return sb;
+}
 
-    SleDev D;
+// The encoder's tables for an alphabet in rank order, the per-position marks (literal, ranked, rank) and, from the buffer-fill scan,
+// the fired positions: minfo[] (n + 8 entries, from the arena).  owner == nullptr: every position is a literal.
+static u16* sle_marks(Ctx& c, const u8* text, const u32* owner, size_t n, u32 k, u32 sb, const std::vector<SleEnt>& alpha, SleDev& D) {
+    hipStream_t s = c.stream;
     memset(&D, 0, sizeof(D));
     D.sb = sb; D.k = k;
     D.f0 = 0; D.f1 = 0;
@@ -1324,7 +1385,8 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
     u16* minfo = c.arena.get<u16>(n + 8);
     {
         unsigned g = cdiv(n, 256 * 8); if (g > 8192) g = 8192; if (g == 0) g = 1;
-        sle_minfo_kernel<<<g, 256, 0, s>>>(text, plain_owner(fs), n, D, minfo);
+        if (owner) sle_minfo_kernel<true><<<g, 256, 0, s>>>(text, owner, n, D, minfo);
+        else sle_minfo_kernel<false><<<g, 256, 0, s>>>(text, nullptr, n, D, minfo);
         LAUNCH_CHECK();
     }
     if (D.nk) {
@@ -1337,6 +1399,28 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
         sle_fire_kernel<<<tiles, 256, 0, s>>>(minfo, n, D, tile_in);
         LAUNCH_CHECK();
     }
+    HIP_TRY(hipStreamSynchronize(s));      // (the host tables of this frame are copied from)
+    return minfo;
+}
+
+static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k, u8* d_out, size_t out_cap, EncodeStats* st) {
+    if (k == 0) k = 3;                                                       // option "kmer", SLECoder.hpp:38
+    if (k > 7) throw HipError{hipErrorInvalidValue, "sle: kmer must be in 1..7 (SLECoder.hpp:12)", -1};
+    hipStream_t s = c.stream;
+    const size_t mark = c.arena.mark();
+    EncPrelude pre;
+    encode_prelude(c, text, n, fs, pre);
+    const size_t z = pre.z;
+
+    std::vector<SleEnt> alpha;
+    const u32 sb = sle_alphabet(c, text, plain_owner(fs), n, k, pre.hist, alpha);
+    const size_t sigma = alpha.size();
+    HostBitWriter hw;
+    hw.write_compressed_int(sigma);                                           // :155-158
+    for (const SleEnt& e : alpha) hw.write_compressed_int(e.sym);
+    SleDev D;
+    const u16* minfo = sle_marks(c, text, plain_owner(fs), n, k, sb, alpha, D);
+    const unsigned tiles = cdiv(n, ENC_TILE);
 
     // ---- fields of LZSSCoding.hpp:47-50, then the token stream -----------------------------------------------------
     EncParams P;
@@ -1373,6 +1457,72 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
     st->sigma = (u32)sigma;
     c.arena.release(mark);
     return out_len;
+}
+
+// ---- encode(sle) = LiteralEncoder<SLECoder> (compressors/LiteralEncoder.hpp:23-32): the whole input is one literal run ----------------
+// Worst case: 3 + 10 bits per byte (the longest class code; a k-mer symbol costs no more and stands for k bytes), a ranking of sigma
+// (two bytes) and at most 1024 symbols (256 bytes extended to 2^(8 + 2)) of at most ten 7-bit groups each, and the terminator, which
+// takes a byte of its own when 6 or 7 bits of the last one are used.
+u64 sle_literals_bound(u64 n) { return (13 * n + 7) / 8 + 2 + 1024 * 10 + 2; }
+// Scratch besides the output.  Always: the marks (2 bytes per position) and the tile tables (16 bytes per 2048 positions).  The k-mer
+// count, released before the marks are made: k <= 3: a table of 256^k counters (64 MiB at k = 3) and up to min(256^k, n) + 64 sort
+// pairs twice over (24 bytes each); k = 4 .. 7: the key list of the whole text -- 8 + 4 bytes per window, twice over for the radix sort,
+// one head flag per window, then up to one (count, start) pair per window twice over again, 12 bytes of which reuse the idle half of the
+// key buffers -- 24 + 1 + 12 bytes per byte, and the radix sort's tile histograms (1 KiB per 4096 pairs).  A device that cannot hold that fails the call with
+// TDC_GPU_ERR_OOM when the arena is reserved, before anything is written.
+u64 sle_literals_scratch_bound(u64 n, u32 k) {
+    const u64 fixed = (u64)8 << 20;
+    const u64 marks = 2 * n + n / 128 + 65536;
+    const u64 count = k <= 1 ? 0 : k <= 3 ? ((u64)4 << (8 * k)) + 24 * (std::min<u64>((u64)1 << (8 * k), n) + 64) : 38 * n;
+    return fixed + marks + count;
+}
+
+StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 k) {
+    if (k == 0) k = 3;
+    if (k > 7) throw HipError{hipErrorInvalidValue, "sle: kmer must be in 1..7 (SLECoder.hpp:12)", -1};
+    hipStream_t s = c.stream;
+    StageOut r;
+    u32 hist[256] = {0};
+    if (n) {
+        u32* d_hist = c.arena.get<u32>(256);
+        HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * sizeof(u32), s));
+        text_histogram_add(c, d_in, n, d_hist);
+        c.read_n(d_hist, hist, 256);
+    }
+    std::vector<SleEnt> alpha;
+    u32 sb = 1;
+    if (n) sb = sle_alphabet(c, d_in, nullptr, n, k, hist, alpha);
+    HostBitWriter hw;
+    hw.write_compressed_int(alpha.size());                                    // (an empty input: sigma = 0 and nothing else)
+    for (const SleEnt& e : alpha) hw.write_compressed_int(e.sym);
+    const u64 base_bits = hw.nbits;
+    u64 total_bits = base_bits;
+    const unsigned tiles = cdiv(n, ENC_TILE);
+    SleDev D;
+    const u16* minfo = nullptr;
+    u64* tile_bits = nullptr;
+    if (n) {
+        minfo = sle_marks(c, d_in, nullptr, n, k, sb, alpha, D);
+        tile_bits = c.arena.get<u64>((size_t)tiles + 1);
+        sle_lit_stream_kernel<false><<<tiles, 256, 0, s>>>(d_in, minfo, n, D, tile_bits, 0, nullptr);
+        LAUNCH_CHECK();
+        exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
+        total_bits += c.read(tile_bits + tiles);
+    }
+    r.len = (total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
+    if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
+    const size_t padded = align_up(r.len + 8, 8);
+    r.d = c.arena.get<u8>(padded + 64);
+    HIP_TRY(hipMemsetAsync(r.d, 0, padded, s));
+    HIP_TRY(hipMemcpyAsync(r.d, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, s));
+    if (n) {
+        sle_lit_stream_kernel<true><<<tiles, 256, 0, s>>>(d_in, minfo, n, D, tile_bits, base_bits, (u64*)r.d);
+        LAUNCH_CHECK();
+    }
+    terminator_kernel<<<1, 64, 0, s>>>(r.d, total_bits);
+    LAUNCH_CHECK();
+    HIP_TRY(hipStreamSynchronize(s));                            // (the header lives on this frame)
+    return r;
 }
 
 }  // namespace tdc

@@ -576,10 +576,10 @@ public:
     }
 };
 
-// tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) over bwt, rle, mtf and encode(huff) -- e.g. the reference's
+// tdc::ChainCompressor (tudocomp_driver/ChainCompressor.hpp) over bwt, rle, mtf, encode(huff) and encode(sle) -- e.g. the reference's
 // bwtzip = bwt:rle:mtf:encode(huff) -- and the three single compressors as chains of one stage: tdc::RunLengthEncoder
 // (compressors/RunLengthEncoder.hpp:52-74, option offset), tdc::MTFCompressor (compressors/MTFCompressor.hpp:45-69), tdc::LiteralEncoder
-// (compressors/LiteralEncoder.hpp:11-42, `encode(coder)`, coder huff).  compress(): every stage on the device, intermediates in device
+// (compressors/LiteralEncoder.hpp:11-42, `encode(coder)`, coder huff or sle(kmer=1 .. 7)).  compress(): every stage on the device, intermediates in device
 // memory (tdc_gpu_pipeline_compress).  decompress(): tdc_gpu_pipeline_decompress -- the stages backwards on the device for streams of
 // 1 MiB and more, the host loops of tdc_coders.hpp below that (option dec_parse) and on a machine without a device.  Only a leading bwt
 // has input restrictions.
@@ -598,6 +598,14 @@ protected:
             return {TDC_GPU_STAGE_RLE, (uint64_t)o};
         }
         if (av.name == "encode" && av.get("coder", "huff") == "huff") return {TDC_GPU_STAGE_HUFF, 0};
+        if (av.name == "encode") {                                            // encode(sle), encode(sle(kmer=K)), encode(coder=sle(kmer=K))
+            const AlgorithmValue cv = parse_algorithm_id(av.get("coder", ""), {"kmer"});
+            if (cv.name == "sle") {
+                const long k = cv.get_int("kmer", 3);                         // SLECoder.hpp:38
+                if (k < 1 || k > 7) throw std::runtime_error("sle: kmer must be in 1..7");
+                return {TDC_GPU_STAGE_SLE, (uint64_t)k};
+            }
+        }
         throw std::runtime_error("No implementation found for compressor " + part);       // Registry.hpp:214
     }
 public:
@@ -638,6 +646,7 @@ public:
                 ByteSink sink(o, cap);
                 if (st.kind == TDC_GPU_STAGE_RLE) rle_decode(a.data(), a.size(), st.param, sink);
                 else if (st.kind == TDC_GPU_STAGE_MTF) mtf_decode(a.data(), a.size(), sink);
+                else if (st.kind == TDC_GPU_STAGE_SLE) sle_decode_literals(a.data(), a.size(), (unsigned)st.param, sink);
                 else huff_decode_literals(a.data(), a.size(), sink);
                 return sink.n;
             };
@@ -709,7 +718,9 @@ inline std::vector<std::string> registered_algorithms() {
              "rle                                                                         [MI355X; host decoder]",
              "rle(offset=0)                                                               [MI355X; host decoder]",
              "mtf                                                                         [MI355X: chunk summaries + one list per thread; host decoder]",
-             "encode(huff)                                                                [MI355X; host decoder]" };
+             "encode(huff)                                                                [MI355X; host decoder]",
+             "encode(sle)                                                                 [MI355X: k-mer count, fill-state scan, one cost / scan / pack pass; decompression on the MI355X for streams of 1 MiB and more]",
+             "encode(sle(kmer=3))                                                         [kmer = 1 .. 7]" };
 }
 
 inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuContext> ctx = nullptr, int device = 0) {

@@ -526,6 +526,112 @@ template <typename sink_t> inline void huff_decode_literals(const uint8_t* in, s
     while (!dec.eof()) os.put(dec.template decode<uliteral_t>(literal_r));
 }
 
+// ---- LiteralEncoder::decompress (compressors/LiteralEncoder.hpp:34-41) with SLECoder::Decoder (coders/SLECoder.hpp:311-416) ----------
+// The stream: the ranking (sigma and sigma symbols as compressed integers; a symbol is a byte, or 0xFF << 56 | the k bytes of a k-mer,
+// first byte most significant), then one class code per symbol until the bit stream ends; a k-mer symbol stands for k bytes.  The class
+// code of a rank depends on sigma_bits = bits_for(sigma - 1) alone (:378-404), and its length on its first three bits:
+//   sigma_bits < 4:  sigma_bits plain bits
+//   4, 5:            0 + 2 bits (ranks 0 .. 3) | 1 + sigma_bits bits
+//   6:               00 + 3 | 01 + 3 (8 ..) | 10 + 4 (16 ..) | 11 + 6
+//   >= 7:            0cc + 2 (4 cc ..) | 100, 101, 110 + 3 (16, 24, 32 ..) | 111 + sigma_bits
+// sle_decode_literals is the specification of the device decoder (csrc/bytestages_decode.hip), its path for small streams, and the text
+// of the C ABI's tdc_sle_decode.  Refused (std::runtime_error): a ranking that does not end inside the stream, sigma above 1024 (no
+// encoder extends 256 bytes by more than 768 k-mers), a ranking entry that is neither a byte nor a k-mer of this k (marker byte, zero
+// bytes between the marker and the k bytes), a rank >= sigma (the reference reads out of bounds there), a code cut off by the end of
+// the stream (the reference reads zeros there).  More than 2^32 - 2 bytes of output: std::length_error.
+#if defined(__HIPCC__)
+#define TDC_CODERS_HD __host__ __device__
+#else
+#define TDC_CODERS_HD
+#endif
+constexpr uint32_t SLE_MAX_SIGMA = 1024;
+constexpr uint32_t SLE_MAX_CODE_BITS = 13;                   // 3 + sigma_bits of 10
+// header: at most ten groups for sigma and for every entry
+constexpr size_t SLE_MAX_HEADER_BYTES = 10 * (1 + (size_t)SLE_MAX_SIGMA);
+// length of the code whose first three bits are top3
+TDC_CODERS_HD inline uint32_t sle_code_len(uint32_t sb, uint32_t top3) {
+    if (sb < 4) return sb;
+    if (sb < 6) return (top3 & 4u) ? 1 + sb : 3;
+    if (sb == 6) return top3 < 4 ? 5 : top3 < 6 ? 6 : 8;
+    return top3 < 4 ? 5 : top3 < 7 ? 6 : 3 + sb;
+}
+// rank of the code v (its sle_code_len bits, right-aligned)
+TDC_CODERS_HD inline uint32_t sle_code_rank(uint32_t sb, uint32_t len, uint32_t v) {
+    if (sb < 4) return v;
+    if (sb < 6) return len == 3 ? (v & 3u) : (v & ((1u << sb) - 1));
+    if (sb == 6) return len == 5 ? (v & 15u) : len == 6 ? 16 + (v & 15u) : (v & 63u);           // (01 + 3 bits = 8 + the three bits)
+    return len == 5 ? v : len == 6 ? 16 + 8 * ((v >> 3) - 4) + (v & 7u) : (v & ((1u << sb) - 1));
+}
+struct SleRanking {
+    uint32_t sigma = 0, sb = 1;
+    uint64_t body = 0, total = 0;                            // first bit of the codes; bits in front of the terminator
+    std::vector<uint64_t> ent;                               // rank -> its bytes (first byte most significant) | their number << 56
+};
+// 64 bits from bit x on, MSB first, zeros behind `total` (p: `avail` readable bytes)
+inline uint64_t sle_peek(const uint8_t* p, size_t avail, uint64_t total, uint64_t x) {
+    if (x >= total) return 0;
+    const size_t b = (size_t)(x >> 3);
+    uint64_t w = 0;
+    for (size_t i = 0; i < 8; ++i) w = (w << 8) | (b + i < avail ? p[b + i] : 0);
+    const unsigned sh = (unsigned)(x & 7);
+    if (sh) w = (w << sh) | ((b + 8 < avail ? p[b + 8] : 0) >> (8 - sh));
+    if (x + 64 > total) w &= ~0ull << (64 - (total - x));
+    return w;
+}
+// the bits in front of the terminator (io/BitOStream.hpp:53-64) of a stream of n >= 1 bytes that ends with `last`
+inline uint64_t sle_total_bits(size_t n, uint8_t last) {
+    const unsigned u = last & 7u;
+    if (u >= 6 && n < 2) throw std::runtime_error("corrupt stream: no SLE ranking");
+    return u >= 6 ? (uint64_t)(n - 2) * 8 + u : (uint64_t)(n - 1) * 8 + u;
+}
+// Decoder ctor :333-346 from the first `avail` bytes of the stream (all of it, or at least SLE_MAX_HEADER_BYTES + 8)
+inline void sle_parse_ranking(const uint8_t* p, size_t avail, uint64_t total, unsigned k, SleRanking& R) {
+    if (k < 1 || k > 7) throw std::runtime_error("sle: kmer must be in 1..7");
+    uint64_t pos = 0;
+    auto cint = [&]() -> uint64_t {                          // io/BitIStream.hpp:174-188: groups of "more" + 7 bits, low group first
+        uint64_t v = 0;
+        for (unsigned i = 0; ; ++i) {
+            if (pos + 8 > total) throw std::runtime_error("corrupt stream: the SLE ranking does not end inside the stream");
+            const uint64_t g = sle_peek(p, avail, total, pos) >> 56;
+            pos += 8;
+            if (i == 10 || (i == 9 && (g & 0x7Eu))) throw std::runtime_error("corrupt stream: SLE ranking entry out of range");
+            v |= (g & 0x7Fu) << (7 * i);
+            if (!(g & 0x80u)) return v;
+        }
+    };
+    const uint64_t sigma = cint();
+    if (sigma > SLE_MAX_SIGMA) throw std::runtime_error("corrupt stream: SLE ranking of more than 1024 symbols");
+    R.sigma = (uint32_t)sigma; R.total = total;
+    R.sb = sigma ? coder_bits_for(sigma - 1) : 1;            // (no code is valid without a symbol)
+    R.ent.assign((size_t)sigma, 0);
+    for (uint64_t r = 0; r < sigma; ++r) {
+        const uint64_t x = cint();
+        if (x < 256) R.ent[r] = x | (1ull << 56);
+        else if ((x >> 56) == 0xFF && ((x & 0x00FFFFFFFFFFFFFFull) >> (8 * k)) == 0) R.ent[r] = (x & 0x00FFFFFFFFFFFFFFull) | ((uint64_t)k << 56);
+        else throw std::runtime_error("corrupt stream: SLE ranking entry is neither a byte nor a k-mer");
+    }
+    R.body = pos;
+}
+template <typename sink_t> inline void sle_decode_literals(const uint8_t* in, size_t n, unsigned k, sink_t& os) {
+    if (!n) throw std::runtime_error("corrupt stream: no SLE ranking");
+    SleRanking R;
+    sle_parse_ranking(in, n, sle_total_bits(n, in[n - 1]), k, R);
+    uint64_t len = 0;
+    for (uint64_t pos = R.body; pos < R.total; ) {
+        const uint64_t w = sle_peek(in, n, R.total, pos);
+        const uint32_t l = sle_code_len(R.sb, (uint32_t)(w >> 61));
+        if (pos + l > R.total) throw std::runtime_error("corrupt stream: cut-off SLE code");
+        const uint32_t rank = sle_code_rank(R.sb, l, (uint32_t)(w >> (64 - l)));
+        if (rank >= R.sigma) throw std::runtime_error("corrupt stream: SLE rank out of range");
+        const uint64_t e = R.ent[rank];
+        const unsigned m = (unsigned)(e >> 56);
+        len += m;
+        for (unsigned j = m; j-- > 0; ) os.put((uint8_t)(e >> (8 * j)));
+        pos += l;
+    }
+    if (len > 0xFFFFFFFEull) throw std::length_error("sle: the stream decodes to more than 2^32 - 2 bytes");   // (a malformed code further on comes first)
+}
+
 // ---- LZWCompressor::decompress (compressors/LZWCompressor.hpp:110-133) with lzw::decode_step (lzw/LZWDecoding.hpp:12-99) restated ------
 // The specification of the device decoder (csrc/lzw.hip), its path for small streams, and the text of the C ABI's tdc_lzw_decode.
 // bit: BitCoder -- code k (0-based) in bits_for(k + 256) bits; else EliasGammaCoder.  dict_size = 0: the dictionary is never reset.
