@@ -39,7 +39,7 @@ typedef enum {
 
 /* coder ids (option `coder`, etc/registry_config.py:28-31,138-142) */
 enum { TDC_GPU_CODER_HUFF = 0, TDC_GPU_CODER_GAMMA = 1, TDC_GPU_CODER_ARITH = 2, TDC_GPU_CODER_ASCII = 3, TDC_GPU_CODER_SLE = 4,
-       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw, lzss_lcp */, TDC_GPU_CODER_DELTA = 6 /* EliasDeltaCoder: lzss_lcp */ };
+       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw, lzss_lcp, lzss */, TDC_GPU_CODER_DELTA = 6 /* EliasDeltaCoder: lzss_lcp, lzss */ };
 /* coder=sle(kmer=K) (coders/SLECoder.hpp:36-40; the reference's default is 3): the option travels in bits 8.. of `coder` */
 #define TDC_GPU_CODER_SLE_K(K) (TDC_GPU_CODER_SLE | ((K) << 8))
 /* factorization strategy of lcpcomp (option `comp`, LCPCompressor.hpp:87): ArraysComp or PLCPPeaksStrategy */
@@ -344,6 +344,35 @@ int tdc_gpu_lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, 
 int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                 size_t* out_len, uint64_t* codes, uint32_t* rounds);
 
+/* ---- lzss: LZSSSlidingWindowCompressor<ASCIICoder | BitCoder | EliasGammaCoder | EliasDeltaCoder> (compressors/
+ * LZSSSlidingWindowCompressor.hpp:39-143): the classic LZ77 parse over a sliding window, factorized ON THE DEVICE.
+ * No input restrictions (raw bytes, no sentinel); the empty input has no tokens.  Options: window (the reference's default: 16) and
+ * threshold (3; 0 behaves as 1).  At text position p the candidates are the sources s in [max(0, p - window), p), the look-ahead is
+ * L(p) = end(p) - p with end(p) = n for n < 2 window, else clamp(p - window, 0, n - 2 window) + 2 window -- so a factor in the first
+ * `window` positions may be as long as 2 window - 1 --, and the smallest s among the longest matches of at least `threshold` bytes wins;
+ * a source may overlap p.  The stream has no header: a literal is the flag 0 and the byte under literal_r, a factor the flag 1,
+ * p - s under Range(0, p) and the length under Range(0, window); the bit stream's terminator ends it.
+ * coder: TDC_GPU_CODER_ASCII, _BIT, _GAMMA or _DELTA; anything else (huff among it): TDC_GPU_ERR_UNSUPPORTED.
+ * window: 1 .. 4096 (the match kernel keeps a tile's text and its window in LDS); 0: TDC_GPU_ERR_ARG, above 4096: TDC_GPU_ERR_UNSUPPORTED.
+ * n above 2^32 - 2: TDC_GPU_ERR_TOO_LARGE.
+ * One defect of the reference is not reproduced: under coder=bit with a window that is no power of two, a length of up to
+ * 2 window - 1 may not fit the bits_for(window) bits of its field; the reference truncates it and its own decoder then yields another
+ * text (window 3, "aaaaaaaa": lengths 4 and 5 in 2 bits).  On such inputs the call returns TDC_GPU_ERR_UNSUPPORTED and writes nothing to
+ * `out`; the other three coders ignore the range and code them normally.
+ * stats (may be NULL): n, out_len, factors, flen_max, ms_h2d, ms_factorize, ms_encode, ms_d2h, ms_total, arena_bytes.
+ * There is no device decoder (DESIGN.md section 5.7 says why): streams are decoded by tdc_lzss_sw_decode. */
+int tdc_gpu_lzss_sw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder,
+                             uint8_t** out, size_t* out_len, tdc_gpu_stats* stats);
+/* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small. */
+int tdc_gpu_lzss_sw_compress_into(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder,
+                                  uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
+/* worst-case stream length for n input bytes (what an _into buffer needs at most); 0 for a coder or a window the call does not take */
+size_t tdc_gpu_lzss_sw_bound(size_t n, uint32_t window, int coder);
+/* the factors of the parse on their own, sorted by pos: pos / src / len are malloc'd (tdc_gpu_free), z entries each; what
+ * tdc_lzss_sw_factors computes on the host */
+int tdc_gpu_lzss_sw_factorize(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold,
+                              uint32_t** pos, uint32_t** src, uint32_t** len, size_t* z);
+
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG
  * for an inner 0, TDC_GPU_ERR_TOO_LARGE).  out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0): n bytes, no header.  The suffix array is the one
@@ -442,6 +471,14 @@ int tdc_lzw_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_
  * into the end of the stream or is longer than 64, a delta width above 64, a length that does not add up to n. */
 int tdc_lzss_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
 
+/* The same contract for LZSSSlidingWindowCompressor::decompress (:120-143) with the Decoder of TDC_GPU_CODER_ASCII, _BIT, _GAMMA or _DELTA
+ * (else TDC_GPU_ERR_UNSUPPORTED): tokens until the stream ends.  window is the compressor's option; only coder=bit reads it (the width of
+ * the length field; 0: TDC_GPU_ERR_ARG).  TDC_GPU_ERR_ARG for: a factor of distance 0 or of a distance above the text so far (the
+ * reference reads out of bounds), a token cut off by the end of the stream (the reference reads zeros there), a unary prefix that runs
+ * into the end of the stream or is longer than 64, a delta width above 64.  TDC_GPU_ERR_TOO_LARGE for a text of more than 2^32 - 2
+ * bytes.  A factor of length 0 decodes to nothing, as in the reference. */
+int tdc_lzss_sw_decode(const uint8_t* in, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap, size_t* out_len);
+
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,
                         const uint32_t* len, size_t z, uint8_t** out, size_t* out_len);
@@ -473,6 +510,11 @@ int tdc_lz78_factors(const uint8_t* in, size_t n, uint32_t** ids, uint8_t** char
  * the dictionary node phrase k ends in (0 .. 255: the bytes; 256 + j: phrase j and the byte behind it), the left-over phrase included; no
  * codes for the empty input.  *codes is malloc'd (tdc_gpu_free). */
 int tdc_lzw_factors(const uint8_t* in, size_t n, uint32_t** codes, size_t* z);
+/* compressors/LZSSSlidingWindowCompressor.hpp:39-118 : the greedy sliding-window parse on its own (host, one core; the specification of
+ * tdc_gpu_lzss_sw_factorize), in the closed form stated at tdc_gpu_lzss_sw_compress -- no sliding buffer.  The factors sorted by pos;
+ * pos / src / len are malloc'd (tdc_gpu_free).  Any window >= 1 (0: TDC_GPU_ERR_ARG); n above 2^32 - 2: TDC_GPU_ERR_TOO_LARGE. */
+int tdc_lzss_sw_factors(const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, uint32_t** pos, uint32_t** src, uint32_t** len,
+                        size_t* z);
 /* The start-up check of tdc_gpu_ctx_create() on its own (no GPU): rebuilds two built-in fixture tables (sigma 40 and 200, many
  * equal counts) and compares them with what the reference build yields; TDC_GPU_ERR_INTERNAL if this build's C++ library
  * orders ties differently (coders/HuffmanCoder.hpp:88-120 heap functions, :455 unstable std::sort) -- every call with

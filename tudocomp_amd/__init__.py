@@ -16,8 +16,8 @@ CODER_GAMMA = 1
 CODER_ARITH = 2
 CODER_ASCII = 3
 CODER_SLE = 4            # coder=sle(kmer=k): CODER_SLE | (k << 8), k = 0 means the reference's default 3
-CODER_BIT = 5            # BitCoder: lzw, lzss_lcp
-CODER_DELTA = 6          # EliasDeltaCoder: lzss_lcp
+CODER_BIT = 5            # BitCoder: lzw, lzss_lcp, lzss
+CODER_DELTA = 6          # EliasDeltaCoder: lzss_lcp, lzss
 COMP_ARRAYS = 0
 COMP_PLCPPEAKS = 1
 COMP_MAXLCP = 2
@@ -115,6 +115,23 @@ def lzw_factors(data):
         L.tdc_gpu_free(codes)
 
 
+def lzss_sw_factors(data, window=16, threshold=3):
+    """The sliding-window parse of lzss on its own (host, one core; compressors/LZSSSlidingWindowCompressor.hpp:39-118 in closed form):
+    (pos, src, len) as numpy arrays, sorted by pos."""
+    L = _native.load()
+    a = _u8(data)
+    p, s, l, z = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+    rc = L.tdc_lzss_sw_factors(_ptr(a) if len(a) else None, len(a), int(window), int(threshold), ctypes.byref(p), ctypes.byref(s),
+                               ctypes.byref(l), ctypes.byref(z))
+    if rc:
+        raise TdcGpuError(rc, "tdc_lzss_sw_factors")
+    try:
+        return tuple(np.ctypeslib.as_array(ctypes.cast(x, ctypes.POINTER(ctypes.c_uint32)), (max(z.value, 1),))[:z.value].copy() for x in (p, s, l))
+    finally:
+        for x in (p, s, l):
+            L.tdc_gpu_free(x)
+
+
 def option_names():
     """Names of the library's options (tdc_gpu_ctx_set_option)."""
     L = _native.load()
@@ -193,6 +210,16 @@ def lzss_decode(data, coder=CODER_HUFF):
     """decode_text_internal (LCPCompressor.hpp:23-76) on an lzss_lcp / lcpcomp stream of coder huff, bit, gamma, delta or ascii, on the
     host: the escaped, 0-terminated text"""
     return _host_decode("tdc_lzss_decode", data, int(coder))
+
+
+def lzss_sw_decode(data, coder=CODER_BIT, window=16):
+    """LZSSSlidingWindowCompressor::decompress (:120-143) on the host; only coder=bit reads `window`"""
+    return _host_decode("tdc_lzss_sw_decode", data, int(coder), ctypes.c_uint32(int(window)))
+
+
+def lzss_sw_bound(n, window=16, coder=CODER_BIT):
+    """worst-case length of an lzss stream for n input bytes (0: a coder or a window lzss does not take)"""
+    return _native.load().tdc_gpu_lzss_sw_bound(n, int(window), int(coder))
 
 
 def lzss_lcp_bound(n, coder=CODER_HUFF):
@@ -433,6 +460,38 @@ class Context:
         p, s, l, z = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         self._check(self._L.tdc_gpu_lzss_lcp_factorize(self._h, _ptr(a), len(a), threshold, ctypes.byref(p), ctypes.byref(s),
                                                        ctypes.byref(l), ctypes.byref(z)))
+        out = [np.frombuffer(self._take(x, z.value * 4), dtype=np.uint32).copy() for x in (p, s, l)]
+        return out[0], out[1], out[2]
+
+    def lzss_sw_compress(self, data, window=16, threshold=3, coder=CODER_BIT):
+        """LZSSSlidingWindowCompressor<coder>::compress on raw bytes (no escaping), factorized on the device; coder: CODER_ASCII, _BIT,
+        _GAMMA or _DELTA.  Returns (stream, stats)."""
+        a = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_lzss_sw_compress(self._h, _ptr(a) if len(a) else None, len(a), int(window), int(threshold), coder,
+                                                     ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)))
+        return self._take(out, n.value), st.as_dict()
+
+    def lzss_sw_compress_into(self, data, n, out, window=16, threshold=3, coder=CODER_BIT):
+        """lzss_sw_compress of the first n bytes of `data` into a caller-owned buffer (PinnedBuffer or writable uint8 array; lzss_sw_bound
+        sizes it): returns (out_len, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the length."""
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_lzss_sw_compress_into(self._h, _ptr(ta) if n else None, n, int(window), int(threshold), coder, _ptr(oa), oa.size,
+                                                   ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
+
+    lzss_sw_bound = staticmethod(lzss_sw_bound)
+
+    def lzss_sw_factorize(self, data, window=16, threshold=3):
+        """the factors of the lzss parse from the device: (pos, src, len), sorted by pos"""
+        a = _u8(data)
+        p, s, l, z = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.tdc_gpu_lzss_sw_factorize(self._h, _ptr(a) if len(a) else None, len(a), int(window), int(threshold), ctypes.byref(p),
+                                                      ctypes.byref(s), ctypes.byref(l), ctypes.byref(z)))
         out = [np.frombuffer(self._take(x, z.value * 4), dtype=np.uint32).copy() for x in (p, s, l)]
         return out[0], out[1], out[2]
 
@@ -963,6 +1022,30 @@ class LZWCompressor:
         if self.dec == "gpu":
             return self.ctx.lzw_decompress(stream, self.coder)[0]
         return lzw_decode(stream, self.coder)
+
+
+class LZSSSlidingWindowCompressor:
+    """Mirror of tdc::LZSSSlidingWindowCompressor<coder> (compressors/LZSSSlidingWindowCompressor.hpp:15-144), the algorithm `lzss`; no
+    input restrictions.  coder: ascii, bit, gamma or delta (it has no default in the reference); window 1 .. 4096, threshold.  The parse
+    runs on the device; decompress() is the host loop (lzss_sw_decode) -- there is no device decoder."""
+
+    _CODERS = {"ascii": CODER_ASCII, "bit": CODER_BIT, "gamma": CODER_GAMMA, "delta": CODER_DELTA}
+
+    def __init__(self, ctx, coder=None, window=16, threshold=3):
+        if coder not in self._CODERS:
+            raise RuntimeError("No implementation found for compressor lzss(coder=%s)" % coder)
+        if not 1 <= int(window) <= 4096:
+            raise RuntimeError("lzss: window=%s is not available (1 .. 4096)" % (window,))
+        self.ctx, self.coder, self.window, self.threshold = ctx, self._CODERS[coder], int(window), int(threshold)
+        self.last_stats = None
+
+    def compress(self, data):
+        out, st = self.ctx.lzss_sw_compress(data, self.window, self.threshold, self.coder)
+        self.last_stats = st
+        return out
+
+    def decompress(self, stream):
+        return lzss_sw_decode(stream, self.coder, self.window)
 
 
 class LZSSLCPCompressor:

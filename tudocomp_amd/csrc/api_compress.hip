@@ -1,4 +1,4 @@
-// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78 and lzw compression -- the upload, the text's arrays, the factors,
+// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw and lzss compression -- the upload, the text's arrays, the factors,
 // the whole pipeline on host and device buffers.
 #include "api.hpp"
 
@@ -585,6 +585,104 @@ int tdc_gpu_lzw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, int code
         }
         ev.finish();
         sink_commit(s, len);
+    });
+}
+
+}  // extern "C"
+
+// ---- lzss (LZSSSlidingWindowCompressor; lzss_sw.hip) ------------------------------------------------------------
+namespace {
+// public coder id -> kind of lzss_sw_encode_tokens for the coders the reference registers lzss with (etc/registry_config.py:13-18,236); -1: none
+int lzss_sw_kind(int coder) {
+    switch (coder) {
+        case TDC_GPU_CODER_BIT: return 0;
+        case TDC_GPU_CODER_ASCII: return 1;
+        case TDC_GPU_CODER_GAMMA: return 2;
+        case TDC_GPU_CODER_DELTA: return 3;
+        default: return -1;
+    }
+}
+void lzss_sw_check(const uint8_t* in, size_t n, uint32_t window) {
+    if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (window == 0) throw ArgError{TDC_GPU_ERR_ARG, "lzss: window must be >= 1"};
+    if (window > LZSS_SW_MAX_WINDOW) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss: windows above 4096 are not built"};
+    if (n > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzss: input must be at most 2^32 - 2 bytes"};
+}
+// text (n + 64), next / factor / two scratch words and the mark per position (17 n) and what comes behind them: the stream's worst case,
+// or the factor lists (three words and a class byte per token, at most n tokens)
+size_t lzss_sw_arena(size_t n, size_t behind) { return 18 * n + behind + ((size_t)64 << 20); }
+
+void lzss_sw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder, Sink s, tdc_gpu_stats* stats) {
+    const int kind = lzss_sw_kind(coder);
+    if (kind < 0) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss: coder must be ascii, bit, gamma or delta"};
+    lzss_sw_check(in, n, window);
+    sink_check(s, "NULL argument");
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const size_t cap = align_up(lzss_sw_bound(n, window, kind) + 16, 8);       // (+ 16: the pack's last word)
+    reserve_arena(c, lzss_sw_arena(n, cap));
+    Events ev(c);
+    const int e0 = ev.tick();
+    const u8* d_text = upload_plain(c, in, n);
+    const int e1 = ev.tick();
+    u32* tokpos = nullptr, *fac = nullptr;
+    const size_t ntok = lzss_sw_tokens(c, d_text, n, window, threshold, &tokpos, &fac);
+    const int e2 = ev.tick();
+    u8* d_out = c.arena.get<u8>(cap);
+    LzssSwStats ls;
+    const size_t len = lzss_sw_encode_tokens(c, d_text, tokpos, fac, ntok, window, kind, d_out, cap, &ls);
+    if (ls.truncates) throw ArgError{TDC_GPU_ERR_UNSUPPORTED,
+        "lzss(coder=bit): a factor is longer than bits_for(window) bits hold; the reference truncates it and decodes another text -- not reproduced"};
+    const int e3 = ev.tick();
+    *s.out_len = len;
+    sink_fit(s, len);
+    sink_download(c, s, d_out, len);
+    const int e4 = ev.tick();
+    if (stats) {
+        stats->n = n; stats->out_len = len; stats->factors = ls.factors; stats->flen_max = ls.flen_max; stats->arena_bytes = c.arena.high;
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_d2h, e3, e4); ev.span(&stats->ms_total, e0, e4);
+    }
+    ev.finish();
+    sink_commit(s, len);
+}
+}  // namespace
+
+extern "C" {
+
+size_t tdc_gpu_lzss_sw_bound(size_t n, uint32_t window, int coder) { return lzss_sw_bound(n, window, lzss_sw_kind(coder)); }
+
+int tdc_gpu_lzss_sw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder,
+                             uint8_t** out, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { lzss_sw_compress(ctx, in, n, window, threshold, coder, sink_malloc(out, out_len), stats); });
+}
+
+int tdc_gpu_lzss_sw_compress_into(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder,
+                                  uint8_t* out, size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { lzss_sw_compress(ctx, in, n, window, threshold, coder, sink_into(out, out_cap, out_len), stats); });
+}
+
+int tdc_gpu_lzss_sw_factorize(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold,
+                              uint32_t** pos, uint32_t** src, uint32_t** len, size_t* z) {
+    return guarded(ctx, [&] {
+        lzss_sw_check(in, n, window);
+        if (!pos || !src || !len || !z) throw ArgError{TDC_GPU_ERR_ARG, "output pointer is NULL"};
+        Ctx& c = ctx->c;
+        reserve_arena(c, lzss_sw_arena(n, 13 * n));
+        Events ev(c);
+        const u8* d_text = upload_plain(c, in, n);
+        u32* tokpos = nullptr, *fac = nullptr;
+        const size_t ntok = lzss_sw_tokens(c, d_text, n, window, threshold, &tokpos, &fac);
+        u32* d_pos = c.arena.get<u32>(ntok + 1), *d_src = c.arena.get<u32>(ntok + 1), *d_len = c.arena.get<u32>(ntok + 1);
+        const size_t cnt = lzss_sw_factor_list(c, tokpos, fac, ntok, d_pos, d_src, d_len);
+        HostBuf hp(cnt * 4), hs(cnt * 4), hl(cnt * 4);
+        if (cnt) {
+            HIP_TRY(hipMemcpyAsync(hp.p, d_pos, cnt * 4, hipMemcpyDeviceToHost, c.stream));
+            HIP_TRY(hipMemcpyAsync(hs.p, d_src, cnt * 4, hipMemcpyDeviceToHost, c.stream));
+            HIP_TRY(hipMemcpyAsync(hl.p, d_len, cnt * 4, hipMemcpyDeviceToHost, c.stream));
+        }
+        ev.finish();
+        *pos = hp.release<uint32_t>(); *src = hs.release<uint32_t>(); *len = hl.release<uint32_t>(); *z = cnt;
     });
 }
 

@@ -18,12 +18,14 @@
 // (2) recompute the costs, scan inside the workgroup, OR the bits into the zeroed output (big-endian 64-bit words).
 //
 // At the end of the file: encode(sle) = LiteralEncoder<SLECoder> as a byte stage (sle_literals_device, declared in bytestages.hpp),
-// the owner-less use of the SLE machinery below.
+// the owner-less use of the SLE machinery below, and the token coder of lzss (lzss_sw_encode_tokens, DESIGN.md
+// section 5.7): the same sink and field writers over a token list instead of position space.
 #include "stages.hpp"
 #include "bytestages.hpp"
 #include "prim.hpp"
 #include "huffman_host.hpp"
 #include "arith.hpp"
+#include "decode.hpp"
 
 #include <string.h>
 #include <algorithm>
@@ -524,6 +526,30 @@ size_t encode_bound_coder(size_t n, int coder) { return ((coder & 0xFF) == 2 ? 2
 // positions).  + 64: the header -- n and three fields, at most 63 + 3 * 65 bits (gamma: the zero-factor stream writes 2^32 - 1 in 65
 // bits) = 33 bytes -- and the terminator byte.
 size_t encode_bound_uni(size_t n, int coder) { return (coder == 4 ? 8 : coder == 5 ? 9 : 6) * n + 64; }
+
+// lzss (LZSSSlidingWindowCompressor.hpp:85-95; kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder): no header, and
+// every token covers at least one text byte, so the worst case is n times the costliest token.  A literal is the flag and the byte: 1 + 8
+// bits, '0' and the byte = 16, 1 + gamma(255) = 1 + 17, 1 + delta(255) = 1 + 17.  A factor is the flag, a distance <= w and a length
+// <= 2w - 1 (both coders' costs grow with the value):
+//   bit    1 + bits_for(p) + bits_for(w) <= 1 + bits_for(n) + bits_for(w)
+//   ascii  8 * (1 + digits(w) + 1 + digits(2w - 1) + 1)
+//   gamma  1 + (2 bits_for(w) + 1) + (2 bits_for(2w - 1) + 1)
+//   delta  1 + delta_bits(w) + delta_bits(2w - 1),  delta_bits(v) = 2 bits_for(bits_for(v)) + 1 + bits_for(v)
+// + 2: the terminator (the count of the last byte's bits, in that byte or in one of its own).
+size_t lzss_sw_bound(size_t n, u32 window, int kind) {
+    if (kind < 0 || kind > 3 || window == 0 || window > LZSS_SW_MAX_WINDOW || n > 0xFFFFFFFEull) return 0;
+    const u64 w = window, l = 2 * w - 1;
+    auto digits = [](u64 v) { u64 d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
+    auto delta_bits = [](u64 v) { return 2 * (u64)bits_for(bits_for(v)) + 1 + bits_for(v); };
+    u64 lit, fac;
+    switch (kind) {
+        case 0:  lit = 9;  fac = 1 + (u64)bits_for(n) + bits_for(w); break;
+        case 1:  lit = 16; fac = 8 * (1 + digits(w) + 1 + digits(l) + 1); break;
+        case 2:  lit = 18; fac = 1 + (2 * (u64)bits_for(w) + 1) + (2 * (u64)bits_for(l) + 1); break;
+        default: lit = 18; fac = 1 + delta_bits(w) + delta_bits(l); break;
+    }
+    return (size_t)(((u64)n * std::max(lit, fac) + 7) / 8 + 2);
+}
 
 size_t encode_huff(Ctx& c, const u8* text, size_t n, FactorSpace fs, u8* d_out, size_t out_cap, EncodeStats* st) {
     return encode_stream(c, text, n, fs, 0, d_out, out_cap, st, nullptr);
@@ -1523,6 +1549,148 @@ StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 k) {
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(s));                            // (the header lives on this frame)
     return r;
+}
+
+
+// ---- lzss: the tokens of the sliding-window parse through one coder (LZSSSlidingWindowCompressor.hpp:85-95) -------
+// Token i starts at text position tokpos[i]; fac[p] = distance << 16 | length, 0 for a literal.  A literal is the flag 0 and the byte
+// under literal_r; a factor the flag 1, the distance under Range(0, p) and the length under Range(0, window).  BitCoder: bits_for(p) and
+// wbits = bits_for(window) bits (the one field whose width depends on where the token stands: hence a cost pass over the tokens instead of
+// closed-form offsets); gamma / delta ignore the ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.
+// Tiles of 2048 tokens: bits per tile, their scan, then the pack recomputes the costs and ORs the fields into the zeroed output.
+constexpr int SWT_PER_THREAD = 8, SWT_TILE = 256 * SWT_PER_THREAD;
+struct SwScalars { unsigned long long factors; u32 flen_max, trunc; };
+
+template <int KIND> __device__ __forceinline__ u32 sw_token_bits(u32 pos, u32 f, u32 ch, u32 wbits) {
+    if (KIND == ENC_TAB) return f ? 1u + uni_bits_for(pos) + wbits : 9u;
+    if (KIND == ENC_ASCII) return f ? 8u * (1u + ascii_int_chars(f >> 16) + ascii_int_chars(f & 0xFFFFu)) : 16u;
+    return f ? 1u + uni_cost<KIND>(f >> 16) + uni_cost<KIND>(f & 0xFFFFu) : 1u + uni_cost<KIND>(ch);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void sw_tile_bits_kernel(const u8* __restrict__ text, const u32* __restrict__ tokpos, const u32* __restrict__ fac,
+                                                            u64 ntok, u32 wbits, u32 tiles, u64* __restrict__ tile_bits, SwScalars* __restrict__ sc) {
+    __shared__ u32 sm[4];
+    u32 nfac = 0, lmax = 0;
+    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const u64 i0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
+        u32 sum = 0;
+#pragma unroll
+        for (int j = 0; j < SWT_PER_THREAD; ++j) {
+            if (i0 + j < ntok) {
+                const u32 pos = tokpos[i0 + j], f = fac[pos];
+                const u32 ch = (KIND == ENC_GAMMA || KIND == ENC_DELTA) && !f ? text[pos] : 0u;
+                sum += sw_token_bits<KIND>(pos, f, ch, wbits);
+                nfac += f ? 1u : 0u;
+                lmax = max(lmax, f & 0xFFFFu);
+            }
+        }
+        sum = wave_reduce_sum(sum);
+        if (lane_id() == 0) sm[wave_id()] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_bits[tile] = (u64)sm[0] + sm[1] + sm[2] + sm[3];
+        __syncthreads();
+    }
+    nfac = wave_reduce_sum(nfac);
+    lmax = wave_reduce_max(lmax);
+    if (lane_id() == 0) {
+        if (nfac) atomicAdd(&sc->factors, (unsigned long long)nfac);
+        if (lmax) atomicMax(&sc->flen_max, lmax);
+        if (KIND == ENC_TAB && (lmax >> wbits)) atomicOr(&sc->trunc, 1u);      // write_int would drop the length's top bits
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void sw_pack_kernel(const u8* __restrict__ text, const u32* __restrict__ tokpos, const u32* __restrict__ fac,
+                                                       u64 ntok, u32 wbits, u32 tiles, const u64* __restrict__ tile_off, u64* __restrict__ out) {
+    __shared__ u32 sm[5];
+    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const u64 i0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
+        u32 pos[SWT_PER_THREAD], f[SWT_PER_THREAD], ch[SWT_PER_THREAD];
+        u32 sum = 0;
+#pragma unroll
+        for (int j = 0; j < SWT_PER_THREAD; ++j) {
+            pos[j] = 0; f[j] = 0; ch[j] = 0;
+            if (i0 + j < ntok) {
+                pos[j] = tokpos[i0 + j]; f[j] = fac[pos[j]];
+                if (!f[j]) ch[j] = text[pos[j]];
+                sum += sw_token_bits<KIND>(pos[j], f[j], ch[j], wbits);
+            }
+        }
+        u32 total;
+        const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
+        BitSink sink;
+        sink.out = out;
+        sink.pos = tile_off[tile] + excl;
+        sink.acc = 0;
+        sink.cnt = 0;
+#pragma unroll
+        for (int j = 0; j < SWT_PER_THREAD; ++j) {
+            if (i0 + j < ntok) {
+                const u32 dist = f[j] >> 16, len = f[j] & 0xFFFFu;
+                if (KIND == ENC_TAB) {
+                    if (!f[j]) sink.append(ch[j], 9);                                  // :94-95 the flag 0 and the byte
+                    else { sink.append(1, 1); sink.append(dist, uni_bits_for(pos[j])); sink.append(len, wbits); }     // :87-89
+                } else if (KIND == ENC_ASCII) {
+                    if (!f[j]) { sink.append('0', 8); sink.append(ch[j], 8); }
+                    else { sink.append('1', 8); append_ascii_int(sink, dist); append_ascii_int(sink, len); }
+                } else {
+                    if (!f[j]) { sink.append(0, 1); append_uni<KIND>(sink, ch[j]); }
+                    else { sink.append(1, 1); append_uni<KIND>(sink, dist); append_uni<KIND>(sink, len); }
+                }
+            }
+        }
+        sink.flush();
+    }
+}
+
+size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const u32* fac, size_t ntok, u32 window, int kind,
+                             u8* d_out, size_t out_cap, LzssSwStats* st) {
+    LzssSwStats local;
+    if (!st) st = &local;
+    *st = LzssSwStats();
+    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "lzss: no such coder", (int)__LINE__};
+    hipStream_t s = c.stream;
+    const size_t mark = c.arena.mark();
+    const u32 wbits = bits_for(window);
+    const size_t tiles = (ntok + SWT_TILE - 1) / SWT_TILE;                      // < 2^21
+    const unsigned grid = dec_grid(tiles * 256);
+    u64 total_bits = 0;
+    u64* tile_bits = nullptr;
+    if (ntok) {
+        tile_bits = c.arena.get<u64>(tiles + 1);
+        SwScalars* d_sc = (SwScalars*)c.arena.alloc(sizeof(SwScalars));
+        HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(SwScalars), s));
+        switch (kind) {
+            case 0:  sw_tile_bits_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
+            case 1:  sw_tile_bits_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
+            case 2:  sw_tile_bits_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
+            default: sw_tile_bits_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
+        }
+        LAUNCH_CHECK();
+        exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
+        total_bits = c.read(tile_bits + tiles);
+        const SwScalars h = c.read(d_sc);
+        st->factors = h.factors; st->flen_max = h.flen_max; st->truncates = h.trunc != 0;
+        if (st->truncates) { c.arena.release(mark); return 0; }
+    }
+    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
+    const size_t padded = align_up(out_len + 8, 8);
+    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "lzss: output buffer too small", (int)__LINE__};
+    HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
+    if (ntok) {
+        switch (kind) {
+            case 0:  sw_pack_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
+            case 1:  sw_pack_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
+            case 2:  sw_pack_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
+            default: sw_pack_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
+        }
+        LAUNCH_CHECK();
+    }
+    bit_stream_terminator(c, d_out, total_bits);
+    HIP_TRY(hipStreamSynchronize(s));
+    c.arena.release(mark);
+    return out_len;
 }
 
 }  // namespace tdc

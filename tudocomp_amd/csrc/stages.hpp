@@ -260,6 +260,22 @@ size_t lzw_encode(Ctx& c, const u32* d_codes, size_t z, bool bit, u8* d_out, siz
 constexpr size_t LZW_DEVICE_MIN = (size_t)64 << 10;
 size_t decode_lzw(Ctx& c, const u8* stream, size_t len, bool bit, Sink& out, size_t* need, DecodeStats* st);
 
+// ---- lzss (compressors/LZSSSlidingWindowCompressor.hpp; lzss_sw.hip, lzss_sw_host.cpp) ----------------------------
+constexpr u32 LZSS_SW_MAX_WINDOW = 4096;      // the match kernel holds a tile of positions, its window and its look-ahead in LDS
+// :57-99 for every text position at once, then the greedy parse as the orbit of position 0.  Returns the number of tokens; tokpos[i] =
+// text position of token i (ascending) and fac[p] = distance << 16 | length of the factor the parse would start AT p (0: a literal) are
+// taken from the arena and stay valid until the caller releases its mark.  1 <= window <= LZSS_SW_MAX_WINDOW, n <= 2^32 - 2.
+size_t lzss_sw_tokens(Ctx& c, const u8* d_text, size_t n, u32 window, u32 threshold, u32** tokpos, u32** fac);
+// the factors among the tokens as a list sorted by pos (d_pos / d_src / d_len: ntok entries of capacity each); returns their number
+size_t lzss_sw_factor_list(Ctx& c, const u32* tokpos, const u32* fac, size_t ntok, u32* d_pos, u32* d_src, u32* d_len);
+// :85-95 -- the tokens through one coder (encode.hip): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
+// Writes the stream, terminator included, to d_out and returns its length -- or 0 with st->truncates set and nothing packed: BitCoder
+// and a length that does not fit bits_for(window) bits.  bound: lzss_sw_bound (0: this kind or window is not taken).
+struct LzssSwStats { u64 factors = 0; u32 flen_max = 0; bool truncates = false; };
+size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const u32* fac, size_t ntok, u32 window, int kind,
+                             u8* d_out, size_t out_cap, LzssSwStats* st);
+size_t lzss_sw_bound(size_t n, u32 window, int kind);
+
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform
 // goes afterwards.  True: it is on its way there already, chunk by chunk on the copy stream behind the gather (page-locked memory, texts

@@ -525,6 +525,52 @@ public:
     }
 };
 
+// tdc::LZSSSlidingWindowCompressor<ASCIICoder | BitCoder | EliasGammaCoder | EliasDeltaCoder>  (compressors/
+// LZSSSlidingWindowCompressor.hpp:15-144), the algorithm `lzss`: no input restrictions.  The reference's meta gives coder no default, so
+// `lzss` without one is refused; window (16) must be in 1 .. 4096, threshold defaults to 3.  The parse runs on the device.
+class LZSSSlidingWindowCompressor : public Compressor {
+    AlgorithmValue m_opts;
+    std::shared_ptr<GpuContext> m_ctx;
+    int m_device = 0;
+    int m_coder = TDC_GPU_CODER_BIT;
+    long m_window = 16;
+public:
+    tdc_gpu_stats last_stats{};
+    void set_device(int d) { m_device = d; }
+    LZSSSlidingWindowCompressor(AlgorithmValue opts, std::shared_ptr<GpuContext> ctx) : m_opts(std::move(opts)), m_ctx(std::move(ctx)) {
+        const std::string coder = m_opts.get("coder", "");
+        if (coder == "bit") m_coder = TDC_GPU_CODER_BIT;
+        else if (coder == "ascii") m_coder = TDC_GPU_CODER_ASCII;
+        else if (coder == "gamma") m_coder = TDC_GPU_CODER_GAMMA;
+        else if (coder == "delta") m_coder = TDC_GPU_CODER_DELTA;
+        else throw std::runtime_error("No implementation found for compressor lzss(coder=" + coder + ")");   // Registry.hpp:214
+        m_window = m_opts.get_int("window", 16);
+        if (m_window < 1 || m_window > 4096) throw std::runtime_error("lzss: window=" + m_opts.get("window", "16") + " is not available (1 .. 4096)");
+        if (m_opts.get_int("threshold", 3) < 0) throw std::runtime_error("lzss: threshold must not be negative");
+    }
+    void compress(Input& input, Output& output) override {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const bytes& in = input.raw();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_lzss_sw_compress(m_ctx->h, in.data(), in.size(), (uint32_t)m_window, (uint32_t)m_opts.get_int("threshold", 3),
+                                                m_coder, &out, &out_len, &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
+    }
+    // :120-143 -- tokens until the stream ends, on the host (tdc_lzss_sw_decode; there is no device decoder).  The window comes from the
+    // algorithm id in the file's header (16 if it names none); only coder=bit needs it.
+    void decompress(Input& input, Output& output) override {
+        const bytes& in = input.raw();
+        size_t n = 0;
+        int rc = tdc_lzss_sw_decode(in.data(), in.size(), m_coder, (uint32_t)m_window, nullptr, 0, &n);
+        bytes text(n ? n : 1);
+        if (!rc) rc = tdc_lzss_sw_decode(in.data(), in.size(), m_coder, (uint32_t)m_window, text.data(), n, &n);
+        if (rc) throw std::runtime_error(std::string("lzss: corrupt stream (") + tdc_gpu_strerror(rc) + ")");
+        output.write(text.data(), n);
+    }
+};
+
 // tdc::BWTCompressor (compressors/BWTCompressor.hpp:14-67, ds/bwt.hpp): the Burrows-Wheeler transform of the escaped, 0-terminated view;
 // n bytes out, no header.
 class BWTCompressor : public Compressor {
@@ -713,6 +759,7 @@ inline std::vector<std::string> registered_algorithms() {
              "lzw(coder=gamma)                                                            [host parse + MI355X gamma packer]",
              "lzw(coder=bit, dec=gpu)                                                     [decompression on the MI355X: codes read side by side, phrases expanded by pointer jumping]",
              "lzw(coder=gamma, dec=gpu)                                                   [decompression parsed and expanded on the MI355X]",
+             "lzss(coder=bit | ascii | gamma | delta, window=16, threshold=3)             [sliding-window LZ77 factorized on the MI355X, window 1 .. 4096; host decoder]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
              "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
              "rle                                                                         [MI355X; host decoder]",
@@ -746,6 +793,12 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
     }
     if (av.name == "lzw") {
         auto z = std::make_unique<LZWCompressor>(parse_algorithm_id(id, {"coder", "lz78trie", "dict_size", "dec"}), std::move(ctx));
+        z->set_device(device);
+        s.compressor = std::move(z);
+        return s;
+    }
+    if (av.name == "lzss") {
+        auto z = std::make_unique<LZSSSlidingWindowCompressor>(parse_algorithm_id(id, {"coder", "window", "threshold"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;

@@ -111,7 +111,7 @@ public:
 class BitIStream {
     const uint8_t* m_p; size_t m_n, m_idx = 0;
     uint8_t m_current = 0, m_next = 0, m_final_bits = 0, m_cursor = 0;
-    bool m_is_final = false;
+    bool m_is_final = false, m_overrun = false;
     void read_next() {
         m_current = m_next; m_cursor = 7;
         if (m_idx < m_n) {
@@ -124,9 +124,10 @@ public:
         if (n) { m_next = m_p[m_idx++]; read_next(); } else { m_is_final = true; }
     }
     bool eof() const { return m_is_final && m_cursor <= (7 - m_final_bits); }
+    bool overrun() const { return m_overrun; }               // a bit has been asked for behind the end (it read as 0)
     size_t size_bytes() const { return m_n; }
     unsigned read_bit() {
-        if (eof()) return 0;
+        if (eof()) { m_overrun = true; return 0; }
         unsigned bit = (m_current >> m_cursor) & 1;
         if (m_cursor) --m_cursor; else read_next();
         return bit;
