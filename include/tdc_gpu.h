@@ -360,7 +360,7 @@ int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t 
  * text (window 3, "aaaaaaaa": lengths 4 and 5 in 2 bits).  On such inputs the call returns TDC_GPU_ERR_UNSUPPORTED and writes nothing to
  * `out`; the other three coders ignore the range and code them normally.
  * stats (may be NULL): n, out_len, factors, flen_max, ms_h2d, ms_factorize, ms_encode, ms_d2h, ms_total, arena_bytes.
- * There is no device decoder (DESIGN.md section 5.7 says why): streams are decoded by tdc_lzss_sw_decode. */
+ * Streams are decoded by tdc_gpu_lzss_sw_decompress (on the device) or by tdc_lzss_sw_decode (the host loop, its specification). */
 int tdc_gpu_lzss_sw_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, int coder,
                              uint8_t** out, size_t* out_len, tdc_gpu_stats* stats);
 /* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small. */
@@ -372,6 +372,25 @@ size_t tdc_gpu_lzss_sw_bound(size_t n, uint32_t window, int coder);
  * tdc_lzss_sw_factors computes on the host */
 int tdc_gpu_lzss_sw_factorize(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint32_t window, uint32_t threshold,
                               uint32_t** pos, uint32_t** src, uint32_t** len, size_t* z);
+/* LZSSSlidingWindowCompressor::decompress (:120-143) of a stream of tdc_gpu_lzss_sw_compress or of the reference's lzss(coder=...).
+ * coder = TDC_GPU_CODER_BIT, _GAMMA or _DELTA: the token stream is parsed and the references are resolved on the device for streams of
+ * 1 MiB and more (option dec_parse: 2 = every stream, 0 = never; dec_seg, dec_log as for the other decoders); smaller streams and
+ * TDC_GPU_CODER_ASCII go through tdc_lzss_sw_decode, which stays the specification.  tdc_gpu_ctx_last_decode_on_device reports the path.
+ * Any other coder: TDC_GPU_ERR_UNSUPPORTED.  window: the compressor's option -- only coder=bit reads it (the width of the length field;
+ * 0: TDC_GPU_ERR_ARG), and distances may reach back further than it, up to the token's text position.  The empty stream decodes to 0 bytes.
+ * TDC_GPU_ERR_ARG, as from the host loop: a token cut off by the end of the stream, a distance of 0 or above the token's text position,
+ * a malformed gamma / delta field, a token chain that does not advance.  The device reads gamma / delta distance and length fields of
+ * at most 32 value bits and literal codes of at most 8; a wider field (no encoder writes one) is refused there with TDC_GPU_ERR_ARG even
+ * where the host loop would read it -- coder=bit has no such case.  A text of more than 2^32 - 2 bytes: TDC_GPU_ERR_TOO_LARGE, decided
+ * before anything of the text's size is allocated.
+ * *out is malloc'd (tdc_gpu_free).  factors (may be NULL): the number of factor tokens; rounds (may be NULL): pointer-jumping rounds of
+ * the reference resolver (both 0 on the host path). */
+int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window,
+                               uint8_t** out, size_t* out_len, uint64_t* factors, uint32_t* rounds);
+/* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small (nothing
+ * is written to `out` then). */
+int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window,
+                                    uint8_t* out, size_t out_cap, size_t* out_len, uint64_t* factors, uint32_t* rounds);
 
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG

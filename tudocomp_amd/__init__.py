@@ -495,6 +495,31 @@ class Context:
         out = [np.frombuffer(self._take(x, z.value * 4), dtype=np.uint32).copy() for x in (p, s, l)]
         return out[0], out[1], out[2]
 
+    def lzss_sw_decompress(self, stream, window=16, coder=CODER_BIT):
+        """LZSSSlidingWindowCompressor::decompress: returns the text and {"factors", "rounds", "device_parse"}.  bit, gamma and delta
+        streams of 1 MiB and more are parsed on the device (option dec_parse: 2 = every stream, 0 = never); ascii streams and smaller
+        ones go through the host loop (lzss_sw_decode).  Only coder=bit reads `window`."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self._L.tdc_gpu_lzss_sw_decompress(self._h, _ptr(a) if len(a) else None, len(a), int(coder), int(window), ctypes.byref(p),
+                                                       ctypes.byref(n), ctypes.byref(f), ctypes.byref(r)))
+        return self._take(p, n.value), {"factors": f.value, "rounds": r.value,
+                                        "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
+    def lzss_sw_decompress_into(self, stream, out, window=16, coder=CODER_BIT):
+        """lzss_sw_decompress into a caller-owned buffer (a PinnedBuffer or a writable uint8 array; `stream` may be a PinnedBuffer too):
+        returns (text length, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the text length."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n = ctypes.c_size_t()
+        f, r = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.tdc_gpu_lzss_sw_decompress_into(self._h, _ptr(a) if len(a) else None, len(a), int(coder), int(window), _ptr(oa), oa.size,
+                                                     ctypes.byref(n), ctypes.byref(f), ctypes.byref(r))
+        if rc:
+            self._raise_required(rc, n.value)
+        return n.value, {"factors": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
     def lz78_compress(self, data, coder=CODER_GAMMA):
         """LZ78Compressor<EliasGammaCoder>::compress on raw bytes (no escaping).  Returns (stream, stats)."""
         a = _u8(data)
@@ -1027,16 +1052,19 @@ class LZWCompressor:
 class LZSSSlidingWindowCompressor:
     """Mirror of tdc::LZSSSlidingWindowCompressor<coder> (compressors/LZSSSlidingWindowCompressor.hpp:15-144), the algorithm `lzss`; no
     input restrictions.  coder: ascii, bit, gamma or delta (it has no default in the reference); window 1 .. 4096, threshold.  The parse
-    runs on the device; decompress() is the host loop (lzss_sw_decode) -- there is no device decoder."""
+    runs on the device.  dec="host": decompress() is the host loop (lzss_sw_decode), which needs no context; dec="gpu" (an addition, as
+    for lz78 / lzw): the device decoder (tdc_gpu_lzss_sw_decompress).  The stream is the same either way."""
 
     _CODERS = {"ascii": CODER_ASCII, "bit": CODER_BIT, "gamma": CODER_GAMMA, "delta": CODER_DELTA}
 
-    def __init__(self, ctx, coder=None, window=16, threshold=3):
+    def __init__(self, ctx, coder=None, window=16, threshold=3, dec="host"):
         if coder not in self._CODERS:
             raise RuntimeError("No implementation found for compressor lzss(coder=%s)" % coder)
         if not 1 <= int(window) <= 4096:
             raise RuntimeError("lzss: window=%s is not available (1 .. 4096)" % (window,))
-        self.ctx, self.coder, self.window, self.threshold = ctx, self._CODERS[coder], int(window), int(threshold)
+        if dec not in ("host", "gpu"):
+            raise RuntimeError("lzss: dec must be host or gpu")
+        self.ctx, self.coder, self.window, self.threshold, self.dec = ctx, self._CODERS[coder], int(window), int(threshold), dec
         self.last_stats = None
 
     def compress(self, data):
@@ -1045,6 +1073,10 @@ class LZSSSlidingWindowCompressor:
         return out
 
     def decompress(self, stream):
+        if self.dec == "gpu":
+            if self.ctx is None:
+                raise RuntimeError("lzss: dec=gpu needs a context")
+            return self.ctx.lzss_sw_decompress(stream, self.window, self.coder)[0]
         return lzss_sw_decode(stream, self.coder, self.window)
 
 

@@ -36,7 +36,7 @@ SYMBOLS = [
     "tdc_gpu_lzw_compress", "tdc_gpu_lzw_decompress", "tdc_gpu_lzw_decompress_into", "tdc_lzw_factors", "tdc_lzw_decode",
     "tdc_gpu_lzss_lcp_compress_into", "tdc_gpu_lzss_lcp_bound", "tdc_gpu_lzss_lcp_decompress", "tdc_gpu_lzss_lcp_decompress_into", "tdc_lzss_decode",
     "tdc_gpu_lzss_sw_compress", "tdc_gpu_lzss_sw_compress_into", "tdc_gpu_lzss_sw_bound", "tdc_gpu_lzss_sw_factorize", "tdc_lzss_sw_factors",
-    "tdc_lzss_sw_decode",
+    "tdc_lzss_sw_decode", "tdc_gpu_lzss_sw_decompress", "tdc_gpu_lzss_sw_decompress_into",
 ]
 
 
@@ -187,6 +187,8 @@ def load():
     L.tdc_gpu_lzss_sw_factorize.argtypes = [vp, vp, sz, u32, u32, pvp, pvp, pvp, psz]
     L.tdc_lzss_sw_factors.argtypes = [vp, sz, u32, u32, pvp, pvp, pvp, psz]
     L.tdc_lzss_sw_decode.argtypes = [vp, sz, i32, u32, vp, sz, psz]
+    L.tdc_gpu_lzss_sw_decompress.argtypes = [vp, vp, sz, i32, u32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lzss_sw_decompress_into.argtypes = [vp, vp, sz, i32, u32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     L.tdc_gpu_option_count.argtypes = []
     L.tdc_gpu_option_name.argtypes = [i32]

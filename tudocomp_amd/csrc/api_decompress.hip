@@ -1,4 +1,4 @@
-// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78 and lzw decompression.
+// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw and lzss decompression.
 #include "api.hpp"
 #include "decode.hpp"
 #include "../host/tdc_coders.hpp"
@@ -80,6 +80,41 @@ void lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int cod
     ctx->last_decode_device = (int)ds.device_parse;
     sink_commit(s, n);
 }
+
+// LZSSSlidingWindowCompressor::decompress.  bit, gamma, delta: the device where decode_lzss_sw takes the stream, else -- and for ascii --
+// the host loop that is its specification (tdc_lzss_sw_decode).
+void lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, Sink s, uint64_t* factors, uint32_t* rounds) {
+    ctx->last_decode_device = 0;
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA && coder != TDC_GPU_CODER_ASCII)
+        throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss: coder must be bit, gamma, delta or ascii"};
+    if (coder == TDC_GPU_CODER_BIT && window == 0) throw ArgError{TDC_GPU_ERR_ARG, "lzss: coder=bit needs the window (the width of the length field)"};
+    if (!stream && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    DecodeStats ds;
+    size_t n = 0, need = 0;
+    bool dev = false;
+    if (coder != TDC_GPU_CODER_ASCII) {
+        const int kind = coder == TDC_GPU_CODER_BIT ? 0 : coder == TDC_GPU_CODER_GAMMA ? 1 : 2;
+        dev = run_decoder(s, "lzss: the stream decodes to more than 2^32 - 2 bytes", &need,
+                          [&] { return (size_t)decode_lzss_sw(ctx->c, stream, len, kind, window, s, &need, &ds, &n); }) != 0;
+    }
+    if (!dev) {
+        std::vector<uint8_t> text;
+        const int rc = lzss_sw_decode_host(stream, len, coder, window, text);
+        if (rc == TDC_GPU_ERR_TOO_LARGE) throw ArgError{rc, "lzss: the stream decodes to more than 2^32 - 2 bytes"};
+        if (rc == TDC_GPU_ERR_OOM) throw std::bad_alloc();
+        if (rc) throw ArgError{rc, "lzss: corrupt stream"};
+        n = text.size();
+        sink_fit(s, n);
+        u8* dst = decode_dest(s, n);
+        if (n) memcpy(dst, text.data(), n);
+        ds = DecodeStats();
+    }
+    if (factors) *factors = ds.factors;
+    if (rounds) *rounds = ds.rounds;
+    ctx->last_decode_device = (int)ds.device_parse;
+    sink_commit(s, n);
+}
 }  // namespace
 
 extern "C" {
@@ -129,6 +164,16 @@ int tdc_gpu_lzw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, 
 int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap,
                                 size_t* out_len, uint64_t* codes, uint32_t* rounds) {
     return guarded(ctx, [&] { lzw_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), codes, rounds); });
+}
+
+int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t** out, size_t* out_len,
+                               uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzss_sw_decompress(ctx, stream, len, coder, window, sink_malloc(out, out_len, "NULL argument"), factors, rounds); });
+}
+
+int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap,
+                                    size_t* out_len, uint64_t* factors, uint32_t* rounds) {
+    return guarded(ctx, [&] { lzss_sw_decompress(ctx, stream, len, coder, window, sink_into(out, out_cap, out_len), factors, rounds); });
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <functional>
+#include <initializer_list>
+#include <utility>
 
 namespace tdc {
 
@@ -113,5 +115,8 @@ size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, s
 // out.into is too small.  ids / chars lie in the arena, nothing above them is live.
 size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
                       const DecTick& tick);
+// The arena is too small for what follows: the live arrays (pointer, bytes) travel to the host and back into an arena of `bytes`;
+// the pointers are updated, everything else in the arena is gone (lz78_decode.hip).
+void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live);
 
 }  // namespace tdc

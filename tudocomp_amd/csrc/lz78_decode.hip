@@ -179,6 +179,8 @@ __global__ void lzw_literal_kernel(const u32* __restrict__ fpos, const u32* __re
         if (codes[k] < 256u) text[fpos[k]] = (u8)codes[k];
 }
 
+}  // namespace
+
 // The arena is too small for what follows: the live arrays travel to the host and back into an arena of `bytes` (the size this call
 // would have needed without moving, so that the next call of the same size on this context does not move again).
 void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live) {
@@ -197,8 +199,6 @@ void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, 
     }
     HIP_TRY(hipStreamSynchronize(c.stream));
 }
-
-}  // namespace
 
 size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick) {
     hipStream_t s = c.stream;

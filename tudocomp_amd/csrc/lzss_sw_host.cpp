@@ -79,26 +79,36 @@ extern "C" int tdc_lzss_sw_factors(const uint8_t* in, size_t n, uint32_t window,
     return TDC_GPU_OK;
 }
 
-extern "C" int tdc_lzss_sw_decode(const uint8_t* in, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap, size_t* out_len) {
-    if ((!in && len) || !out_len) return TDC_GPU_ERR_ARG;
-    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA && coder != TDC_GPU_CODER_ASCII)
-        return TDC_GPU_ERR_UNSUPPORTED;
-    if (coder == TDC_GPU_CODER_BIT && window == 0) return TDC_GPU_ERR_ARG;      // (the other coders ignore the range: no window needed)
+// the loop of one coder with its exceptions as statuses (coder and window checked by the caller); also the path of small streams of
+// tdc_gpu_lzss_sw_decompress (api_decompress.hip)
+namespace tdc {
+int lzss_sw_decode_host(const uint8_t* in, size_t len, int coder, uint32_t window, std::vector<uint8_t>& text) {
     try {
-        std::vector<uint8_t> text;
         switch (coder) {
             case TDC_GPU_CODER_BIT:   lzss_sw_decode_loop<BitCoder::Decoder>(in, len, window, text); break;
             case TDC_GPU_CODER_GAMMA: lzss_sw_decode_loop<EliasGammaCoder::Decoder>(in, len, window, text); break;
             case TDC_GPU_CODER_DELTA: lzss_sw_decode_loop<EliasDeltaCoder::Decoder>(in, len, window, text); break;
             default:                  lzss_sw_decode_loop<ASCIICoder::Decoder>(in, len, window, text); break;
         }
-        *out_len = text.size();
-        if (!out) return TDC_GPU_OK;
-        if (text.size() > out_cap) return TDC_GPU_ERR_ARG;
-        if (!text.empty()) memcpy(out, text.data(), text.size());
         return TDC_GPU_OK;
     } catch (const std::length_error&) { return TDC_GPU_ERR_TOO_LARGE;
     } catch (const std::runtime_error&) { return TDC_GPU_ERR_ARG;
     } catch (const std::bad_alloc&) { return TDC_GPU_ERR_OOM;
     } catch (...) { return TDC_GPU_ERR_INTERNAL; }
+}
+}  // namespace tdc
+
+extern "C" int tdc_lzss_sw_decode(const uint8_t* in, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if ((!in && len) || !out_len) return TDC_GPU_ERR_ARG;
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA && coder != TDC_GPU_CODER_ASCII)
+        return TDC_GPU_ERR_UNSUPPORTED;
+    if (coder == TDC_GPU_CODER_BIT && window == 0) return TDC_GPU_ERR_ARG;      // (the other coders ignore the range: no window needed)
+    std::vector<uint8_t> text;
+    const int rc = tdc::lzss_sw_decode_host(in, len, coder, window, text);
+    if (rc) return rc;
+    *out_len = text.size();
+    if (!out) return TDC_GPU_OK;
+    if (text.size() > out_cap) return TDC_GPU_ERR_ARG;
+    if (!text.empty()) memcpy(out, text.data(), text.size());
+    return TDC_GPU_OK;
 }

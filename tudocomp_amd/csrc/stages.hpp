@@ -275,6 +275,13 @@ struct LzssSwStats { u64 factors = 0; u32 flen_max = 0; bool truncates = false; 
 size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const u32* fac, size_t ntok, u32 window, int kind,
                              u8* d_out, size_t out_cap, LzssSwStats* st);
 size_t lzss_sw_bound(size_t n, u32 window, int kind);
+// :120-143 -- streams of BitCoder (kind 0), EliasGammaCoder (1) and EliasDeltaCoder (2) parsed and resolved on the device
+// (lzss_sw_decode.hip); false: this stream keeps the host loop (option dec_parse, or more tokens than 32-bit indices count), nothing has
+// been written.  *n_out: the text length; *need (nullable) receives it as soon as it is known -- also when out.into is too small
+// (HipError hipErrorOutOfMemory).  Malformed input: StreamFormatError; a text of more than 2^32 - 2 bytes: DecodeTooLarge.
+bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, Sink& out, size_t* need, DecodeStats* st, size_t* n_out);
+// the host loop behind tdc_lzss_sw_decode (lzss_sw_host.cpp): a status of tdc_gpu.h, the text
+int lzss_sw_decode_host(const u8* in, size_t len, int coder, u32 window, std::vector<u8>& text);
 
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform

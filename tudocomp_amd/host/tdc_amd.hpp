@@ -558,10 +558,20 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
-    // :120-143 -- tokens until the stream ends, on the host (tdc_lzss_sw_decode; there is no device decoder).  The window comes from the
+    // :120-143 -- tokens until the stream ends: the host loop (tdc_lzss_sw_decode), which needs no device; dec=gpu (an addition, as for
+    // lz78 / lzw): the device decoder (tdc_gpu_lzss_sw_decompress).  The stream is the same either way.  The window comes from the
     // algorithm id in the file's header (16 if it names none); only coder=bit needs it.
     void decompress(Input& input, Output& output) override {
         const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_lzss_sw_decompress(m_ctx->h, in.data(), in.size(), m_coder, (uint32_t)m_window, &out, &out_len, nullptr, nullptr);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
         size_t n = 0;
         int rc = tdc_lzss_sw_decode(in.data(), in.size(), m_coder, (uint32_t)m_window, nullptr, 0, &n);
         bytes text(n ? n : 1);
@@ -760,6 +770,7 @@ inline std::vector<std::string> registered_algorithms() {
              "lzw(coder=bit, dec=gpu)                                                     [decompression on the MI355X: codes read side by side, phrases expanded by pointer jumping]",
              "lzw(coder=gamma, dec=gpu)                                                   [decompression parsed and expanded on the MI355X]",
              "lzss(coder=bit | ascii | gamma | delta, window=16, threshold=3)             [sliding-window LZ77 factorized on the MI355X, window 1 .. 4096; host decoder]",
+             "lzss(coder=bit | gamma | delta, dec=gpu)                                    [decompression parsed and resolved on the MI355X for streams of 1 MiB and more; ascii: host loop]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
              "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
              "rle                                                                         [MI355X; host decoder]",
@@ -798,7 +809,7 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
         return s;
     }
     if (av.name == "lzss") {
-        auto z = std::make_unique<LZSSSlidingWindowCompressor>(parse_algorithm_id(id, {"coder", "window", "threshold"}), std::move(ctx));
+        auto z = std::make_unique<LZSSSlidingWindowCompressor>(parse_algorithm_id(id, {"coder", "window", "threshold", "dec"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;
