@@ -39,7 +39,7 @@ typedef enum {
 
 /* coder ids (option `coder`, etc/registry_config.py:28-31,138-142) */
 enum { TDC_GPU_CODER_HUFF = 0, TDC_GPU_CODER_GAMMA = 1, TDC_GPU_CODER_ARITH = 2, TDC_GPU_CODER_ASCII = 3, TDC_GPU_CODER_SLE = 4,
-       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw, lzss_lcp, lzss */, TDC_GPU_CODER_DELTA = 6 /* EliasDeltaCoder: lzss_lcp, lzss */ };
+       TDC_GPU_CODER_BIT = 5 /* BitCoder: lzw, lzss_lcp, lzss, repair */, TDC_GPU_CODER_DELTA = 6 /* EliasDeltaCoder: lzss_lcp, lzss, repair */ };
 /* coder=sle(kmer=K) (coders/SLECoder.hpp:36-40; the reference's default is 3): the option travels in bits 8.. of `coder` */
 #define TDC_GPU_CODER_SLE_K(K) (TDC_GPU_CODER_SLE | ((K) << 8))
 /* factorization strategy of lcpcomp (option `comp`, LCPCompressor.hpp:87): ArraysComp or PLCPPeaksStrategy */
@@ -88,6 +88,12 @@ typedef struct {
     float    pipe_ms[8];        /* ... and what stage i took (host clock around a synchronisation; only with option pipe_log)       */
     uint32_t ranges_early;      /* tdc_gpu_lcpcomp_compress_into: rank ranges of the flatten stage whose pack was enqueued before the stage returned (flatten_chunks) */
     uint32_t reserved0;
+    uint64_t rules;             /* tdc_gpu_repair_*: "rules" (RePairCompressor.hpp:204), ...                                          */
+    uint64_t replaced;          /* ... "replaced" (:205): pairs replaced over all rounds, ...                                        */
+    uint32_t tie_rounds;        /* ... rounds in which more than one pair held the largest count, ...                               */
+    uint32_t rebuilds;          /* ... and how often the digram table was rebuilt by a recount of the live sequence                   */
+    float ms_round_first, ms_round_last, ms_round_tie;   /* repair: the first round, the last one, the sum over the tie rounds (host clock, read-back to read-back) */
+    float reserved1;
 } tdc_gpu_stats;
 
 /* ---- context -------------------------------------------------------------------------------------------- */
@@ -392,6 +398,40 @@ int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t l
 int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window,
                                     uint8_t* out, size_t out_cap, size_t* out_len, uint64_t* factors, uint32_t* rounds);
 
+/* ---- repair: RePairCompressor<BitCoder | ASCIICoder | EliasGammaCoder | EliasDeltaCoder> (compressors/RePairCompressor.hpp:96-336;
+ * DESIGN.md section 5.8): the Re-Pair grammar, built ON THE DEVICE.  No input restrictions (raw bytes, no sentinel).  Symbols are 32-bit:
+ * 0 .. 255 are bytes, 256 + k is rule k; a rule is l << 32 | r.  Per round every adjacent pair of the live sequence is counted
+ * (occurrences overlap: aaa counts (a,a) twice); with M the largest count, the pair whose M-th occurrence comes first among the pairs
+ * that count M becomes the next rule (the reference takes a pair over when its running count exceeds the best so far strictly); M <= 1
+ * ends the loop.  The pair is replaced left to right, continuing behind a replaced pair: a run a^k loses floor(k / 2) pairs from its
+ * left end.  max_rules (the reference's option; 0 = unlimited) ends the loop after that many rules.  The empty input, on which the
+ * reference is undefined, is defined as no rules and no symbols.
+ * The stream: the number of rules under len_r, both sides of rule i -- a flag, then the byte under literal_r or x - 256 under Range(i) --,
+ * then the start sequence under Range(rules); the bit stream's terminator ends it.
+ * coder: TDC_GPU_CODER_BIT (the reference's default), _ASCII, _GAMMA or _DELTA; anything else (huff among it, whose literal order is not
+ * built): TDC_GPU_ERR_UNSUPPORTED.  n above 2^30: TDC_GPU_ERR_TOO_LARGE.  A device that cannot hold the arena (DESIGN.md section 5.8 states
+ * the formula): TDC_GPU_ERR_OOM before anything is written.
+ * Options of the context: repair_recount (1: the digram table is recounted in every round instead of taking the round's deltas),
+ * repair_table_bits (8 .. 30: the first capacity of the table), repair_log.
+ * stats (may be NULL): n, out_len, rules, replaced, tie_rounds, rebuilds, ms_round_first / _last / _tie, ms_h2d, ms_factorize (the grammar),
+ * ms_encode, ms_d2h, ms_total, arena_bytes. */
+int tdc_gpu_repair_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, int coder, uint8_t** out, size_t* out_len,
+                            tdc_gpu_stats* stats);
+/* The same into the CALLER's buffer of out_cap bytes; TDC_GPU_ERR_OOM with the required size in *out_len if it is too small. */
+int tdc_gpu_repair_compress_into(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, int coder, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, tdc_gpu_stats* stats);
+/* worst-case stream length for n input bytes (what an _into buffer needs at most); 0 for a coder or a length the call does not take */
+size_t tdc_gpu_repair_bound(size_t n, int coder);
+/* the grammar on its own: *rules (nrules entries, l << 32 | r) and *start (nstart symbols) are malloc'd (tdc_gpu_free); what
+ * tdc_repair_grammar computes on the host.  stats (may be NULL): the repair fields and ms_factorize. */
+int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, uint64_t** rules, size_t* nrules,
+                           uint32_t** start, size_t* nstart, tdc_gpu_stats* stats);
+/* RePairCompressor::decompress behind the signature of the other decompressing entry points: the host loop tdc_repair_decode (there is
+ * no device decoder yet: DESIGN.md section 5.8 names it as the follow-up); its status codes.  *out is malloc'd (tdc_gpu_free); _into:
+ * TDC_GPU_ERR_OOM with the required size in *out_len if out_cap is too small. */
+int tdc_gpu_repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len);
+int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
+
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG
  * for an inner 0, TDC_GPU_ERR_TOO_LARGE).  out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0): n bytes, no header.  The suffix array is the one
@@ -498,6 +538,15 @@ int tdc_lzss_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size
  * bytes.  A factor of length 0 decodes to nothing, as in the reference. */
 int tdc_lzss_sw_decode(const uint8_t* in, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap, size_t* out_len);
 
+/* RePairCompressor::decompress (:287-336) on the host with the Decoder of TDC_GPU_CODER_BIT, _ASCII, _GAMMA or _DELTA (else
+ * TDC_GPU_ERR_UNSUPPORTED); rules are expanded with an explicit stack, not by recursion.  out == NULL: only *out_len is computed.
+ * TDC_GPU_ERR_ARG for: a side of rule i that names a rule >= i (the reference would recurse for ever -- Range(i) holds i itself under
+ * BitCoder when i is a power of two), a start symbol that names a rule >= rules, a field cut off by the end of the stream (the reference
+ * reads zeros there), more rules than the stream has room for, and what the field readers refuse.  The lengths of the rules are summed
+ * in 64 bits with saturation BEFORE any text is written: more than 2^32 - 2 bytes is TDC_GPU_ERR_TOO_LARGE, a buffer of fewer than
+ * *out_len bytes TDC_GPU_ERR_OOM with the length in *out_len and `out` untouched. */
+int tdc_repair_decode(const uint8_t* in, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
+
 /* HuffmanCoder::Encoder + lzss::encode_text on a caller-supplied factor list sorted by pos (LZSSCoding.hpp:18-92) */
 int tdc_gpu_encode_huff(tdc_gpu_ctx* ctx, const uint8_t* text, size_t n, const uint32_t* pos, const uint32_t* src,
                         const uint32_t* len, size_t z, uint8_t** out, size_t* out_len);
@@ -534,6 +583,10 @@ int tdc_lzw_factors(const uint8_t* in, size_t n, uint32_t** codes, size_t* z);
  * pos / src / len are malloc'd (tdc_gpu_free).  Any window >= 1 (0: TDC_GPU_ERR_ARG); n above 2^32 - 2: TDC_GPU_ERR_TOO_LARGE. */
 int tdc_lzss_sw_factors(const uint8_t* in, size_t n, uint32_t window, uint32_t threshold, uint32_t** pos, uint32_t** src, uint32_t** len,
                         size_t* z);
+/* compressors/RePairCompressor.hpp:96-178 : the grammar on its own (host, one core, O(rules * n); the specification of
+ * tdc_gpu_repair_grammar).  *rules (l << 32 | r) and *start are malloc'd (tdc_gpu_free).  max_rules 0: unlimited.  n above 2^30:
+ * TDC_GPU_ERR_TOO_LARGE. */
+int tdc_repair_grammar(const uint8_t* in, size_t n, uint64_t max_rules, uint64_t** rules, size_t* nrules, uint32_t** start, size_t* nstart);
 /* The start-up check of tdc_gpu_ctx_create() on its own (no GPU): rebuilds two built-in fixture tables (sigma 40 and 200, many
  * equal counts) and compares them with what the reference build yields; TDC_GPU_ERR_INTERNAL if this build's C++ library
  * orders ties differently (coders/HuffmanCoder.hpp:88-120 heap functions, :455 unstable std::sort) -- every call with

@@ -16,8 +16,8 @@ CODER_GAMMA = 1
 CODER_ARITH = 2
 CODER_ASCII = 3
 CODER_SLE = 4            # coder=sle(kmer=k): CODER_SLE | (k << 8), k = 0 means the reference's default 3
-CODER_BIT = 5            # BitCoder: lzw, lzss_lcp, lzss
-CODER_DELTA = 6          # EliasDeltaCoder: lzss_lcp, lzss
+CODER_BIT = 5            # BitCoder: lzw, lzss_lcp, lzss, repair
+CODER_DELTA = 6          # EliasDeltaCoder: lzss_lcp, lzss, repair
 COMP_ARRAYS = 0
 COMP_PLCPPEAKS = 1
 COMP_MAXLCP = 2
@@ -132,6 +132,23 @@ def lzss_sw_factors(data, window=16, threshold=3):
             L.tdc_gpu_free(x)
 
 
+def repair_grammar(data, max_rules=0):
+    """The Re-Pair grammar on its own (host, one core, O(rules * n); compressors/RePairCompressor.hpp:96-178): (rules, start) as numpy
+    arrays -- rules[k] = l << 32 | r (uint64; rule k is symbol 256 + k), start the sequence that is left (uint32)."""
+    L = _native.load()
+    a = _u8(data)
+    r, s, nr, ns = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_size_t()
+    rc = L.tdc_repair_grammar(_ptr(a) if len(a) else None, len(a), int(max_rules), ctypes.byref(r), ctypes.byref(nr), ctypes.byref(s), ctypes.byref(ns))
+    if rc:
+        raise TdcGpuError(rc, "tdc_repair_grammar")
+    try:
+        return (np.frombuffer(ctypes.string_at(r, nr.value * 8), dtype=np.uint64).copy(),
+                np.frombuffer(ctypes.string_at(s, ns.value * 4), dtype=np.uint32).copy())
+    finally:
+        L.tdc_gpu_free(r)
+        L.tdc_gpu_free(s)
+
+
 def option_names():
     """Names of the library's options (tdc_gpu_ctx_set_option)."""
     L = _native.load()
@@ -220,6 +237,16 @@ def lzss_sw_decode(data, coder=CODER_BIT, window=16):
 def lzss_sw_bound(n, window=16, coder=CODER_BIT):
     """worst-case length of an lzss stream for n input bytes (0: a coder or a window lzss does not take)"""
     return _native.load().tdc_gpu_lzss_sw_bound(n, int(window), int(coder))
+
+
+def repair_decode(data, coder=CODER_BIT):
+    """RePairCompressor::decompress (:287-336) on the host, rules expanded with an explicit stack"""
+    return _host_decode("tdc_repair_decode", data, int(coder))
+
+
+def repair_bound(n, coder=CODER_BIT):
+    """worst-case length of a repair stream for n input bytes (0: a coder or a length repair does not take)"""
+    return _native.load().tdc_gpu_repair_bound(n, int(coder))
 
 
 def lzss_lcp_bound(n, coder=CODER_HUFF):
@@ -519,6 +546,55 @@ class Context:
         if rc:
             self._raise_required(rc, n.value)
         return n.value, {"factors": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
+    def repair_compress(self, data, max_rules=0, coder=CODER_BIT):
+        """RePairCompressor<coder>::compress on raw bytes (no escaping), the grammar built on the device; coder: CODER_BIT, _ASCII, _GAMMA
+        or _DELTA.  Returns (stream, stats)."""
+        a = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_repair_compress(self._h, _ptr(a) if len(a) else None, len(a), int(max_rules), coder,
+                                                    ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)))
+        return self._take(out, n.value), st.as_dict()
+
+    def repair_compress_into(self, data, n, out, max_rules=0, coder=CODER_BIT):
+        """repair_compress of the first n bytes of `data` into a caller-owned buffer (PinnedBuffer or writable uint8 array; repair_bound
+        sizes it): returns (out_len, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the length."""
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        ol, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_repair_compress_into(self._h, _ptr(ta) if n else None, n, int(max_rules), coder, _ptr(oa), oa.size,
+                                                  ctypes.byref(ol), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, ol.value)
+        return ol.value, st.as_dict()
+
+    repair_bound = staticmethod(repair_bound)
+
+    def repair_grammar(self, data, max_rules=0):
+        """the grammar from the device: (rules, start, stats) -- rules[k] = l << 32 | r (uint64), start the sequence that is left (uint32)"""
+        a = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        r, s, nr, ns, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_size_t(), Stats()
+        self._check(self._L.tdc_gpu_repair_grammar(self._h, _ptr(a) if len(a) else None, len(a), int(max_rules), ctypes.byref(r), ctypes.byref(nr),
+                                                   ctypes.byref(s), ctypes.byref(ns), ctypes.byref(st)))
+        return (np.frombuffer(self._take(r, nr.value * 8), dtype=np.uint64).copy(), np.frombuffer(self._take(s, ns.value * 4), dtype=np.uint32).copy(),
+                st.as_dict())
+
+    def repair_decompress(self, stream, coder=CODER_BIT):
+        """tdc_gpu_repair_decompress: the host loop behind the signature of the other decompressing entry points"""
+        a = _u8(stream)
+        out, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.tdc_gpu_repair_decompress(self._h, _ptr(a) if len(a) else None, len(a), coder, ctypes.byref(out), ctypes.byref(n)))
+        return self._take(out, n.value)
+
+    def repair_decompress_into(self, stream, out, coder=CODER_BIT):
+        """the same into a caller-owned buffer: returns the length; too small raises TdcGpuError (status -5) with `required`"""
+        a = _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n = ctypes.c_size_t()
+        rc = self._L.tdc_gpu_repair_decompress_into(self._h, _ptr(a) if len(a) else None, len(a), coder, _ptr(oa), oa.size, ctypes.byref(n))
+        if rc:
+            self._raise_required(rc, n.value)
+        return n.value
 
     def lz78_compress(self, data, coder=CODER_GAMMA):
         """LZ78Compressor<EliasGammaCoder>::compress on raw bytes (no escaping).  Returns (stream, stats)."""
@@ -1078,6 +1154,30 @@ class LZSSSlidingWindowCompressor:
                 raise RuntimeError("lzss: dec=gpu needs a context")
             return self.ctx.lzss_sw_decompress(stream, self.window, self.coder)[0]
         return lzss_sw_decode(stream, self.coder, self.window)
+
+
+class RePairCompressor:
+    """Mirror of tdc::RePairCompressor<coder> (compressors/RePairCompressor.hpp:14-337), the algorithm `repair`; no input restrictions.
+    coder: bit (the reference's default), ascii, gamma or delta; max_rules 0 = unlimited.  The grammar is built on the device;
+    decompress() is the host loop (repair_decode) -- there is no device decoder yet."""
+
+    _CODERS = {"bit": CODER_BIT, "ascii": CODER_ASCII, "gamma": CODER_GAMMA, "delta": CODER_DELTA}
+
+    def __init__(self, ctx, coder="bit", max_rules=0):
+        if coder not in self._CODERS:
+            raise RuntimeError("No implementation found for compressor repair(coder=%s)" % coder)
+        if int(max_rules) < 0:
+            raise RuntimeError("repair: max_rules must not be negative")
+        self.ctx, self.coder, self.max_rules = ctx, self._CODERS[coder], int(max_rules)
+        self.last_stats = None
+
+    def compress(self, data):
+        out, st = self.ctx.repair_compress(data, self.max_rules, self.coder)
+        self.last_stats = st
+        return out
+
+    def decompress(self, stream):
+        return repair_decode(stream, self.coder)
 
 
 class LZSSLCPCompressor:

@@ -1,4 +1,4 @@
-// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw and lzss compression -- the upload, the text's arrays, the factors,
+// api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw, lzss and repair compression -- the upload, the text's arrays, the factors,
 // the whole pipeline on host and device buffers.
 #include "api.hpp"
 
@@ -684,6 +684,136 @@ int tdc_gpu_lzss_sw_factorize(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uin
         ev.finish();
         *pos = hp.release<uint32_t>(); *src = hs.release<uint32_t>(); *len = hl.release<uint32_t>(); *z = cnt;
     });
+}
+
+}  // extern "C"
+
+// ---- repair (RePairCompressor; repair.hip) -----------------------------------------------------------------------
+namespace {
+// public coder id -> kind of repair_encode for the coders that need no literal iterator (etc/registry_config.py:13-18,240); -1: none
+int repair_kind(int coder) {
+    switch (coder) {
+        case TDC_GPU_CODER_BIT: return 0;
+        case TDC_GPU_CODER_ASCII: return 1;
+        case TDC_GPU_CODER_GAMMA: return 2;
+        case TDC_GPU_CODER_DELTA: return 3;
+        default: return -1;
+    }
+}
+void repair_check(const uint8_t* in, size_t n) {
+    if (!in && n) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (n > REPAIR_MAX_N) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "repair: input must be at most 2^30 bytes"};
+}
+void repair_fill_stats(tdc_gpu_stats* stats, const RepairStats& rs) {
+    stats->rules = rs.rules; stats->replaced = rs.replaced; stats->tie_rounds = rs.tie_rounds; stats->rebuilds = rs.rebuilds;
+    stats->ms_round_first = rs.ms_first; stats->ms_round_last = rs.ms_last; stats->ms_round_tie = rs.ms_tie;
+}
+
+void repair_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, int coder, Sink s, tdc_gpu_stats* stats) {
+    const int kind = repair_kind(coder);
+    if (kind < 0) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "repair: coder must be bit, ascii, gamma or delta"};
+    repair_check(in, n);
+    sink_check(s, "NULL argument");
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const size_t cap = align_up(repair_bound(n, kind) + 16, 8);                 // (+ 16: the pack's last word)
+    reserve_arena(c, n + 64 + repair_arena(c, n, max_rules) + cap);             // before anything is written
+    Events ev(c);
+    const int e0 = ev.tick();
+    const u8* d_text = upload_plain(c, in, n);
+    const int e1 = ev.tick();
+    u64* d_rules = nullptr; u32* d_start = nullptr;
+    RepairStats rs;
+    repair_grammar(c, d_text, n, max_rules, &d_rules, &d_start, &rs);
+    const int e2 = ev.tick();
+    u8* d_out = c.arena.get<u8>(cap);
+    const size_t len = repair_encode(c, d_rules, (size_t)rs.rules, d_start, rs.nstart, kind, d_out, cap);
+    const int e3 = ev.tick();
+    *s.out_len = len;
+    sink_fit(s, len);
+    sink_download(c, s, d_out, len);
+    const int e4 = ev.tick();
+    if (stats) {
+        stats->n = n; stats->out_len = len; stats->arena_bytes = c.arena.high;
+        repair_fill_stats(stats, rs);
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_d2h, e3, e4); ev.span(&stats->ms_total, e0, e4);
+    }
+    ev.finish();
+    sink_commit(s, len);
+}
+
+// the host loop behind the signature of the other decompressing entry points
+int repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, uint8_t* into, size_t cap, size_t* out_len) {
+    if (!ctx) return TDC_GPU_ERR_ARG;
+    ctx->last_error.clear();
+    if ((!stream && len) || !out_len || (!out && !into)) { ctx->last_error = "NULL argument"; return TDC_GPU_ERR_ARG; }
+    size_t n = 0;
+    int rc = tdc_repair_decode(stream, len, coder, nullptr, 0, &n);
+    if (rc) { ctx->last_error = "repair: the stream is refused (tdc_repair_decode)"; return rc; }
+    *out_len = n;
+    if (into) {
+        if (n > cap) { ctx->last_error = "output buffer too small (*out_len holds the required size)"; return TDC_GPU_ERR_OOM; }
+        return tdc_repair_decode(stream, len, coder, into, cap, &n);
+    }
+    uint8_t* buf = (uint8_t*)malloc(n ? n : 1);
+    if (!buf) { ctx->last_error = "host allocation failed"; return TDC_GPU_ERR_OOM; }
+    rc = tdc_repair_decode(stream, len, coder, buf, n, &n);
+    if (rc) { free(buf); return rc; }
+    *out = buf;
+    return TDC_GPU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t tdc_gpu_repair_bound(size_t n, int coder) { return repair_bound(n, repair_kind(coder)); }
+
+int tdc_gpu_repair_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, int coder, uint8_t** out, size_t* out_len,
+                            tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { repair_compress(ctx, in, n, max_rules, coder, sink_malloc(out, out_len), stats); });
+}
+
+int tdc_gpu_repair_compress_into(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, int coder, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { repair_compress(ctx, in, n, max_rules, coder, sink_into(out, out_cap, out_len), stats); });
+}
+
+int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, uint64_t** rules, size_t* nrules,
+                           uint32_t** start, size_t* nstart, tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] {
+        repair_check(in, n);
+        if (!rules || !nrules || !start || !nstart) throw ArgError{TDC_GPU_ERR_ARG, "output pointer is NULL"};
+        Ctx& c = ctx->c;
+        if (stats) memset(stats, 0, sizeof(*stats));
+        reserve_arena(c, n + 64 + repair_arena(c, n, max_rules));
+        Events ev(c);
+        const int e0 = ev.tick();
+        const u8* d_text = upload_plain(c, in, n);
+        u64* d_rules = nullptr; u32* d_start = nullptr;
+        RepairStats rs;
+        repair_grammar(c, d_text, n, max_rules, &d_rules, &d_start, &rs);
+        const int e1 = ev.tick();
+        HostBuf hr((size_t)rs.rules * 8), hs(rs.nstart * 4);
+        if (rs.rules) HIP_TRY(hipMemcpyAsync(hr.p, d_rules, (size_t)rs.rules * 8, hipMemcpyDeviceToHost, c.stream));
+        if (rs.nstart) HIP_TRY(hipMemcpyAsync(hs.p, d_start, rs.nstart * 4, hipMemcpyDeviceToHost, c.stream));
+        if (stats) {
+            stats->n = n; stats->arena_bytes = c.arena.high;
+            repair_fill_stats(stats, rs);
+            ev.span(&stats->ms_factorize, e0, e1);
+        }
+        ev.finish();
+        *rules = hr.release<uint64_t>(); *nrules = (size_t)rs.rules; *start = hs.release<uint32_t>(); *nstart = rs.nstart;
+    });
+}
+
+int tdc_gpu_repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len) {
+    return repair_decompress(ctx, stream, len, coder, out, nullptr, 0, out_len);
+}
+
+int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (!out) return TDC_GPU_ERR_ARG;
+    return repair_decompress(ctx, stream, len, coder, nullptr, out, out_cap, out_len);
 }
 
 }  // extern "C"

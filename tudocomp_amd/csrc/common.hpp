@@ -209,6 +209,9 @@ struct Ctx {
     int flatten_chunks = 0;        // flatten: rank ranges the rounds run on one after the other (flatten.hip).  0: ranges only where pack and download follow them (host-buffer calls that overlap the two; api_compress.hip picks the count), 1: never, k >= 2: k ranges wherever flatten_factors runs
     int sa_init_syms = 0;          // classic suffix sort: cap on the symbols of the initial key (0: as many as 64 bits hold; tuning)
     int dec_done = 1;              // decompression: final-bit mask in the pointer-jumping rounds (0: A/B switch)
+    int repair_recount = 0;        // repair: 1 = the digram table is rebuilt from the live sequence in every round instead of taking the round's deltas (the cross-check of the deltas; tests)
+    int repair_table_bits = 0;     // repair: 0 = the first capacity of the digram table comes from the text length; 8 .. 30 forces 2^bits slots (small texts reach the rebuild; tests)
+    int repair_log = 0;            // repair: one line per round on stderr
     int dec_log = 0, bwt_log = 0, pipe_log = 0, level_log = 0, wsort_log = 0, eager_dump = 0, small_prof = 0, arena_log = 0;   // diagnostics on stderr
 
     // overlapped D2H of the compressed stream (end-to-end entry point with a caller buffer): while the pack kernel works on the

@@ -19,7 +19,8 @@
 //
 // At the end of the file: encode(sle) = LiteralEncoder<SLECoder> as a byte stage (sle_literals_device, declared in bytestages.hpp),
 // the owner-less use of the SLE machinery below, and the token coder of lzss (lzss_sw_encode_tokens, DESIGN.md
-// section 5.7): the same sink and field writers over a token list instead of position space.
+// section 5.7) and the grammar coder of repair (repair_encode, section 5.8): the same sink and field writers over a token or symbol list
+// instead of position space.
 #include "stages.hpp"
 #include "bytestages.hpp"
 #include "prim.hpp"
@@ -1687,6 +1688,145 @@ size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const 
         }
         LAUNCH_CHECK();
     }
+    bit_stream_terminator(c, d_out, total_bits);
+    HIP_TRY(hipStreamSynchronize(s));
+    c.arena.release(mark);
+    return out_len;
+}
+
+// ---- repair: a grammar through one coder (RePairCompressor.hpp:208-263) -------------------------------------------
+// Field 0 is the number of rules under len_r; fields 1 .. 2R are the sides of the rules -- rule i's under Range(i) --, the rest the start
+// sequence under Range(R).  A symbol is the flag 0 and the byte under literal_r, or the flag 1 and x - 256 under its range.  BitCoder: 32
+// bits for the count, bits_for(i) or bits_for(R) for a rule index -- a function of the field's index alone; gamma / delta ignore the
+// ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.  Same shape as the lzss token coder: bits per tile of 2048
+// fields, their scan, then the pack recomputes the costs and ORs the fields into the zeroed output.
+struct RpField { u32 x, hi; };     // hi: the top of the range
+__device__ __forceinline__ RpField rp_field(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 j) {
+    if (j <= 2ull * R) {
+        const u32 i = (u32)((j - 1) >> 1);
+        const u64 di = rules[i];
+        return RpField{ ((j - 1) & 1) ? (u32)di : (u32)(di >> 32), i };
+    }
+    return RpField{ start[j - 1 - 2ull * R], R };
+}
+template <int KIND> __device__ __forceinline__ u32 rp_count_bits(u32 R) {
+    if (KIND == ENC_TAB) return 32u;
+    if (KIND == ENC_ASCII) return 8u * ascii_int_chars(R);
+    return uni_cost<KIND>(R);
+}
+template <int KIND> __device__ __forceinline__ u32 rp_field_bits(RpField f) {
+    if (KIND == ENC_TAB) return f.x < 256u ? 9u : 1u + uni_bits_for(f.hi);
+    if (KIND == ENC_ASCII) return f.x < 256u ? 16u : 8u * (1u + ascii_int_chars(f.x - 256u));
+    return 1u + uni_cost<KIND>(f.x < 256u ? f.x : f.x - 256u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void rp_tile_bits_kernel(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 nfields,
+                                                            u32 tiles, u64* __restrict__ tile_bits) {
+    __shared__ u32 sm[4];
+    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const u64 j0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
+        u32 sum = 0;
+#pragma unroll
+        for (int k = 0; k < SWT_PER_THREAD; ++k) {
+            const u64 j = j0 + k;
+            if (j < nfields) sum += j == 0 ? rp_count_bits<KIND>(R) : rp_field_bits<KIND>(rp_field(rules, R, start, j));
+        }
+        sum = wave_reduce_sum(sum);
+        if (lane_id() == 0) sm[wave_id()] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_bits[tile] = (u64)sm[0] + sm[1] + sm[2] + sm[3];
+        __syncthreads();
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void rp_pack_kernel(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 nfields,
+                                                       u32 tiles, const u64* __restrict__ tile_off, u64* __restrict__ out) {
+    __shared__ u32 sm[5];
+    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const u64 j0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
+        RpField f[SWT_PER_THREAD];
+        u32 sum = 0;
+#pragma unroll
+        for (int k = 0; k < SWT_PER_THREAD; ++k) {
+            const u64 j = j0 + k;
+            f[k] = RpField{0, 0};
+            if (j < nfields) {
+                if (j) f[k] = rp_field(rules, R, start, j);
+                sum += j == 0 ? rp_count_bits<KIND>(R) : rp_field_bits<KIND>(f[k]);
+            }
+        }
+        u32 total;
+        const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
+        BitSink sink;
+        sink.out = out;
+        sink.pos = tile_off[tile] + excl;
+        sink.acc = 0;
+        sink.cnt = 0;
+#pragma unroll
+        for (int k = 0; k < SWT_PER_THREAD; ++k) {
+            const u64 j = j0 + k;
+            if (j >= nfields) continue;
+            if (j == 0) {                                                                  // :212 the number of rules under len_r
+                if (KIND == ENC_TAB) sink.append(R, 32);
+                else if (KIND == ENC_ASCII) append_ascii_int(sink, R);
+                else append_uni<KIND>(sink, R);
+                continue;
+            }
+            const u32 x = f[k].x;
+            if (KIND == ENC_TAB) {
+                if (x < 256u) sink.append(x, 9);                                           // :216-218 the flag 0 and the byte
+                else { sink.append(1, 1); sink.append(x - 256u, uni_bits_for(f[k].hi)); }  // :219-222
+            } else if (KIND == ENC_ASCII) {
+                if (x < 256u) { sink.append('0', 8); sink.append(x, 8); }
+                else { sink.append('1', 8); append_ascii_int(sink, x - 256u); }
+            } else {
+                if (x < 256u) { sink.append(0, 1); append_uni<KIND>(sink, x); }
+                else { sink.append(1, 1); append_uni<KIND>(sink, x - 256u); }
+            }
+        }
+        sink.flush();
+    }
+}
+
+// every rule replaces at least one pair and a replaced pair leaves one symbol, so R rules leave at most n - R start
+// symbols: 1 + 2R + (n - R) <= 2n + 1 fields for n >= 1 (R < n).  The costliest field: bit 1 + 31 (a rule index) against 9; ascii '1',
+// ten digits and ':' = 96; gamma 1 + 63; delta 1 + 11 + 31.  + 16: the count (at most 96 bits) and the terminator.
+size_t repair_bound(size_t n, int kind) {
+    if (kind < 0 || kind > 3 || n > REPAIR_MAX_N) return 0;
+    const u64 per = kind == 0 ? 32 : kind == 1 ? 96 : kind == 2 ? 64 : 43;
+    return (size_t)(((2 * (u64)n + 1) * per + 7) / 8 + 16);
+}
+
+size_t repair_encode(Ctx& c, const u64* d_rules, size_t R, const u32* d_start, size_t m, int kind, u8* d_out, size_t out_cap) {
+    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "repair: no such coder", (int)__LINE__};
+    hipStream_t s = c.stream;
+    const size_t mark = c.arena.mark();
+    const u64 nfields = 1 + 2 * (u64)R + m;
+    const size_t tiles = (size_t)((nfields + SWT_TILE - 1) / SWT_TILE);
+    const unsigned grid = dec_grid(tiles * 256);
+    u64* tile_bits = c.arena.get<u64>(tiles + 1);
+    switch (kind) {
+        case 0:  rp_tile_bits_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
+        case 1:  rp_tile_bits_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
+        case 2:  rp_tile_bits_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
+        default: rp_tile_bits_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
+    }
+    LAUNCH_CHECK();
+    exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
+    const u64 total_bits = c.read(tile_bits + tiles);
+    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
+    const size_t padded = align_up(out_len + 8, 8);
+    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "repair: output buffer too small", (int)__LINE__};
+    HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
+    switch (kind) {
+        case 0:  rp_pack_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
+        case 1:  rp_pack_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
+        case 2:  rp_pack_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
+        default: rp_pack_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
+    }
+    LAUNCH_CHECK();
     bit_stream_terminator(c, d_out, total_bits);
     HIP_TRY(hipStreamSynchronize(s));
     c.arena.release(mark);

@@ -283,6 +283,21 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
 // the host loop behind tdc_lzss_sw_decode (lzss_sw_host.cpp): a status of tdc_gpu.h, the text
 int lzss_sw_decode_host(const u8* in, size_t len, int coder, u32 window, std::vector<u8>& text);
 
+// ---- repair (compressors/RePairCompressor.hpp; repair.hip, repair_host.cpp) ------------------------------------------
+constexpr size_t REPAIR_MAX_N = (size_t)1 << 30;
+// ms_first / ms_last / ms_tie: the first round, the last one and the sum over the tie rounds, on the host clock from one round's read-back
+// to the next one's
+struct RepairStats { u64 rules = 0, replaced = 0; u32 tie_rounds = 0, rebuilds = 0, rounds = 0; size_t nstart = 0; float ms_first = 0, ms_last = 0, ms_tie = 0; };
+// :96-178 on the device: the rules (l << 32 | r, rule k stands for symbol 256 + k) and the start sequence, taken from the arena and valid
+// until the caller releases its mark.  max_rules 0: unlimited.  n <= REPAIR_MAX_N.  What the arena has to hold: repair_arena(n, max_rules,
+// table_bits) -- checked by the caller before anything is written.
+void repair_grammar(Ctx& c, const u8* d_text, size_t n, u64 max_rules, u64** d_rules, u32** d_start, RepairStats* st);
+size_t repair_arena(const Ctx& c, size_t n, u64 max_rules);
+// :208-263 -- the grammar through one coder (encode.hip): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
+// Writes the stream, terminator included, to d_out and returns its length.  bound: repair_bound (0: this kind is not taken).
+size_t repair_encode(Ctx& c, const u64* d_rules, size_t nrules, const u32* d_start, size_t nstart, int kind, u8* d_out, size_t out_cap);
+size_t repair_bound(size_t n, int kind);
+
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform
 // goes afterwards.  True: it is on its way there already, chunk by chunk on the copy stream behind the gather (page-locked memory, texts

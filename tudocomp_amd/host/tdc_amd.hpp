@@ -581,6 +581,49 @@ public:
     }
 };
 
+// tdc::RePairCompressor<BitCoder | ASCIICoder | EliasGammaCoder | EliasDeltaCoder>  (compressors/RePairCompressor.hpp:14-337), the
+// algorithm `repair`: no input restrictions.  coder defaults to bit (:89), max_rules to 0 = unlimited (:90).  The grammar is built on the
+// device; coder=huff needs the literal order of :36-84, which is not built.
+class RePairCompressor : public Compressor {
+    AlgorithmValue m_opts;
+    std::shared_ptr<GpuContext> m_ctx;
+    int m_device = 0;
+    int m_coder = TDC_GPU_CODER_BIT;
+    long m_max_rules = 0;
+public:
+    tdc_gpu_stats last_stats{};
+    void set_device(int d) { m_device = d; }
+    RePairCompressor(AlgorithmValue opts, std::shared_ptr<GpuContext> ctx) : m_opts(std::move(opts)), m_ctx(std::move(ctx)) {
+        const std::string coder = m_opts.get("coder", "bit");
+        if (coder == "bit") m_coder = TDC_GPU_CODER_BIT;
+        else if (coder == "ascii") m_coder = TDC_GPU_CODER_ASCII;
+        else if (coder == "gamma") m_coder = TDC_GPU_CODER_GAMMA;
+        else if (coder == "delta") m_coder = TDC_GPU_CODER_DELTA;
+        else throw std::runtime_error("No implementation found for compressor repair(coder=" + coder + ")");   // Registry.hpp:214
+        m_max_rules = m_opts.get_int("max_rules", 0);
+        if (m_max_rules < 0) throw std::runtime_error("repair: max_rules must not be negative");
+    }
+    void compress(Input& input, Output& output) override {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const bytes& in = input.raw();
+        uint8_t* out = nullptr; size_t out_len = 0;
+        const int rc = tdc_gpu_repair_compress(m_ctx->h, in.data(), in.size(), (uint64_t)m_max_rules, m_coder, &out, &out_len, &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        output.write(out, out_len);
+        tdc_gpu_free(out);
+    }
+    // :287-336 on the host (tdc_repair_decode: the rules expanded with an explicit stack; there is no device decoder yet)
+    void decompress(Input& input, Output& output) override {
+        const bytes& in = input.raw();
+        size_t n = 0;
+        int rc = tdc_repair_decode(in.data(), in.size(), m_coder, nullptr, 0, &n);
+        bytes text(n ? n : 1);
+        if (!rc) rc = tdc_repair_decode(in.data(), in.size(), m_coder, text.data(), n, &n);
+        if (rc) throw std::runtime_error(std::string("repair: corrupt stream (") + tdc_gpu_strerror(rc) + ")");
+        output.write(text.data(), n);
+    }
+};
+
 // tdc::BWTCompressor (compressors/BWTCompressor.hpp:14-67, ds/bwt.hpp): the Burrows-Wheeler transform of the escaped, 0-terminated view;
 // n bytes out, no header.
 class BWTCompressor : public Compressor {
@@ -771,6 +814,7 @@ inline std::vector<std::string> registered_algorithms() {
              "lzw(coder=gamma, dec=gpu)                                                   [decompression parsed and expanded on the MI355X]",
              "lzss(coder=bit | ascii | gamma | delta, window=16, threshold=3)             [sliding-window LZ77 factorized on the MI355X, window 1 .. 4096; host decoder]",
              "lzss(coder=bit | gamma | delta, dec=gpu)                                    [decompression parsed and resolved on the MI355X for streams of 1 MiB and more; ascii: host loop]",
+             "repair(coder=bit | ascii | gamma | delta, max_rules=0)                      [Re-Pair grammar built on the MI355X: digram table, one rule per round; host decoder]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
              "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
              "rle                                                                         [MI355X; host decoder]",
@@ -810,6 +854,12 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
     }
     if (av.name == "lzss") {
         auto z = std::make_unique<LZSSSlidingWindowCompressor>(parse_algorithm_id(id, {"coder", "window", "threshold", "dec"}), std::move(ctx));
+        z->set_device(device);
+        s.compressor = std::move(z);
+        return s;
+    }
+    if (av.name == "repair") {
+        auto z = std::make_unique<RePairCompressor>(parse_algorithm_id(id, {"coder", "max_rules"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;

@@ -695,4 +695,63 @@ template <typename sink_t> inline void lzw_decode(const uint8_t* in, size_t n, b
     }
 }
 
+// ---- RePairCompressor::decompress (compressors/RePairCompressor.hpp:287-336) --------------------------------------------------------------
+// The stream: the number of rules under len_r; both sides of rule i, each a flag and the byte under literal_r or x - 256 under Range(i);
+// then the start sequence under Range(rules) until the stream ends.  Symbols 0 .. 255 are bytes, 256 + k is rule k; a rule is l << 32 | r.
+// Refused (std::runtime_error): a side of rule i that names a rule >= i (the reference would recurse for ever: Range(i) holds i itself
+// under BitCoder when i is a power of two), a start symbol that names a rule >= rules, a field cut off by the end of the stream (the
+// reference reads zeros there), more rules than the stream has room for (a rule takes at least four bits), and what the field readers
+// refuse.
+struct RepairGrammar { std::vector<uint64_t> rules; std::vector<uint32_t> start; };
+template <typename decoder_t> inline void repair_parse(const uint8_t* in, size_t n, RepairGrammar& g) {
+    auto bits = std::make_shared<BitIStream>(in, n);
+    decoder_t decoder(bits);
+    auto decode_sym = [&](size_t hi, uint64_t limit) -> uint32_t {      // :292-301
+        if (decoder.template decode<bool>(bit_r)) {
+            const uint64_t v = decoder.template decode<uint64_t>(Range(hi));
+            if (bits->overrun()) throw std::runtime_error("corrupt stream: cut-off field");
+            if (v >= limit) throw std::runtime_error("corrupt stream: rule index out of range");
+            return (uint32_t)(256 + v);
+        }
+        const uliteral_t c = decoder.template decode<uliteral_t>(literal_r);
+        if (bits->overrun()) throw std::runtime_error("corrupt stream: cut-off field");
+        return c;
+    };
+    const uint64_t num_rules = decoder.template decode<uint64_t>(len_r);
+    if (bits->overrun()) throw std::runtime_error("corrupt stream: cut-off field");
+    if (num_rules > 2 * (uint64_t)n) throw std::runtime_error("corrupt stream: more rules than the stream can hold");
+    g.rules.reserve((size_t)num_rules);
+    for (uint64_t i = 0; i < num_rules; ++i) {
+        const uint32_t l = decode_sym((size_t)i, i);
+        const uint32_t r = decode_sym((size_t)i, i);
+        g.rules.push_back((uint64_t)l << 32 | r);
+    }
+    while (!decoder.eof()) g.start.push_back(decode_sym((size_t)num_rules, num_rules));
+}
+// the length of the text a grammar stands for, summed in 64 bits with saturation (A_i = A_{i-1} A_{i-1} doubles per rule) -- known
+// before any text is allocated
+inline uint64_t repair_text_length(const RepairGrammar& g) {
+    auto sat_add = [](uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; };
+    std::vector<uint64_t> len(g.rules.size());
+    auto of = [&](uint32_t x) -> uint64_t { return x < 256 ? 1 : len[x - 256]; };
+    for (size_t i = 0; i < g.rules.size(); ++i) len[i] = sat_add(of((uint32_t)(g.rules[i] >> 32)), of((uint32_t)g.rules[i]));
+    uint64_t total = 0;
+    for (uint32_t x : g.start) total = sat_add(total, of(x));
+    return total;
+}
+// :274-284 with an explicit stack instead of the recursion (a rule chain may be as deep as there are rules)
+template <typename sink_t> inline void repair_expand(const RepairGrammar& g, sink_t& os) {
+    std::vector<uint32_t> stack;
+    for (uint32_t x : g.start) {
+        stack.push_back(x);
+        while (!stack.empty()) {
+            const uint32_t y = stack.back(); stack.pop_back();
+            if (y < 256) { os.put((uint8_t)y); continue; }
+            const uint64_t di = g.rules[y - 256];
+            stack.push_back((uint32_t)di);
+            stack.push_back((uint32_t)(di >> 32));
+        }
+    }
+}
+
 }  // namespace tdc_amd
