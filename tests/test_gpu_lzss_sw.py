@@ -1,4 +1,4 @@
-"""GPU tests of lzss (tdc_gpu_lzss_sw_factorize, tdc_gpu_lzss_sw_compress{,_into}; lzss_sw.hip and the token coder of encode.hip): the
+"""GPU tests of lzss (tdc_gpu_lzss_sw_factorize, tdc_gpu_lzss_sw_compress{,_into}; lzss_sw.hip and the shared field coder, field_coder.hpp): the
 device factors against the host parse tdc_lzss_sw_factors (which tests/test_lzss_sw_cli.py holds against the model), the device streams
 byte for byte against the model's coders (tests/models/lzss_sw.py), every stream back through tdc_lzss_sw_decode, the refusals, and the
 `tdc` round trip."""
@@ -159,6 +159,16 @@ def test_threshold_above_every_match(dev):
     assert check_factors(dev, data, 16, 30)[0] == (2, 0, 30)    # (the look-ahead at p = 2 is 2w - 2)
     check_stream(dev, data, 16, 33, "gamma")
     assert check_factors(dev, data, 16, 0) == host(data, 16, 1)
+    # every position a literal: as many tokens as bytes.  Token counts on both sides of the coder's tile border (2048 tokens, 8 per
+    # thread), and 13 and 14 tokens: under bit their streams end with 5 and with 6 bits in the last byte, the two sides of the
+    # terminator rule (9 bits per literal)
+    for n in (13, 14, 2047, 2048, 2049, 4096, 4097):
+        text = two_letters(n, n)
+        assert host(text, 16, 33) == []
+        for coder in M.CODERS:
+            got, _ = check_stream(dev, text, 16, 33, coder, [])
+            if coder == "bit":
+                assert len(got) == (9 * n) // 8 + (1 if (9 * n) % 8 <= 5 else 2)
 
 
 def test_of_equal_matches_the_farther_one(dev):

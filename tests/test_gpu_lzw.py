@@ -12,6 +12,7 @@ import pytest
 
 import tudocomp_amd as T
 from tests import corpus
+from tests.coder_borders import LZW_COUNTS, phrase_prefixes, two_letters_64k
 from tests.lzw_damage import base_stream, damaged_streams
 from tests.models import lzw as M
 
@@ -106,6 +107,14 @@ def test_exact_code_counts(dev, coder):
     for z in (767, 768, 769, 2049, 65281):                              # and through the packer: a text of z distinct-pair-free phrases
         codes = [int(c) for c in rng.integers(0, 256, z)]
         assert dev.lzw_compress(bytes(codes), CID[coder])[0] == M.compress(bytes(codes), coder)
+    # Code counts on both sides of the gamma coder's tile border (2048 items, 8 per thread) and streams on both sides of the terminator
+    # rule, for both coders: tests/coder_borders.py, held against the model in tests/test_lzw_model.py
+    text = two_letters_64k()
+    for k, prefix in phrase_prefixes(text, M.phrase_lengths(np.asarray(M.parse(text)))[0], LZW_COUNTS):
+        got, st = dev.lzw_compress(prefix, CID[coder])
+        assert st["factors"] == k == len(M.parse(prefix))
+        assert got == M.compress(prefix, coder), k
+        assert dev.lzw_decompress(got, CID[coder])[0] == prefix
 
 
 def test_gamma_many_segments():

@@ -6,6 +6,8 @@ import pytest
 import tudocomp_amd as T
 from oracle import oracle as O
 from tests import corpus
+from tests.coder_borders import LZ78_COUNTS, phrase_prefixes, two_letters_64k
+from tests.models import lz78_decode as lz78_model
 from tests.util import load_json, sha256, factors_struct
 
 pytestmark = pytest.mark.gpu
@@ -209,6 +211,14 @@ def test_lz78_gamma_bitexact(gpu_ctx):
         assert st["factors"] == len(ids)
     big = T.gen_dna(1 << 22, 7).tobytes()
     assert gpu_ctx.lz78_compress(big)[0] == O.lz78_gamma_compress(big)
+    # Pair counts on both sides of the coder's tile border (2048 items, 8 per thread): tests/coder_borders.py, held against the oracle
+    # in tests/test_lz78_decode_model.py
+    text = two_letters_64k()
+    lengths = lz78_model.phrase_lengths(O.lz78_factors(text)[0].astype(np.int64))[0]
+    for k, prefix in phrase_prefixes(text, lengths, LZ78_COUNTS):
+        got, st = gpu_ctx.lz78_compress(prefix)
+        assert st["factors"] == k == len(O.lz78_factors(prefix)[0])
+        assert got == O.lz78_gamma_compress(prefix), k
     with pytest.raises(RuntimeError, match="No implementation found"):
         T.LZ78Compressor(gpu_ctx, coder="bit")
 

@@ -1,4 +1,4 @@
-"""GPU tests of repair (tdc_gpu_repair_grammar, tdc_gpu_repair_compress{,_into}; repair.hip and the grammar coder of encode.hip): the
+"""GPU tests of repair (tdc_gpu_repair_grammar, tdc_gpu_repair_compress{,_into}; repair.hip and the shared field coder, field_coder.hpp): the
 device grammar -- rules and start sequence, exactly -- against the host loop tdc_repair_grammar (which tests/test_repair_cli.py holds
 against the model), the device streams byte for byte against the model's coders (tests/models/repair.py), every stream back through
 tdc_repair_decode.  Every case runs twice: with the digram table kept up to date by the rounds' deltas, and with option
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import tudocomp_amd as T
+from tests.coder_borders import repair_borders
 from tests.models import repair as M
 from tests.util import load_json
 
@@ -147,7 +148,9 @@ def test_small_table_is_rebuilt():
 
 @pytest.mark.parametrize("coder", M.CODERS)
 def test_compress(dev, coder):
-    for data, mr in ((english(64 << 10), 0), (english(64 << 10), 100), (binary16k(), 0), (b"a" * 1000, 0), (tie_text(), 0)):
+    cases = ((english(64 << 10), 0), (english(64 << 10), 100), (binary16k(), 0), (b"a" * 1000, 0), (tie_text(), 0))
+    # and field counts on the tile borders of the coder (tests/coder_borders.py; the counts are asserted in tests/test_repair_model.py)
+    for data, mr in cases + tuple((t, mr) for t, mr, _ in repair_borders()):
         want = M.encode(*as_model(*host(data, mr)), coder)
         got, st = dev.repair_compress(data, mr, CID[coder])
         assert got == want, (len(data), mr, coder)

@@ -8,6 +8,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import corpus
+from tests.coder_borders import LZ78_COUNTS, phrase_prefixes, residue, two_letters_64k
 from tests.models import lz78_decode as M
 
 
@@ -134,3 +135,15 @@ def test_model_oversized_claim_is_found_before_the_text():
     assert int(lengths.sum()) > M.MAX_TEXT and rounds <= 18
     with pytest.raises(M.TooLarge):
         M.factor_list(ids, lengths)
+
+
+def test_coder_border_inputs():
+    """what tests/test_gpu_parity.py relies on: a prefix that ends where phrase k ends parses into k pairs.  A pair is two gamma codes of
+    odd length, so no stream ends with 5 bits in its last byte; the far side of the terminator rule, 6, is among the prefixes."""
+    text = two_letters_64k()
+    lengths = M.phrase_lengths(O.lz78_factors(text)[0].astype(np.int64))[0]
+    residues = set()
+    for k, prefix in phrase_prefixes(text, lengths, LZ78_COUNTS):
+        assert len(O.lz78_factors(prefix)[0]) == k
+        residues.add(residue(O.lz78_gamma_compress(prefix)))
+    assert 6 in residues and all(r % 2 == 0 for r in residues)

@@ -7,6 +7,7 @@ import pytest
 
 import tudocomp_amd as T
 from tests import corpus
+from tests.coder_borders import LZW_COUNTS, phrase_prefixes, residue, two_letters_64k
 from tests.models import lzw as M
 from tests.util import load_json
 
@@ -153,3 +154,15 @@ def test_differential_seed_shows_something(coder):
         except T.TdcGpuError:
             got = None
         assert got == want
+
+
+def test_coder_border_inputs():
+    """what tests/test_gpu_lzw.py relies on: a prefix that ends where phrase k ends parses into k codes, and the prefixes of
+    tests/coder_borders.py end on both sides of the terminator rule under either coder"""
+    text = two_letters_64k()
+    residues = {"bit": set(), "gamma": set()}
+    for k, prefix in phrase_prefixes(text, M.phrase_lengths(np.asarray(M.parse(text)))[0], LZW_COUNTS):
+        assert len(M.parse(prefix)) == k
+        for coder in residues:
+            residues[coder].add(residue(M.compress(prefix, coder)))
+    assert {5, 6} <= residues["bit"] and {5, 6} <= residues["gamma"]

@@ -5,6 +5,7 @@ import itertools
 import numpy as np
 import pytest
 
+from tests.coder_borders import repair_borders, residue
 from tests.models import repair as M
 from tests.models.lzss_coders import terminate
 from tests.util import load_json
@@ -156,3 +157,17 @@ def test_decode_refusals():
     assert M.expansion_lengths(many)[-1] == (1 << 64) - 1         # saturates
     with pytest.raises(M.TooLarge):
         M.sequential_decode(enc(many, [256 + 69] * 3), "bit")
+
+
+def test_coder_border_inputs():
+    """what tests/test_gpu_repair.py relies on: the field counts 1 + 2 rules + start symbols of tests/coder_borders.py, a grammar whose
+    rule sides reach across the first tile border of the coder, and streams on both sides of the terminator rule"""
+    residues = set()
+    for data, mr, fields in repair_borders():
+        rules, start = M.grammar(data, mr)
+        if fields is None:
+            assert len(rules) == mr == 1100 and 1 + 2 * len(rules) > 2048          # field 2048 is a rule side
+        else:
+            assert len(rules) == 0 and 1 + len(start) == fields
+        residues |= {residue(M.encode(rules, start, coder)) for coder in M.CODERS}
+    assert {5, 6} <= residues

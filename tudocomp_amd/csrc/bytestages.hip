@@ -9,6 +9,7 @@
 //   huff: histogram -> host table (huffman_host.cpp: the tie order of libstdc++ is the format) -> bits per tile -> scan -> pack.
 #include "bytestages.hpp"
 #include "stages.hpp"
+#include "bitsink.hpp"
 #include "prim.hpp"
 #include "huffman_host.hpp"
 
@@ -291,19 +292,6 @@ __global__ void __launch_bounds__(256) huff_tile_bits_kernel(const u8* __restric
     if (threadIdx.x == 0) tile_bits[blockIdx.x] = total;
 }
 
-// MSB-first stream = big-endian 64-bit words; threads own disjoint bit ranges of a zeroed buffer, so OR is order-independent
-__device__ __forceinline__ void or_bits(u64* __restrict__ out, u64 bitpos, u64 val, u32 nbits) {       // 1 <= nbits <= 64
-    const u64 w = bitpos >> 6;
-    const u32 off = (u32)(bitpos & 63), avail = 64 - off;
-    if (nbits <= avail) {
-        atomicOr((unsigned long long*)&out[w], (unsigned long long)__builtin_bswap64(nbits == 64 ? val : (val << (avail - nbits))));
-    } else {
-        const u32 rem = nbits - avail;
-        atomicOr((unsigned long long*)&out[w], (unsigned long long)__builtin_bswap64(val >> rem));
-        atomicOr((unsigned long long*)&out[w + 1], (unsigned long long)__builtin_bswap64(val << (64 - rem)));
-    }
-}
-
 __global__ void __launch_bounds__(256) huff_pack_kernel(const u8* __restrict__ in, size_t n, const HuffDev* __restrict__ T, const u64* __restrict__ tile_off,
                                                         u64 base_bits, u64* __restrict__ out) {
     __shared__ u64 code[256];
@@ -324,26 +312,17 @@ __global__ void __launch_bounds__(256) huff_pack_kernel(const u8* __restrict__ i
     u32 total;
     const u32 pre = block_exclusive_sum<u32, 4>(bits, sm, total);
     if (base >= n) return;
-    u64 pos = base_bits + tile_off[blockIdx.x] + pre;
-    u64 acc = 0;
-    u32 cnt = 0;                                                  // pending bits, right-aligned in acc
+    BitSink sink;
+    sink.out = out;
+    sink.pos = base_bits + tile_off[blockIdx.x] + pre;
+    sink.acc = 0;
+    sink.cnt = 0;
 #pragma unroll
     for (u32 b = 0; b < 16; ++b) {
         const u32 ch = (x[b >> 2] >> (8 * (b & 3))) & 255u;
-        const u32 l = base + b < n ? len[ch] : 0u;                // (nothing behind the input)
-        if (cnt + l > 64) { or_bits(out, pos, acc, cnt); pos += cnt; cnt = 0; acc = 0; }
-        if (l) acc = l == 64 ? code[ch] : ((acc << l) | code[ch]);
-        cnt += l;
+        if (base + b < n) sink.append(code[ch], len[ch]);           // (nothing behind the input)
     }
-    if (cnt) or_bits(out, pos, acc, cnt);
-}
-
-// io/BitOStream.hpp:53-64: u = bits used in the last byte; u <= 5: OR u into that byte, else one more byte that holds u
-__global__ void huff_terminator_kernel(u8* out, u64 total_bits) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const u32 u = (u32)(total_bits & 7);
-    if (u <= 5) out[total_bits >> 3] |= (u8)u;
-    else out[(total_bits >> 3) + 1] = (u8)u;
+    sink.flush();
 }
 
 }  // namespace
@@ -442,9 +421,9 @@ StageOut huff_literals_device(Ctx& c, const u8* d_in, size_t n) {
         exclusive_sum_u64(c, tile_bits, tile_bits, ntiles, tile_bits + ntiles);
         total_bits += c.read(tile_bits + ntiles);
     }
-    r.len = (total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
+    r.len = bit_stream_len(total_bits);
     if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
-    const size_t padded = align_up(r.len + 8, 8);
+    const size_t padded = bit_stream_padded(r.len);
     r.d = c.arena.get<u8>(padded + 64);
     HIP_TRY(hipMemsetAsync(r.d, 0, padded, s));
     HIP_TRY(hipMemcpyAsync(r.d, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, s));
@@ -452,8 +431,7 @@ StageOut huff_literals_device(Ctx& c, const u8* d_in, size_t n) {
         huff_pack_kernel<<<ntiles, 256, 0, s>>>(d_in, n, d_tab, tile_bits, hw.nbits, (u64*)r.d);
         LAUNCH_CHECK();
     }
-    huff_terminator_kernel<<<1, 64, 0, s>>>(r.d, total_bits);
-    LAUNCH_CHECK();
+    bit_stream_terminator(c, r.d, total_bits);
     HIP_TRY(hipStreamSynchronize(s));                            // (the header and the table live on this frame)
     return r;
 }

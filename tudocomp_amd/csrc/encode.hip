@@ -18,11 +18,10 @@
 // (2) recompute the costs, scan inside the workgroup, OR the bits into the zeroed output (big-endian 64-bit words).
 //
 // At the end of the file: encode(sle) = LiteralEncoder<SLECoder> as a byte stage (sle_literals_device, declared in bytestages.hpp),
-// the owner-less use of the SLE machinery below, and the token coder of lzss (lzss_sw_encode_tokens, DESIGN.md
-// section 5.7) and the grammar coder of repair (repair_encode, section 5.8): the same sink and field writers over a token or symbol list
-// instead of position space.
+// the owner-less use of the SLE machinery below.  The sink and the field writers: bitsink.hpp.
 #include "stages.hpp"
 #include "bytestages.hpp"
+#include "bitsink.hpp"
 #include "prim.hpp"
 #include "huffman_host.hpp"
 #include "arith.hpp"
@@ -45,26 +44,6 @@ struct EncParams {
     u32 ascii;            // ASCIICoder (coders/ASCIICoder.hpp:29-50): decimal integers + ':', '0'/'1', raw literals, no "- min"
     u32 uni;              // 0, ENC_GAMMA or ENC_DELTA: every integer and every literal as a self-delimiting code, no "- min"
 };
-// what the kernels are instantiated for: a code table or raw literals with fixed-width fields (HuffmanCoder, ArithmeticCoder, BitCoder),
-// ASCIICoder, EliasGammaCoder (coders/EliasGammaCoder.hpp:26-29), EliasDeltaCoder (coders/EliasDeltaCoder.hpp:26-29)
-constexpr int ENC_TAB = 0, ENC_ASCII = 1, ENC_GAMMA = 2, ENC_DELTA = 3;
-
-// io/BitOStream.hpp:105-135 -- gamma(v): bits_for(v) zeros, a one, v in bits_for(v) bits; delta(v): gamma(bits_for(v)), then v in
-// bits_for(v) bits.  bits_for(0) = 1.  v < 2^31: gamma takes at most 63 bits, delta 11 + 31
-__device__ __forceinline__ u32 uni_bits_for(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 1u; }
-template <int KIND> __device__ __forceinline__ u32 uni_cost(u32 v) {
-    const u32 b = uni_bits_for(v);
-    return KIND == ENC_GAMMA ? 2u * b + 1u : 2u * uni_bits_for(b) + 1u + b;
-}
-
-// number of characters ASCIICoder writes for an integer: its decimal digits and the ':'
-__device__ __forceinline__ u32 ascii_int_chars(u32 v) {
-    u32 d = 1;
-    if (v >= 1000000000u) d = 10; else if (v >= 100000000u) d = 9; else if (v >= 10000000u) d = 8; else if (v >= 1000000u) d = 7;
-    else if (v >= 100000u) d = 6; else if (v >= 10000u) d = 5; else if (v >= 1000u) d = 4; else if (v >= 100u) d = 3; else if (v >= 10u) d = 2;
-    return d + 1;
-}
-
 struct EncScalars { u32 flen_min, flen_max, fdist_max, pad; };
 
 // literal coder = ArithmeticCoder: what a literal contributes is looked up per literal ordinal (arith.hip)
@@ -275,57 +254,6 @@ __global__ __launch_bounds__(256) void tile_bits_cls_kernel(const u8* __restrict
     }
 }
 
-// Append `nbits` (1..64) bits of `val` at absolute bit position `bitpos`; the stream is MSB-first, so the output is
-// treated as big-endian 64-bit words.  Different threads own disjoint bit ranges: OR is order-independent.
-__device__ __forceinline__ void put_bits(u64* __restrict__ out, u64 bitpos, u64 val, u32 nbits) {
-    const u64 w = bitpos >> 6;
-    const u32 off = (u32)(bitpos & 63);
-    const u32 avail = 64 - off;
-    if (nbits <= avail) {
-        const u64 x = (nbits == 64) ? val : (val << (avail - nbits));
-        atomicOr((unsigned long long*)&out[w], (unsigned long long)__builtin_bswap64(x));
-    } else {
-        const u32 rem = nbits - avail;
-        atomicOr((unsigned long long*)&out[w], (unsigned long long)__builtin_bswap64(val >> rem));
-        atomicOr((unsigned long long*)&out[w + 1], (unsigned long long)__builtin_bswap64(val << (64 - rem)));
-    }
-}
-
-struct BitSink {
-    u64* out;
-    u64 pos;     // bit position of the first pending bit
-    u64 acc;     // pending bits, right-aligned
-    u32 cnt;
-    __device__ __forceinline__ void flush() {
-        if (cnt) { put_bits(out, pos, acc, cnt); pos += cnt; cnt = 0; acc = 0; }
-    }
-    __device__ __forceinline__ void append(u64 v, u32 nb) {     // v < 2^nb, 0 <= nb <= 64
-        if (nb == 0) return;
-        if (cnt + nb > 64) flush();
-        acc = (nb == 64) ? v : ((acc << nb) | v);
-        cnt += nb;
-    }
-};
-
-// ASCIICoder::Encoder::encode(v, Range) (ASCIICoder.hpp:33-39): decimal digits, most significant first, then ':'
-__device__ __forceinline__ void append_ascii_int(BitSink& sink, u32 v) {
-    u32 pw = 1000000000u;
-    bool started = false;
-    for (int i = 0; i < 10; ++i) {
-        const u32 d = v / pw;
-        if (d || started || pw == 1u) { sink.append('0' + d, 8); started = true; }
-        v -= d * pw;
-        pw /= 10u;
-    }
-    sink.append(':', 8);
-}
-
-template <int KIND> __device__ __forceinline__ void append_uni(BitSink& sink, u32 v) {
-    const u32 b = uni_bits_for(v);
-    if (KIND == ENC_GAMMA) sink.append((1ull << b) | v, 2u * b + 1u);                 // b zeros, the one, v: one field of at most 63 bits
-    else { const u32 bb = uni_bits_for(b); sink.append((1ull << bb) | b, 2u * bb + 1u); sink.append(v, b); }
-}
-
 template <int KIND>
 __global__ __launch_bounds__(256) void pack_kernel(const u8* __restrict__ text, const u32* __restrict__ owner,
                                                     const u32* __restrict__ flen, const u32* __restrict__ fsrc, size_t n,
@@ -502,15 +430,6 @@ __global__ void range_tiles_kernel(const u32* __restrict__ fpos, u32 z, u32 K, u
     if (k + 1 < K) out[k] = fpos[(u32)((u64)z * (k + 1) / K)] / (u32)ENC_TILE;
 }
 
-// io/BitOStream.hpp:53-64 : u = bits used in the last byte; u <= 5: OR u into that byte, else append a byte holding u.
-__global__ void terminator_kernel(u8* out, u64 total_bits) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const u64 byte = total_bits >> 3;
-    const u32 u = (u32)(total_bits & 7);
-    if (u <= 5) out[byte] |= (u8)u;
-    else out[byte + 1] = (u8)u;
-}
-
 // worst case per position: 1 + 32 bits of run header + 64 (+128 once) of arithmetic words; ASCIICoder (coder 2): a one-byte
 // factor costs '0' + two integers of up to 10 digits and ':' each; SLECoder (coder 3): at most 13 bits per literal, 67 per factor,
 // and a ranking header of at most 1024 symbols of 10 bytes
@@ -527,30 +446,6 @@ size_t encode_bound_coder(size_t n, int coder) { return ((coder & 0xFF) == 2 ? 2
 // positions).  + 64: the header -- n and three fields, at most 63 + 3 * 65 bits (gamma: the zero-factor stream writes 2^32 - 1 in 65
 // bits) = 33 bytes -- and the terminator byte.
 size_t encode_bound_uni(size_t n, int coder) { return (coder == 4 ? 8 : coder == 5 ? 9 : 6) * n + 64; }
-
-// lzss (LZSSSlidingWindowCompressor.hpp:85-95; kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder): no header, and
-// every token covers at least one text byte, so the worst case is n times the costliest token.  A literal is the flag and the byte: 1 + 8
-// bits, '0' and the byte = 16, 1 + gamma(255) = 1 + 17, 1 + delta(255) = 1 + 17.  A factor is the flag, a distance <= w and a length
-// <= 2w - 1 (both coders' costs grow with the value):
-//   bit    1 + bits_for(p) + bits_for(w) <= 1 + bits_for(n) + bits_for(w)
-//   ascii  8 * (1 + digits(w) + 1 + digits(2w - 1) + 1)
-//   gamma  1 + (2 bits_for(w) + 1) + (2 bits_for(2w - 1) + 1)
-//   delta  1 + delta_bits(w) + delta_bits(2w - 1),  delta_bits(v) = 2 bits_for(bits_for(v)) + 1 + bits_for(v)
-// + 2: the terminator (the count of the last byte's bits, in that byte or in one of its own).
-size_t lzss_sw_bound(size_t n, u32 window, int kind) {
-    if (kind < 0 || kind > 3 || window == 0 || window > LZSS_SW_MAX_WINDOW || n > 0xFFFFFFFEull) return 0;
-    const u64 w = window, l = 2 * w - 1;
-    auto digits = [](u64 v) { u64 d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
-    auto delta_bits = [](u64 v) { return 2 * (u64)bits_for(bits_for(v)) + 1 + bits_for(v); };
-    u64 lit, fac;
-    switch (kind) {
-        case 0:  lit = 9;  fac = 1 + (u64)bits_for(n) + bits_for(w); break;
-        case 1:  lit = 16; fac = 8 * (1 + digits(w) + 1 + digits(l) + 1); break;
-        case 2:  lit = 18; fac = 1 + (2 * (u64)bits_for(w) + 1) + (2 * (u64)bits_for(l) + 1); break;
-        default: lit = 18; fac = 1 + delta_bits(w) + delta_bits(l); break;
-    }
-    return (size_t)(((u64)n * std::max(lit, fac) + 7) / 8 + 2);
-}
 
 size_t encode_huff(Ctx& c, const u8* text, size_t n, FactorSpace fs, u8* d_out, size_t out_cap, EncodeStats* st) {
     return encode_stream(c, text, n, fs, 0, d_out, out_cap, st, nullptr);
@@ -767,7 +662,7 @@ static void encode_step_c(Ctx& c, EncodeEarly& E) {
     if (E.seq_b) c.publish_wait(E.seq_b, h_tp, sizeof(h_tp), 2); else c.read_n(E.d_tp, h_tp, 1 + PACK_CH);
     const bool may_overlap = E.may_overlap;
     E.total_bits = E.base_bits + h_tp[0];
-    E.out_len = (size_t)(E.total_bits >> 3) + ((E.total_bits & 7) <= 5 ? 1 : 2);
+    E.out_len = bit_stream_len(E.total_bits);
     E.overlap = may_overlap && E.out_len <= c.d2h_cap;
     for (u32 q = 0; q < PACK_CH; ++q) E.h_end[q] = h_tp[1 + q];
     E.step = 3;
@@ -796,7 +691,7 @@ void encode_early_free(EncodeEarly* E) { delete E; }
 static void pack_begin(Ctx& c, hipStream_t ps, EncodeEarly& E, u8* d_out) {
     if (E.begun) return;
     const HostBitWriter& hw = E.hw;
-    HIP_TRY(hipMemsetAsync(d_out, 0, align_up(E.out_len + 8, 8), ps));
+    HIP_TRY(hipMemsetAsync(d_out, 0, bit_stream_padded(E.out_len), ps));
     if (c.pinned_hdr && hw.bytes.size() <= Ctx::PINNED_HDR) {        // (through the context's page-locked block: a copy from pageable memory drains the stream)
         memcpy(c.pinned_hdr, hw.bytes.data(), hw.bytes.size());
         HIP_TRY(hipMemcpyAsync(d_out, c.pinned_hdr, hw.bytes.size(), hipMemcpyHostToDevice, ps));
@@ -872,7 +767,7 @@ void encode_early_chunk_done(Ctx& c, const u8* text, size_t n, const FactorSpace
     // The host does not wait here: if the bit offsets of step B have not arrived, this range's tiles are issued with the next one's (and
     // whatever is left when the ranges are over with encode_stream, behind the first half's last step).
     if (E.step == 2 && E.seq_b && c.publish_test(E.seq_b, 2)) encode_step_c(c, E);
-    if (!E.done || align_up(E.out_len + 8, 8) > E.out_cap) return;
+    if (!E.done || bit_stream_padded(E.out_len) > E.out_cap) return;
     if (E.q_ready == E.nb) return;                     // (the last range: encode_stream is about to pack it, with the terminator behind)
     const hipStream_t ps = c.copy_stream, cs = c.aux_stream;
     pack_begin(c, ps, E, E.d_out);
@@ -904,7 +799,7 @@ size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder
     const EncScalars h_sc = E.sc;
     const u64 total_bits = E.total_bits;
     const size_t out_len = E.out_len;
-    const size_t padded = align_up(out_len + 8, 8);
+    const size_t padded = bit_stream_padded(out_len);
     if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "encode: output buffer too small", (int)__LINE__};
 
     // ---- pass 2: pack ----------------------------------------------------------------------------------------
@@ -924,8 +819,7 @@ size_t encode_stream(Ctx& c, const u8* text, size_t n, FactorSpace fs, int coder
         for (u32 q = E.overlap ? E.q_done + 1 : E.nb; q <= E.nb; ++q) pack_upto(c, ps, cs, text, n, fs, E, d_out, q);
         c.d2h_done = E.copied;
     }
-    terminator_kernel<<<1, 64, 0, ps>>>(d_out, total_bits);
-    LAUNCH_CHECK();
+    { StreamSwap on_ps(c, ps); bit_stream_terminator(c, d_out, total_bits); }
     if (ps != s) c.wait_for(s, ps);
     HIP_TRY(hipStreamSynchronize(s));      // hw.bytes must outlive the async copy
 
@@ -1467,15 +1361,14 @@ static size_t encode_sle(Ctx& c, const u8* text, size_t n, FactorSpace fs, u32 k
     LAUNCH_CHECK();
     exclusive_sum_u64(c, tile_bits, tile_bits, tiles, d_total);
     const u64 total_bits = base_bits + c.read(d_total);
-    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
-    const size_t padded = align_up(out_len + 8, 8);
+    const size_t out_len = bit_stream_len(total_bits);
+    const size_t padded = bit_stream_padded(out_len);
     if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "encode: output buffer too small", (int)__LINE__};
     HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
     HIP_TRY(hipMemcpyAsync(d_out, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, s));
     sle_stream_kernel<true><<<tiles, 256, 0, s>>>(text, plain_owner(fs), fs.flen, fs.fsrc, minfo, n, D, P, tile_bits, base_bits, (u64*)d_out);
     LAUNCH_CHECK();
-    terminator_kernel<<<1, 64, 0, s>>>(d_out, total_bits);
-    LAUNCH_CHECK();
+    bit_stream_terminator(c, d_out, total_bits);
     HIP_TRY(hipStreamSynchronize(s));      // hw.bytes and the host tables must outlive the async copies
 
     st->factors = z;
@@ -1536,9 +1429,9 @@ StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 k) {
         exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
         total_bits += c.read(tile_bits + tiles);
     }
-    r.len = (total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
+    r.len = bit_stream_len(total_bits);
     if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
-    const size_t padded = align_up(r.len + 8, 8);
+    const size_t padded = bit_stream_padded(r.len);
     r.d = c.arena.get<u8>(padded + 64);
     HIP_TRY(hipMemsetAsync(r.d, 0, padded, s));
     HIP_TRY(hipMemcpyAsync(r.d, hw.bytes.data(), hw.bytes.size(), hipMemcpyHostToDevice, s));
@@ -1546,291 +1439,9 @@ StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 k) {
         sle_lit_stream_kernel<true><<<tiles, 256, 0, s>>>(d_in, minfo, n, D, tile_bits, base_bits, (u64*)r.d);
         LAUNCH_CHECK();
     }
-    terminator_kernel<<<1, 64, 0, s>>>(r.d, total_bits);
-    LAUNCH_CHECK();
+    bit_stream_terminator(c, r.d, total_bits);
     HIP_TRY(hipStreamSynchronize(s));                            // (the header lives on this frame)
     return r;
-}
-
-
-// ---- lzss: the tokens of the sliding-window parse through one coder (LZSSSlidingWindowCompressor.hpp:85-95) -------
-// Token i starts at text position tokpos[i]; fac[p] = distance << 16 | length, 0 for a literal.  A literal is the flag 0 and the byte
-// under literal_r; a factor the flag 1, the distance under Range(0, p) and the length under Range(0, window).  BitCoder: bits_for(p) and
-// wbits = bits_for(window) bits (the one field whose width depends on where the token stands: hence a cost pass over the tokens instead of
-// closed-form offsets); gamma / delta ignore the ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.
-// Tiles of 2048 tokens: bits per tile, their scan, then the pack recomputes the costs and ORs the fields into the zeroed output.
-constexpr int SWT_PER_THREAD = 8, SWT_TILE = 256 * SWT_PER_THREAD;
-struct SwScalars { unsigned long long factors; u32 flen_max, trunc; };
-
-template <int KIND> __device__ __forceinline__ u32 sw_token_bits(u32 pos, u32 f, u32 ch, u32 wbits) {
-    if (KIND == ENC_TAB) return f ? 1u + uni_bits_for(pos) + wbits : 9u;
-    if (KIND == ENC_ASCII) return f ? 8u * (1u + ascii_int_chars(f >> 16) + ascii_int_chars(f & 0xFFFFu)) : 16u;
-    return f ? 1u + uni_cost<KIND>(f >> 16) + uni_cost<KIND>(f & 0xFFFFu) : 1u + uni_cost<KIND>(ch);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void sw_tile_bits_kernel(const u8* __restrict__ text, const u32* __restrict__ tokpos, const u32* __restrict__ fac,
-                                                            u64 ntok, u32 wbits, u32 tiles, u64* __restrict__ tile_bits, SwScalars* __restrict__ sc) {
-    __shared__ u32 sm[4];
-    u32 nfac = 0, lmax = 0;
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u64 i0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
-        u32 sum = 0;
-#pragma unroll
-        for (int j = 0; j < SWT_PER_THREAD; ++j) {
-            if (i0 + j < ntok) {
-                const u32 pos = tokpos[i0 + j], f = fac[pos];
-                const u32 ch = (KIND == ENC_GAMMA || KIND == ENC_DELTA) && !f ? text[pos] : 0u;
-                sum += sw_token_bits<KIND>(pos, f, ch, wbits);
-                nfac += f ? 1u : 0u;
-                lmax = max(lmax, f & 0xFFFFu);
-            }
-        }
-        sum = wave_reduce_sum(sum);
-        if (lane_id() == 0) sm[wave_id()] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_bits[tile] = (u64)sm[0] + sm[1] + sm[2] + sm[3];
-        __syncthreads();
-    }
-    nfac = wave_reduce_sum(nfac);
-    lmax = wave_reduce_max(lmax);
-    if (lane_id() == 0) {
-        if (nfac) atomicAdd(&sc->factors, (unsigned long long)nfac);
-        if (lmax) atomicMax(&sc->flen_max, lmax);
-        if (KIND == ENC_TAB && (lmax >> wbits)) atomicOr(&sc->trunc, 1u);      // write_int would drop the length's top bits
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void sw_pack_kernel(const u8* __restrict__ text, const u32* __restrict__ tokpos, const u32* __restrict__ fac,
-                                                       u64 ntok, u32 wbits, u32 tiles, const u64* __restrict__ tile_off, u64* __restrict__ out) {
-    __shared__ u32 sm[5];
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u64 i0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
-        u32 pos[SWT_PER_THREAD], f[SWT_PER_THREAD], ch[SWT_PER_THREAD];
-        u32 sum = 0;
-#pragma unroll
-        for (int j = 0; j < SWT_PER_THREAD; ++j) {
-            pos[j] = 0; f[j] = 0; ch[j] = 0;
-            if (i0 + j < ntok) {
-                pos[j] = tokpos[i0 + j]; f[j] = fac[pos[j]];
-                if (!f[j]) ch[j] = text[pos[j]];
-                sum += sw_token_bits<KIND>(pos[j], f[j], ch[j], wbits);
-            }
-        }
-        u32 total;
-        const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
-        BitSink sink;
-        sink.out = out;
-        sink.pos = tile_off[tile] + excl;
-        sink.acc = 0;
-        sink.cnt = 0;
-#pragma unroll
-        for (int j = 0; j < SWT_PER_THREAD; ++j) {
-            if (i0 + j < ntok) {
-                const u32 dist = f[j] >> 16, len = f[j] & 0xFFFFu;
-                if (KIND == ENC_TAB) {
-                    if (!f[j]) sink.append(ch[j], 9);                                  // :94-95 the flag 0 and the byte
-                    else { sink.append(1, 1); sink.append(dist, uni_bits_for(pos[j])); sink.append(len, wbits); }     // :87-89
-                } else if (KIND == ENC_ASCII) {
-                    if (!f[j]) { sink.append('0', 8); sink.append(ch[j], 8); }
-                    else { sink.append('1', 8); append_ascii_int(sink, dist); append_ascii_int(sink, len); }
-                } else {
-                    if (!f[j]) { sink.append(0, 1); append_uni<KIND>(sink, ch[j]); }
-                    else { sink.append(1, 1); append_uni<KIND>(sink, dist); append_uni<KIND>(sink, len); }
-                }
-            }
-        }
-        sink.flush();
-    }
-}
-
-size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const u32* fac, size_t ntok, u32 window, int kind,
-                             u8* d_out, size_t out_cap, LzssSwStats* st) {
-    LzssSwStats local;
-    if (!st) st = &local;
-    *st = LzssSwStats();
-    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "lzss: no such coder", (int)__LINE__};
-    hipStream_t s = c.stream;
-    const size_t mark = c.arena.mark();
-    const u32 wbits = bits_for(window);
-    const size_t tiles = (ntok + SWT_TILE - 1) / SWT_TILE;                      // < 2^21
-    const unsigned grid = dec_grid(tiles * 256);
-    u64 total_bits = 0;
-    u64* tile_bits = nullptr;
-    if (ntok) {
-        tile_bits = c.arena.get<u64>(tiles + 1);
-        SwScalars* d_sc = (SwScalars*)c.arena.alloc(sizeof(SwScalars));
-        HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(SwScalars), s));
-        switch (kind) {
-            case 0:  sw_tile_bits_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
-            case 1:  sw_tile_bits_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
-            case 2:  sw_tile_bits_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
-            default: sw_tile_bits_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, d_sc); break;
-        }
-        LAUNCH_CHECK();
-        exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
-        total_bits = c.read(tile_bits + tiles);
-        const SwScalars h = c.read(d_sc);
-        st->factors = h.factors; st->flen_max = h.flen_max; st->truncates = h.trunc != 0;
-        if (st->truncates) { c.arena.release(mark); return 0; }
-    }
-    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
-    const size_t padded = align_up(out_len + 8, 8);
-    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "lzss: output buffer too small", (int)__LINE__};
-    HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
-    if (ntok) {
-        switch (kind) {
-            case 0:  sw_pack_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
-            case 1:  sw_pack_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
-            case 2:  sw_pack_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
-            default: sw_pack_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_text, tokpos, fac, (u64)ntok, wbits, (u32)tiles, tile_bits, (u64*)d_out); break;
-        }
-        LAUNCH_CHECK();
-    }
-    bit_stream_terminator(c, d_out, total_bits);
-    HIP_TRY(hipStreamSynchronize(s));
-    c.arena.release(mark);
-    return out_len;
-}
-
-// ---- repair: a grammar through one coder (RePairCompressor.hpp:208-263) -------------------------------------------
-// Field 0 is the number of rules under len_r; fields 1 .. 2R are the sides of the rules -- rule i's under Range(i) --, the rest the start
-// sequence under Range(R).  A symbol is the flag 0 and the byte under literal_r, or the flag 1 and x - 256 under its range.  BitCoder: 32
-// bits for the count, bits_for(i) or bits_for(R) for a rule index -- a function of the field's index alone; gamma / delta ignore the
-// ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.  Same shape as the lzss token coder: bits per tile of 2048
-// fields, their scan, then the pack recomputes the costs and ORs the fields into the zeroed output.
-struct RpField { u32 x, hi; };     // hi: the top of the range
-__device__ __forceinline__ RpField rp_field(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 j) {
-    if (j <= 2ull * R) {
-        const u32 i = (u32)((j - 1) >> 1);
-        const u64 di = rules[i];
-        return RpField{ ((j - 1) & 1) ? (u32)di : (u32)(di >> 32), i };
-    }
-    return RpField{ start[j - 1 - 2ull * R], R };
-}
-template <int KIND> __device__ __forceinline__ u32 rp_count_bits(u32 R) {
-    if (KIND == ENC_TAB) return 32u;
-    if (KIND == ENC_ASCII) return 8u * ascii_int_chars(R);
-    return uni_cost<KIND>(R);
-}
-template <int KIND> __device__ __forceinline__ u32 rp_field_bits(RpField f) {
-    if (KIND == ENC_TAB) return f.x < 256u ? 9u : 1u + uni_bits_for(f.hi);
-    if (KIND == ENC_ASCII) return f.x < 256u ? 16u : 8u * (1u + ascii_int_chars(f.x - 256u));
-    return 1u + uni_cost<KIND>(f.x < 256u ? f.x : f.x - 256u);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void rp_tile_bits_kernel(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 nfields,
-                                                            u32 tiles, u64* __restrict__ tile_bits) {
-    __shared__ u32 sm[4];
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u64 j0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
-        u32 sum = 0;
-#pragma unroll
-        for (int k = 0; k < SWT_PER_THREAD; ++k) {
-            const u64 j = j0 + k;
-            if (j < nfields) sum += j == 0 ? rp_count_bits<KIND>(R) : rp_field_bits<KIND>(rp_field(rules, R, start, j));
-        }
-        sum = wave_reduce_sum(sum);
-        if (lane_id() == 0) sm[wave_id()] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_bits[tile] = (u64)sm[0] + sm[1] + sm[2] + sm[3];
-        __syncthreads();
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void rp_pack_kernel(const u64* __restrict__ rules, u32 R, const u32* __restrict__ start, u64 nfields,
-                                                       u32 tiles, const u64* __restrict__ tile_off, u64* __restrict__ out) {
-    __shared__ u32 sm[5];
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u64 j0 = (u64)tile * SWT_TILE + (u64)threadIdx.x * SWT_PER_THREAD;
-        RpField f[SWT_PER_THREAD];
-        u32 sum = 0;
-#pragma unroll
-        for (int k = 0; k < SWT_PER_THREAD; ++k) {
-            const u64 j = j0 + k;
-            f[k] = RpField{0, 0};
-            if (j < nfields) {
-                if (j) f[k] = rp_field(rules, R, start, j);
-                sum += j == 0 ? rp_count_bits<KIND>(R) : rp_field_bits<KIND>(f[k]);
-            }
-        }
-        u32 total;
-        const u32 excl = block_exclusive_sum<u32, 4>(sum, sm, total);
-        BitSink sink;
-        sink.out = out;
-        sink.pos = tile_off[tile] + excl;
-        sink.acc = 0;
-        sink.cnt = 0;
-#pragma unroll
-        for (int k = 0; k < SWT_PER_THREAD; ++k) {
-            const u64 j = j0 + k;
-            if (j >= nfields) continue;
-            if (j == 0) {                                                                  // :212 the number of rules under len_r
-                if (KIND == ENC_TAB) sink.append(R, 32);
-                else if (KIND == ENC_ASCII) append_ascii_int(sink, R);
-                else append_uni<KIND>(sink, R);
-                continue;
-            }
-            const u32 x = f[k].x;
-            if (KIND == ENC_TAB) {
-                if (x < 256u) sink.append(x, 9);                                           // :216-218 the flag 0 and the byte
-                else { sink.append(1, 1); sink.append(x - 256u, uni_bits_for(f[k].hi)); }  // :219-222
-            } else if (KIND == ENC_ASCII) {
-                if (x < 256u) { sink.append('0', 8); sink.append(x, 8); }
-                else { sink.append('1', 8); append_ascii_int(sink, x - 256u); }
-            } else {
-                if (x < 256u) { sink.append(0, 1); append_uni<KIND>(sink, x); }
-                else { sink.append(1, 1); append_uni<KIND>(sink, x - 256u); }
-            }
-        }
-        sink.flush();
-    }
-}
-
-// every rule replaces at least one pair and a replaced pair leaves one symbol, so R rules leave at most n - R start
-// symbols: 1 + 2R + (n - R) <= 2n + 1 fields for n >= 1 (R < n).  The costliest field: bit 1 + 31 (a rule index) against 9; ascii '1',
-// ten digits and ':' = 96; gamma 1 + 63; delta 1 + 11 + 31.  + 16: the count (at most 96 bits) and the terminator.
-size_t repair_bound(size_t n, int kind) {
-    if (kind < 0 || kind > 3 || n > REPAIR_MAX_N) return 0;
-    const u64 per = kind == 0 ? 32 : kind == 1 ? 96 : kind == 2 ? 64 : 43;
-    return (size_t)(((2 * (u64)n + 1) * per + 7) / 8 + 16);
-}
-
-size_t repair_encode(Ctx& c, const u64* d_rules, size_t R, const u32* d_start, size_t m, int kind, u8* d_out, size_t out_cap) {
-    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "repair: no such coder", (int)__LINE__};
-    hipStream_t s = c.stream;
-    const size_t mark = c.arena.mark();
-    const u64 nfields = 1 + 2 * (u64)R + m;
-    const size_t tiles = (size_t)((nfields + SWT_TILE - 1) / SWT_TILE);
-    const unsigned grid = dec_grid(tiles * 256);
-    u64* tile_bits = c.arena.get<u64>(tiles + 1);
-    switch (kind) {
-        case 0:  rp_tile_bits_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
-        case 1:  rp_tile_bits_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
-        case 2:  rp_tile_bits_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
-        default: rp_tile_bits_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits); break;
-    }
-    LAUNCH_CHECK();
-    exclusive_sum_u64(c, tile_bits, tile_bits, tiles, tile_bits + tiles);
-    const u64 total_bits = c.read(tile_bits + tiles);
-    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
-    const size_t padded = align_up(out_len + 8, 8);
-    if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "repair: output buffer too small", (int)__LINE__};
-    HIP_TRY(hipMemsetAsync(d_out, 0, padded, s));
-    switch (kind) {
-        case 0:  rp_pack_kernel<ENC_TAB><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
-        case 1:  rp_pack_kernel<ENC_ASCII><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
-        case 2:  rp_pack_kernel<ENC_GAMMA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
-        default: rp_pack_kernel<ENC_DELTA><<<grid, 256, 0, s>>>(d_rules, (u32)R, d_start, nfields, (u32)tiles, tile_bits, (u64*)d_out); break;
-    }
-    LAUNCH_CHECK();
-    bit_stream_terminator(c, d_out, total_bits);
-    HIP_TRY(hipStreamSynchronize(s));
-    c.arena.release(mark);
-    return out_len;
 }
 
 }  // namespace tdc

@@ -11,12 +11,14 @@
 //                  matches.  A lane stops as soon as best == L(p): nothing can beat it, and runs or periodic texts, whose first
 //                  candidate already reaches L, cost one candidate per position instead of w.
 //   the parse      next(p) = p + max(1, len(p)); the tokens are the orbit of position 0 (mark_orbit_u32), listed by select_by_class.
-// The tokens then go through lzss_sw_encode_tokens (encode.hip): cost pass, scan, pack, terminator.
+// The tokens then go through lzss_sw_encode_tokens: the cost pass, scan, pack and terminator of field_coder.hpp over SwTokens below.
 //
 // Worst case of the match kernel: n * w * L / 8 word compares, on texts built so that many candidates match almost to L.
 #include "stages.hpp"
-#include "prim.hpp"
+#include "field_coder.hpp"
 #include "decode.hpp"
+
+#include <algorithm>
 
 namespace tdc {
 
@@ -103,7 +105,95 @@ __global__ __launch_bounds__(256) void lzss_sw_factor_emit_kernel(const u32* __r
     }
 }
 
+// ---- the tokens through one coder (LZSSSlidingWindowCompressor.hpp:85-95): the source of field_coder.hpp ------------------------------
+// Token i starts at text position tokpos[i]; fac[p] = distance << 16 | length, 0 for a literal.  A literal is the flag 0 and the byte
+// under literal_r; a factor the flag 1, the distance under Range(0, p) and the length under Range(0, window).  BitCoder: bits_for(p) and
+// wbits = bits_for(window) bits (the one field whose width depends on where the token stands: hence a cost pass over the tokens instead of
+// closed-form offsets); gamma / delta ignore the ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.
+// The cost pass also counts the factors and finds the longest one, and whether BitCoder would drop bits of a length.
+struct SwScalars { unsigned long long factors; u32 flen_max, trunc; };
+
+struct SwTokens {
+    const u8* __restrict__ text;
+    const u32* __restrict__ tokpos;
+    const u32* __restrict__ fac;
+    u32 wbits;
+    SwScalars* sc;
+    struct Item { u32 pos = 0, f = 0, ch = 0; };     // ch: the byte at pos (read for a factor too: no branch on f between the loads)
+    template <int KIND, bool COST_ONLY> __device__ __forceinline__ void load(u64 i, Item& it) const {
+        it.pos = tokpos[i]; it.f = fac[it.pos];
+        if (!COST_ONLY || KIND == ENC_GAMMA || KIND == ENC_DELTA) it.ch = text[it.pos];       // (bit and ascii: every byte costs 8 bits)
+    }
+    template <int KIND> __device__ __forceinline__ u32 bits(const Item& it) const {
+        return flag_cost<KIND>() + (it.f ? int_cost<KIND>(it.f >> 16, uni_bits_for(it.pos)) + int_cost<KIND>(it.f & 0xFFFFu, wbits) : byte_cost<KIND>(it.ch));
+    }
+    template <int KIND> __device__ __forceinline__ void put(BitSink& sink, const Item& it) const {
+        append_flag<KIND>(sink, it.f ? 1u : 0u);
+        if (!it.f) append_byte<KIND>(sink, it.ch);                                                  // :94-95
+        else { append_int<KIND>(sink, it.f >> 16, uni_bits_for(it.pos)); append_int<KIND>(sink, it.f & 0xFFFFu, wbits); }     // :87-89
+    }
+    struct Tally {
+        u32 nfac = 0, lmax = 0;
+        __device__ __forceinline__ void note(const SwTokens&, const Item& it) { nfac += it.f ? 1u : 0u; lmax = max(lmax, it.f & 0xFFFFu); }
+        template <int KIND> __device__ __forceinline__ void commit(const SwTokens& src) {
+            nfac = wave_reduce_sum(nfac);
+            lmax = wave_reduce_max(lmax);
+            if (lane_id() == 0) {
+                if (nfac) atomicAdd(&src.sc->factors, (unsigned long long)nfac);
+                if (lmax) atomicMax(&src.sc->flen_max, lmax);
+                if (KIND == ENC_TAB && (lmax >> src.wbits)) atomicOr(&src.sc->trunc, 1u);      // write_int would drop the length's top bits
+            }
+        }
+    };
+};
+
 }  // namespace
+
+// lzss (LZSSSlidingWindowCompressor.hpp:85-95; kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder): no header, and
+// every token covers at least one text byte, so the worst case is n times the costliest token.  A literal is the flag and the byte: 1 + 8
+// bits, '0' and the byte = 16, 1 + gamma(255) = 1 + 17, 1 + delta(255) = 1 + 17.  A factor is the flag, a distance <= w and a length
+// <= 2w - 1 (both coders' costs grow with the value):
+//   bit    1 + bits_for(p) + bits_for(w) <= 1 + bits_for(n) + bits_for(w)
+//   ascii  8 * (1 + digits(w) + 1 + digits(2w - 1) + 1)
+//   gamma  1 + (2 bits_for(w) + 1) + (2 bits_for(2w - 1) + 1)
+//   delta  1 + delta_bits(w) + delta_bits(2w - 1),  delta_bits(v) = 2 bits_for(bits_for(v)) + 1 + bits_for(v)
+// + 2: the terminator (the count of the last byte's bits, in that byte or in one of its own).
+size_t lzss_sw_bound(size_t n, u32 window, int kind) {
+    if (kind < 0 || kind > 3 || window == 0 || window > LZSS_SW_MAX_WINDOW || n > 0xFFFFFFFEull) return 0;
+    const u64 w = window, l = 2 * w - 1;
+    auto digits = [](u64 v) { u64 d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
+    auto delta_bits = [](u64 v) { return 2 * (u64)bits_for(bits_for(v)) + 1 + bits_for(v); };
+    u64 lit, fac;
+    switch (kind) {
+        case 0:  lit = 9;  fac = 1 + (u64)bits_for(n) + bits_for(w); break;
+        case 1:  lit = 16; fac = 8 * (1 + digits(w) + 1 + digits(l) + 1); break;
+        case 2:  lit = 18; fac = 1 + (2 * (u64)bits_for(w) + 1) + (2 * (u64)bits_for(l) + 1); break;
+        default: lit = 18; fac = 1 + delta_bits(w) + delta_bits(l); break;
+    }
+    return (size_t)(((u64)n * std::max(lit, fac) + 7) / 8 + 2);
+}
+
+size_t lzss_sw_encode_tokens(Ctx& c, const u8* d_text, const u32* tokpos, const u32* fac, size_t ntok, u32 window, int kind,
+                             u8* d_out, size_t out_cap, LzssSwStats* st) {
+    LzssSwStats local;
+    if (!st) st = &local;
+    *st = LzssSwStats();
+    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "lzss: no such coder", (int)__LINE__};
+    const size_t mark = c.arena.mark();
+    SwScalars* d_sc = nullptr;                                                                      // (an empty list: no cost pass, no tally)
+    if (ntok) {
+        d_sc = (SwScalars*)c.arena.alloc(sizeof(SwScalars));
+        HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(SwScalars), c.stream));
+    }
+    const size_t len = encode_fields(c, SwTokens{ d_text, tokpos, fac, bits_for(window), d_sc }, (u64)ntok, kind, d_out, out_cap,
+                                     "lzss: output buffer too small", [&] {
+        const SwScalars h = c.read(d_sc);
+        st->factors = h.factors; st->flen_max = h.flen_max; st->truncates = h.trunc != 0;
+        return !st->truncates;                                                                      // BitCoder would truncate: nothing is packed
+    });
+    c.arena.release(mark);
+    return len;
+}
 
 size_t lzss_sw_tokens(Ctx& c, const u8* d_text, size_t n, u32 window, u32 threshold, u32** tokpos, u32** fac_out) {
     *tokpos = nullptr; *fac_out = nullptr;

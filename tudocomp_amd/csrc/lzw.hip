@@ -5,10 +5,10 @@
 // coder=bit: code k is written with bits_for(k + 256) bits (Coder.hpp:61-63), a width that depends on k alone, so the bit offset of
 // every code is a closed form (lzw_offset) and so is its inverse (lzw_code_at): neither direction needs a cost pass, a scan or a guess.
 //   pack:  one thread per 64-bit OUTPUT word gathers the at most 8 codes that touch it -- every word is written once, whole: no zeroed
-//          buffer and no atomics (the put_bits / atomicOr scheme of lz78.hip was not built: it would add a memset of the output and
+//          buffer and no atomics (the put_bits / atomicOr scheme of field_coder.hpp was not built: it would add a memset of the output and
 //          up to two atomics per code for the same bytes).
 //   parse: the payload bit count fixes the number of codes; one thread per code reads its at most two words and validates it.
-// coder=gamma: gamma(code) per phrase -- the cost / scan / pack kernels of lz78.hip with one value per item, and on the way back the
+// coder=gamma: gamma(code) per phrase -- the gamma items of lz78.hip with one value per item, and on the way back the
 // next() / orbit parse of lz78_decode.hip with one code per item.
 //
 // Decoding: dictionary entry 256 + j is phrase j plus the first byte of phrase j + 1, and those bytes are adjacent in the text.  A code
@@ -16,6 +16,7 @@
 // same copy overlapping its own first byte.  Lengths by pointer jumping over k -> c_k - 256, starts by one scan, the text by the shared
 // reference resolver: expand_phrases() of lz78_decode.hip.  Code k must be <= 255 + k ("invalid compressed code" otherwise, :72-76).
 #include "stages.hpp"
+#include "bitsink.hpp"
 #include "prim.hpp"
 #include "decode.hpp"
 #include "../host/tdc_coders.hpp"
@@ -99,8 +100,8 @@ size_t lzw_decode_host(const u8* stream, size_t len, bool bit, Sink& out, size_t
 
 size_t lzw_bit_encode(Ctx& c, const u32* d_codes, size_t z, u8* d_out, size_t out_cap) {
     const u64 total_bits = lzw_offset(z);
-    const size_t out_len = (size_t)(total_bits >> 3) + ((total_bits & 7) <= 5 ? 1 : 2);
-    const size_t padded = align_up(out_len + 8, 8);
+    const size_t out_len = bit_stream_len(total_bits);
+    const size_t padded = bit_stream_padded(out_len);
     if (padded > out_cap) throw HipError{hipErrorOutOfMemory, "lzw: output buffer too small", (int)__LINE__};
     const u64 words = padded / 8;
     lzw_bit_pack_kernel<<<dec_grid(words), 256, 0, c.stream>>>(d_codes, (u64)z, (u64*)d_out, words);

@@ -23,8 +23,10 @@
 // The table is rebuilt by a recount of S, at twice the size, when a round could fill it beyond half; the recount drops the slots whose
 // count had fallen to 0, and a table the live pairs would fill to less than an eighth is made to fit them.  Option repair_recount = 1
 // rebuilds it in every round instead of applying the deltas.
+//
+// The grammar then goes through repair_encode: the cost pass, scan, pack and terminator of field_coder.hpp over RpFields below.
 #include "stages.hpp"
-#include "prim.hpp"
+#include "field_coder.hpp"
 #include "decode.hpp"
 
 #include <chrono>
@@ -302,7 +304,52 @@ struct Builder {
     }
 };
 
+// ---- a grammar through one coder (RePairCompressor.hpp:208-263): the source of field_coder.hpp -------------------------------------------
+// Field 0 is the number of rules under len_r; fields 1 .. 2R are the sides of the rules -- rule i's under Range(i) --, the rest the start
+// sequence under Range(R).  A symbol is the flag 0 and the byte under literal_r, or the flag 1 and x - 256 under its range.  BitCoder: 32
+// bits for the count, bits_for(i) or bits_for(R) for a rule index -- a function of the field's index alone; gamma / delta ignore the
+// ranges; ASCIICoder writes '0' / '1', decimal digits with ':' and the byte.
+struct RpFields {
+    const u64* __restrict__ rules;
+    u32 R;
+    const u32* __restrict__ start;
+    struct Item { u32 x = 0, hi = 0; };     // hi: the top of the range; RP_NONE: the count
+    template <int, bool> __device__ __forceinline__ void load(u64 j, Item& f) const {
+        if (j == 0) { f.x = R; f.hi = RP_NONE; }
+        else if (j <= 2ull * R) {
+            const u32 i = (u32)((j - 1) >> 1);
+            const u64 di = rules[i];
+            f.x = ((j - 1) & 1) ? (u32)di : (u32)(di >> 32); f.hi = i;
+        } else { f.x = start[j - 1 - 2ull * R]; f.hi = R; }
+    }
+    using Tally = NoTally;
+    template <int KIND> __device__ __forceinline__ u32 bits(const Item& f) const {
+        if (f.hi == RP_NONE) return int_cost<KIND>(f.x, 32u);
+        return flag_cost<KIND>() + (f.x < 256u ? byte_cost<KIND>(f.x) : int_cost<KIND>(f.x - 256u, uni_bits_for(f.hi)));
+    }
+    template <int KIND> __device__ __forceinline__ void put(BitSink& sink, const Item& f) const {
+        if (f.hi == RP_NONE) { append_int<KIND>(sink, f.x, 32u); return; }                   // :212 the number of rules under len_r
+        append_flag<KIND>(sink, f.x < 256u ? 0u : 1u);
+        if (f.x < 256u) append_byte<KIND>(sink, f.x);                                         // :216-218
+        else append_int<KIND>(sink, f.x - 256u, uni_bits_for(f.hi));                          // :219-222
+    }
+};
+
 }  // namespace
+
+// every rule replaces at least one pair and a replaced pair leaves one symbol, so R rules leave at most n - R start
+// symbols: 1 + 2R + (n - R) <= 2n + 1 fields for n >= 1 (R < n).  The costliest field: bit 1 + 31 (a rule index) against 9; ascii '1',
+// ten digits and ':' = 96; gamma 1 + 63; delta 1 + 11 + 31.  + 16: the count (at most 96 bits) and the terminator.
+size_t repair_bound(size_t n, int kind) {
+    if (kind < 0 || kind > 3 || n > REPAIR_MAX_N) return 0;
+    const u64 per = kind == 0 ? 32 : kind == 1 ? 96 : kind == 2 ? 64 : 43;
+    return (size_t)(((2 * (u64)n + 1) * per + 7) / 8 + 16);
+}
+
+size_t repair_encode(Ctx& c, const u64* d_rules, size_t R, const u32* d_start, size_t m, int kind, u8* d_out, size_t out_cap) {
+    if (kind < 0 || kind > 3) throw HipError{hipErrorInvalidValue, "repair: no such coder", (int)__LINE__};
+    return encode_fields(c, RpFields{ d_rules, (u32)R, d_start }, 1 + 2 * (u64)R + m, kind, d_out, out_cap, "repair: output buffer too small");
+}
 
 size_t repair_arena(const Ctx& c, size_t n, u64 max_rules) {
     const u64 R = std::min<u64>(max_rules ? max_rules : n, n);

@@ -245,9 +245,8 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
 size_t lz78_parse_host(const u8* in, size_t n, std::vector<u32>& ids, std::vector<u8>& chars, bool* leftover_is_high);
 // a16: coders/EliasGammaCoder.hpp:26-29 + io/BitOStream.hpp:105-129 on the device; returns the stream length
 size_t lz78_gamma_encode(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap);
-// the same kernels for items of one value (d_chars == NULL) or two; the reference's bit-stream terminator at bit total_bits of d_out
+// the same for items of one value (d_chars == NULL) or two
 size_t gamma_encode_items(Ctx& c, const u32* d_ids, const u8* d_chars, size_t z, u8* d_out, size_t out_cap);
-void bit_stream_terminator(Ctx& c, u8* d_out, u64 total_bits);
 
 // ---- lzw (compressors/LZWCompressor.hpp, lzw/LZWDecoding.hpp; lzw_host.cpp, lzw.hip) -----------------------
 // :39-108 -- the sequential parse on the host: codes[k] = id of the node phrase k ends in; returns the number of codes
@@ -268,7 +267,7 @@ constexpr u32 LZSS_SW_MAX_WINDOW = 4096;      // the match kernel holds a tile o
 size_t lzss_sw_tokens(Ctx& c, const u8* d_text, size_t n, u32 window, u32 threshold, u32** tokpos, u32** fac);
 // the factors among the tokens as a list sorted by pos (d_pos / d_src / d_len: ntok entries of capacity each); returns their number
 size_t lzss_sw_factor_list(Ctx& c, const u32* tokpos, const u32* fac, size_t ntok, u32* d_pos, u32* d_src, u32* d_len);
-// :85-95 -- the tokens through one coder (encode.hip): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
+// :85-95 -- the tokens through one coder (field_coder.hpp): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
 // Writes the stream, terminator included, to d_out and returns its length -- or 0 with st->truncates set and nothing packed: BitCoder
 // and a length that does not fit bits_for(window) bits.  bound: lzss_sw_bound (0: this kind or window is not taken).
 struct LzssSwStats { u64 factors = 0; u32 flen_max = 0; bool truncates = false; };
@@ -293,7 +292,7 @@ struct RepairStats { u64 rules = 0, replaced = 0; u32 tie_rounds = 0, rebuilds =
 // table_bits) -- checked by the caller before anything is written.
 void repair_grammar(Ctx& c, const u8* d_text, size_t n, u64 max_rules, u64** d_rules, u32** d_start, RepairStats* st);
 size_t repair_arena(const Ctx& c, size_t n, u64 max_rules);
-// :208-263 -- the grammar through one coder (encode.hip): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
+// :208-263 -- the grammar through one coder (field_coder.hpp): kind 0 = BitCoder, 1 = ASCIICoder, 2 = EliasGammaCoder, 3 = EliasDeltaCoder.
 // Writes the stream, terminator included, to d_out and returns its length.  bound: repair_bound (0: this kind is not taken).
 size_t repair_encode(Ctx& c, const u64* d_rules, size_t nrules, const u32* d_start, size_t nstart, int kind, u8* d_out, size_t out_cap);
 size_t repair_bound(size_t n, int kind);
