@@ -87,7 +87,7 @@ typedef struct {
     uint64_t pipe_len[8];       /* ... the length in bytes behind stage i, ...                                                      */
     float    pipe_ms[8];        /* ... and what stage i took (host clock around a synchronisation; only with option pipe_log)       */
     uint32_t ranges_early;      /* tdc_gpu_lcpcomp_compress_into: rank ranges of the flatten stage whose pack was enqueued before the stage returned (flatten_chunks) */
-    uint32_t reserved0;
+    uint32_t len_rounds;        /* tdc_gpu_repair_decompress_stats: rounds of the length pass over the rules                          */
     uint64_t rules;             /* tdc_gpu_repair_*: "rules" (RePairCompressor.hpp:204), ...                                          */
     uint64_t replaced;          /* ... "replaced" (:205): pairs replaced over all rounds, ...                                        */
     uint32_t tie_rounds;        /* ... rounds in which more than one pair held the largest count, ...                               */
@@ -426,11 +426,22 @@ size_t tdc_gpu_repair_bound(size_t n, int coder);
  * tdc_repair_grammar computes on the host.  stats (may be NULL): the repair fields and ms_factorize. */
 int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, uint64_t** rules, size_t* nrules,
                            uint32_t** start, size_t* nstart, tdc_gpu_stats* stats);
-/* RePairCompressor::decompress behind the signature of the other decompressing entry points: the host loop tdc_repair_decode (there is
- * no device decoder yet: DESIGN.md section 5.8 names it as the follow-up); its status codes.  *out is malloc'd (tdc_gpu_free); _into:
+/* RePairCompressor::decompress.  bit, gamma and delta streams are decoded ON THE DEVICE ("Device decoder"): the
+ * tokens are parsed side by side, the grammar becomes a factor list (lengths bottom-up, first occurrences top-down) and the reference
+ * resolver of the other decoders writes the text.  Option dec_parse picks the path: 1 (default) = streams of 1 MiB and more, 2 = every
+ * stream, 0 = the host loop tdc_repair_decode, which also keeps the ascii streams.  Option repair_dec_rounds (default 1024) bounds the
+ * rounds of the two grammar passes; a grammar that needs more (a chain of rules) is decoded by the host loop, as is a stream with a gamma /
+ * delta field wider than the device reads (an index above 32 bits, a literal above 8).  Verdict and text are tdc_repair_decode's on
+ * every stream; tdc_gpu_ctx_last_decode_on_device reports the path a successful call took.  *out is malloc'd (tdc_gpu_free); _into:
  * TDC_GPU_ERR_OOM with the required size in *out_len if out_cap is too small. */
 int tdc_gpu_repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len);
 int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len);
+/* _into with what the call did.  stats (may be NULL): n and out_len (the text), rules, factors, arena_bytes, len_rounds (rounds of the
+ * length pass), levels (rounds of the first-occurrence pass), flatten_rounds (pointer-jumping rounds of the reference resolver),
+ * small_levels (segments of the parse), ms_h2d (the upload), ms_factorize (parse and grammar passes), ms_d2h (items, resolver and
+ * download), ms_total -- host clock around synchronisations; all zero but n, out_len and ms_total where the host loop decoded. */
+int tdc_gpu_repair_decompress_stats(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len,
+                                    tdc_gpu_stats* stats);
 
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG

@@ -5,7 +5,9 @@ same text at the largest max_rules it is expected to finish within --host-second
 A round is timed on the host clock from its read-back to the next one's (no synchronisation is added for it).
 Usage: python3 tools/repair_bench.py [english|dna] [N] [--rules 256,4096,65536] [--reps R] [--host-seconds S]
        python3 tools/repair_bench.py --trace DIR      (per-kernel totals of a rocprofv3 --kernel-trace --stats run of the line above)
-(output: profiles/repair_<text>_<N>.txt by redirection)"""
+       python3 tools/repair_bench.py --decode [english|dna] [N] [--rules ...] [--dec-reps R] [--cross]
+           (the device decoder against the host loop on the streams of bit, gamma and delta; --cross: streams of 64 KiB .. 4 MiB)
+(output: profiles/repair_<text>_<N>.txt, profiles/repair_decode_<text>_<N>.txt by redirection)"""
 import argparse
 import csv
 import glob
@@ -22,6 +24,9 @@ ap.add_argument("--rules", default="256,4096,65536")
 ap.add_argument("--reps", type=int, default=1)
 ap.add_argument("--host-seconds", type=float, default=60.0)
 ap.add_argument("--trace", default=None)
+ap.add_argument("--decode", action="store_true")
+ap.add_argument("--cross", action="store_true")
+ap.add_argument("--dec-reps", type=int, default=3)
 args = ap.parse_args()
 
 if args.trace:
@@ -38,6 +43,54 @@ if args.trace:
     sys.exit(0)
 
 import tudocomp_amd as T
+
+if args.decode:
+    # Decode column: every stream the compressor makes is decoded by the device decoder (repair_decode.hip; dec_parse = 2, pinned buffers,
+    # one warm call, then --dec-reps timed ones) and, in the same run, by the host loop tdc_repair_decode on the same stream (one call that
+    # parses, sums the length and expands).  --cross: streams of about 64 KiB .. 4 MiB instead, to see where the two paths cross.
+    import ctypes
+    import numpy as np
+    L = T._native.load()
+    CODERS = (("bit", T.CODER_BIT), ("gamma", T.CODER_GAMMA), ("delta", T.CODER_DELTA))
+    N = int(float(args.n))
+    rules = [int(x) for x in args.rules.split(",")]
+    jobs = [(N, mr) for mr in rules] if not args.cross else [(n, 256) for n in (100 << 10, 400 << 10, 1600 << 10, 6400 << 10)]
+    print("repair decode, %s; device: dec_parse=2, pinned buffers, one warm call then %d timed ones (all shown, the fastest first); host: "
+          "tdc_repair_decode, one call on the same stream" % (args.gen, args.dec_reps))
+    print("text B | max_rules | coder | stream B | device ms (h2d / parse+grammar / items+resolver+d2h) | host ms | segments | length rounds | "
+          "placement rounds | factors | resolver rounds")
+    with T.Context(0, options={"dec_parse": 2}) as ctx:
+        for n_text, mr in jobs:
+            text = T.PinnedBuffer(n_text)
+            (T.gen_english if args.gen == "english" else T.gen_dna)(n_text, 42 if args.gen == "english" else 7, out=text.a)
+            want = text.a.tobytes()
+            back = T.PinnedBuffer(n_text)
+            for name, cid in CODERS:
+                out = T.PinnedBuffer(T.repair_bound(n_text, cid))
+                slen, _ = ctx.repair_compress_into(text, n_text, out, mr, cid)
+                stream = T.PinnedBuffer(slen)
+                stream.a[:] = out.a[:slen]
+                out.free()
+                runs = []
+                for _ in range(1 + args.dec_reps):
+                    back.a[:] = 0
+                    n, st = ctx.repair_decompress_stats_into(stream, back, cid)
+                    assert n == n_text and st["device_parse"] == 1 and back.a.tobytes() == want
+                    runs.append(st)
+                runs = sorted(runs[1:], key=lambda s: s["ms_total"])
+                best = runs[0]
+                hbuf, hn = np.zeros(n_text, dtype=np.uint8), ctypes.c_size_t()
+                t0 = time.perf_counter()
+                rc = L.tdc_repair_decode(stream.a.ctypes.data_as(ctypes.c_void_p), slen, cid, hbuf.ctypes.data_as(ctypes.c_void_p), n_text, ctypes.byref(hn))
+                t_host = time.perf_counter() - t0
+                assert rc == 0 and hn.value == n_text and hbuf.tobytes() == want
+                print("%d | %d | %s | %d | %s (%.2f / %.2f / %.2f) | %.2f | %d | %d | %d | %d | %d"
+                      % (n_text, mr, name, slen, " ".join("%.2f" % s["ms_total"] for s in runs), best["ms_h2d"], best["ms_factorize"], best["ms_d2h"],
+                         t_host * 1e3, best["small_levels"], best["len_rounds"], best["levels"], best["factors"], best["flatten_rounds"]), flush=True)
+                stream.free()
+            back.free()
+            text.free()
+    sys.exit(0)
 
 N = int(float(args.n))
 RULES = [int(x) for x in args.rules.split(",")]

@@ -579,8 +579,44 @@ class Context:
         return (np.frombuffer(self._take(r, nr.value * 8), dtype=np.uint64).copy(), np.frombuffer(self._take(s, ns.value * 4), dtype=np.uint32).copy(),
                 st.as_dict())
 
+    def repair_decompress_stats(self, stream, coder=CODER_BIT):
+        """RePairCompressor::decompress with what the call did: returns (text, stats).  stats: the fields of
+        tdc_gpu_repair_decompress_stats and "device_parse".  bit, gamma and delta streams of 1 MiB and more are decoded on the device
+        (option dec_parse: 2 = every stream, 0 = never); ascii streams, smaller ones and grammars deeper than option repair_dec_rounds
+        go through the host loop (repair_decode)."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        n, st = ctypes.c_size_t(), Stats()
+        probe = np.empty(1, dtype=np.uint8)      # the length first: no bytes are "too small" for every text but the empty one (the _into form decodes once)
+        rc = self._L.tdc_gpu_repair_decompress_stats(self._h, _ptr(a) if len(a) else None, len(a), int(coder), _ptr(probe), 0, ctypes.byref(n),
+                                                     ctypes.byref(st))
+        if rc == 0:
+            return b"", self._repair_dec_stats(st)
+        if rc != -5:
+            self._check(rc)
+        out = np.empty(n.value, dtype=np.uint8)
+        self._check(self._L.tdc_gpu_repair_decompress_stats(self._h, _ptr(a) if len(a) else None, len(a), int(coder), _ptr(out), out.size,
+                                                            ctypes.byref(n), ctypes.byref(st)))
+        return out[:n.value].tobytes(), self._repair_dec_stats(st)
+
+    def repair_decompress_stats_into(self, stream, out, coder=CODER_BIT):
+        """repair_decompress_stats into a caller-owned buffer (a PinnedBuffer or a writable uint8 array; `stream` may be a PinnedBuffer
+        too): returns (text length, stats).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the length."""
+        a = stream.a if isinstance(stream, PinnedBuffer) else _u8(stream)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        n, st = ctypes.c_size_t(), Stats()
+        rc = self._L.tdc_gpu_repair_decompress_stats(self._h, _ptr(a) if len(a) else None, len(a), int(coder), _ptr(oa), oa.size, ctypes.byref(n),
+                                                     ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, n.value)
+        return n.value, self._repair_dec_stats(st)
+
+    def _repair_dec_stats(self, st):
+        d = st.as_dict()
+        d["device_parse"] = int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))
+        return d
+
     def repair_decompress(self, stream, coder=CODER_BIT):
-        """tdc_gpu_repair_decompress: the host loop behind the signature of the other decompressing entry points"""
+        """tdc_gpu_repair_decompress: the text.  The path is repair_decompress_stats's."""
         a = _u8(stream)
         out, n = ctypes.c_void_p(), ctypes.c_size_t()
         self._check(self._L.tdc_gpu_repair_decompress(self._h, _ptr(a) if len(a) else None, len(a), coder, ctypes.byref(out), ctypes.byref(n)))
@@ -1158,17 +1194,20 @@ class LZSSSlidingWindowCompressor:
 
 class RePairCompressor:
     """Mirror of tdc::RePairCompressor<coder> (compressors/RePairCompressor.hpp:14-337), the algorithm `repair`; no input restrictions.
-    coder: bit (the reference's default), ascii, gamma or delta; max_rules 0 = unlimited.  The grammar is built on the device;
-    decompress() is the host loop (repair_decode) -- there is no device decoder yet."""
+    coder: bit (the reference's default), ascii, gamma or delta; max_rules 0 = unlimited.  The grammar is built on the device.
+    dec="host": decompress() is the host loop (repair_decode), which needs no context; dec="gpu" (an addition, as for lzss): the device
+    decoder (tdc_gpu_repair_decompress; coder=ascii decodes through the host loop there too).  The stream is the same either way."""
 
     _CODERS = {"bit": CODER_BIT, "ascii": CODER_ASCII, "gamma": CODER_GAMMA, "delta": CODER_DELTA}
 
-    def __init__(self, ctx, coder="bit", max_rules=0):
+    def __init__(self, ctx, coder="bit", max_rules=0, dec="host"):
         if coder not in self._CODERS:
             raise RuntimeError("No implementation found for compressor repair(coder=%s)" % coder)
         if int(max_rules) < 0:
             raise RuntimeError("repair: max_rules must not be negative")
-        self.ctx, self.coder, self.max_rules = ctx, self._CODERS[coder], int(max_rules)
+        if dec not in ("host", "gpu"):
+            raise RuntimeError("repair: dec must be host or gpu")
+        self.ctx, self.coder, self.max_rules, self.dec = ctx, self._CODERS[coder], int(max_rules), dec
         self.last_stats = None
 
     def compress(self, data):
@@ -1177,6 +1216,10 @@ class RePairCompressor:
         return out
 
     def decompress(self, stream):
+        if self.dec == "gpu":
+            if self.ctx is None:
+                raise RuntimeError("repair: dec=gpu needs a context")
+            return self.ctx.repair_decompress(stream, self.coder)
         return repair_decode(stream, self.coder)
 
 

@@ -38,7 +38,7 @@ SYMBOLS = [
     "tdc_gpu_lzss_sw_compress", "tdc_gpu_lzss_sw_compress_into", "tdc_gpu_lzss_sw_bound", "tdc_gpu_lzss_sw_factorize", "tdc_lzss_sw_factors",
     "tdc_lzss_sw_decode", "tdc_gpu_lzss_sw_decompress", "tdc_gpu_lzss_sw_decompress_into",
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
-    "tdc_gpu_repair_decompress_into", "tdc_repair_grammar", "tdc_repair_decode",
+    "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
 ]
 
 
@@ -55,7 +55,7 @@ class Stats(ctypes.Structure):
                                         "probes", "max_push_targets")] +
         [("d2h_early", ctypes.c_uint64)] +
         [("pipe_stages", ctypes.c_uint32), ("pipe_dev", ctypes.c_uint32), ("pipe_len", ctypes.c_uint64 * 8), ("pipe_ms", ctypes.c_float * 8),
-         ("ranges_early", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+         ("ranges_early", ctypes.c_uint32), ("len_rounds", ctypes.c_uint32),
          ("rules", ctypes.c_uint64), ("replaced", ctypes.c_uint64), ("tie_rounds", ctypes.c_uint32), ("rebuilds", ctypes.c_uint32),
          ("ms_round_first", ctypes.c_float), ("ms_round_last", ctypes.c_float), ("ms_round_tie", ctypes.c_float), ("reserved1", ctypes.c_float)])
 
@@ -199,7 +199,8 @@ def load():
     L.tdc_gpu_repair_grammar.argtypes = [vp, vp, sz, u64, pvp, psz, pvp, psz, ctypes.POINTER(Stats)]
     L.tdc_gpu_repair_decompress.argtypes = [vp, vp, sz, i32, pvp, psz]
     L.tdc_gpu_repair_decompress_into.argtypes = [vp, vp, sz, i32, vp, sz, psz]
-    L.tdc_repair_grammar.argtypes = [vp, sz, u64, pvp, psz, pvp, psz]
+    L.tdc_gpu_repair_decompress_stats.argtypes = [vp, vp, sz, i32, vp, sz, psz, ctypes.POINTER(Stats)]
+    L.tdc_repair_grammar.argtypes =[vp, sz, u64, pvp, psz, pvp, psz]
     L.tdc_repair_decode.argtypes = [vp, sz, i32, vp, sz, psz]
     L.tdc_gpu_lzss_sw_decompress.argtypes = [vp, vp, sz, i32, u32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lzss_sw_decompress_into.argtypes = [vp, vp, sz, i32, u32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]

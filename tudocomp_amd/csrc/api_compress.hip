@@ -742,27 +742,6 @@ void repair_compress(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max
     ev.finish();
     sink_commit(s, len);
 }
-
-// the host loop behind the signature of the other decompressing entry points
-int repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, uint8_t* into, size_t cap, size_t* out_len) {
-    if (!ctx) return TDC_GPU_ERR_ARG;
-    ctx->last_error.clear();
-    if ((!stream && len) || !out_len || (!out && !into)) { ctx->last_error = "NULL argument"; return TDC_GPU_ERR_ARG; }
-    size_t n = 0;
-    int rc = tdc_repair_decode(stream, len, coder, nullptr, 0, &n);
-    if (rc) { ctx->last_error = "repair: the stream is refused (tdc_repair_decode)"; return rc; }
-    *out_len = n;
-    if (into) {
-        if (n > cap) { ctx->last_error = "output buffer too small (*out_len holds the required size)"; return TDC_GPU_ERR_OOM; }
-        return tdc_repair_decode(stream, len, coder, into, cap, &n);
-    }
-    uint8_t* buf = (uint8_t*)malloc(n ? n : 1);
-    if (!buf) { ctx->last_error = "host allocation failed"; return TDC_GPU_ERR_OOM; }
-    rc = tdc_repair_decode(stream, len, coder, buf, n, &n);
-    if (rc) { free(buf); return rc; }
-    *out = buf;
-    return TDC_GPU_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -805,15 +784,6 @@ int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64
         ev.finish();
         *rules = hr.release<uint64_t>(); *nrules = (size_t)rs.rules; *start = hs.release<uint32_t>(); *nstart = rs.nstart;
     });
-}
-
-int tdc_gpu_repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len) {
-    return repair_decompress(ctx, stream, len, coder, out, nullptr, 0, out_len);
-}
-
-int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
-    if (!out) return TDC_GPU_ERR_ARG;
-    return repair_decompress(ctx, stream, len, coder, nullptr, out, out_cap, out_len);
 }
 
 }  // extern "C"

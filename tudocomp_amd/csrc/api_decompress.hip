@@ -1,8 +1,9 @@
-// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw and lzss decompression.
+// api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw, lzss and repair decompression.
 #include "api.hpp"
 #include "decode.hpp"
 #include "../host/tdc_coders.hpp"
 
+#include <chrono>
 #include <stdexcept>
 #include <vector>
 
@@ -115,6 +116,41 @@ void lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int
     ctx->last_decode_device = (int)ds.device_parse;
     sink_commit(s, n);
 }
+
+// RePairCompressor::decompress.  bit, gamma, delta: the device where decode_repair takes the stream, else -- and for ascii -- the host
+// loop that is its specification (tdc_repair_decode), whose status codes the call returns.
+void repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, tdc_gpu_stats* stats) {
+    ctx->last_decode_device = 0;
+    if (!stream && len) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    sink_check(s, "NULL argument");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const auto t_start = std::chrono::steady_clock::now();
+    RepairDecodeStats rs;
+    size_t n = 0, need = 0;
+    bool dev = false;
+    if (coder == TDC_GPU_CODER_BIT || coder == TDC_GPU_CODER_GAMMA || coder == TDC_GPU_CODER_DELTA) {
+        const int kind = coder == TDC_GPU_CODER_BIT ? 0 : coder == TDC_GPU_CODER_GAMMA ? 1 : 2;
+        dev = run_decoder(s, "repair: the stream decodes to more than 2^32 - 2 bytes", &need,
+                          [&] { return (size_t)decode_repair(ctx->c, stream, len, kind, s, &need, &rs, &n); }) != 0;
+    }
+    if (!dev) {
+        int rc = tdc_repair_decode(stream, len, coder, nullptr, 0, &n);          // the verdict and the length, before any text is made
+        if (rc == TDC_GPU_OK) {
+            sink_fit(s, n);
+            rc = tdc_repair_decode(stream, len, coder, decode_dest(s, n), n, &n);
+        }
+        if (rc) throw ArgError{rc, "repair: the stream is refused (tdc_repair_decode)"};
+        rs = RepairDecodeStats();
+    }
+    if (stats) {
+        stats->n = n; stats->out_len = n; stats->rules = rs.rules; stats->factors = rs.dec.factors; stats->arena_bytes = dev ? ctx->c.arena.high : 0;
+        stats->flatten_rounds = rs.dec.rounds; stats->len_rounds = rs.len_rounds; stats->levels = rs.first_rounds; stats->small_levels = rs.segments;
+        stats->ms_h2d = rs.ms_h2d; stats->ms_factorize = rs.ms_grammar; stats->ms_d2h = rs.ms_text;
+        stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    ctx->last_decode_device = (int)rs.dec.device_parse;
+    sink_commit(s, n);
+}
 }  // namespace
 
 extern "C" {
@@ -174,6 +210,19 @@ int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t l
 int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap,
                                     size_t* out_len, uint64_t* factors, uint32_t* rounds) {
     return guarded(ctx, [&] { lzss_sw_decompress(ctx, stream, len, coder, window, sink_into(out, out_cap, out_len), factors, rounds); });
+}
+
+int tdc_gpu_repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t** out, size_t* out_len) {
+    return guarded(ctx, [&] { repair_decompress(ctx, stream, len, coder, sink_malloc(out, out_len, "NULL argument"), nullptr); });
+}
+
+int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len) {
+    return guarded(ctx, [&] { repair_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), nullptr); });
+}
+
+int tdc_gpu_repair_decompress_stats(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len,
+                                    tdc_gpu_stats* stats) {
+    return guarded(ctx, [&] { repair_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), stats); });
 }
 
 }  // extern "C"

@@ -296,6 +296,13 @@ size_t repair_arena(const Ctx& c, size_t n, u64 max_rules);
 // Writes the stream, terminator included, to d_out and returns its length.  bound: repair_bound (0: this kind is not taken).
 size_t repair_encode(Ctx& c, const u64* d_rules, size_t nrules, const u32* d_start, size_t nstart, int kind, u8* d_out, size_t out_cap);
 size_t repair_bound(size_t n, int kind);
+// :287-336 on the device (repair_decode.hip): kind 0 = BitCoder, 1 = EliasGammaCoder, 2 = EliasDeltaCoder.  True: the text is in `out`.
+// False: this stream keeps the host loop (option dec_parse, a grammar deeper than option repair_dec_rounds, a field beyond the device's
+// caps, more items than 32-bit indices count), nothing has been written.  *need, *n_out, what it throws: as decode_lzss_sw.
+// ms_h2d: the upload; ms_grammar: parse, lengths, positions, first occurrences; ms_text: items, reference resolver and download (host
+// clock around synchronisations).
+struct RepairDecodeStats { DecodeStats dec; u64 rules = 0, nstart = 0; u32 segments = 0, len_rounds = 0, first_rounds = 0; float ms_h2d = 0, ms_grammar = 0, ms_text = 0; };
+bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, size_t* need, RepairDecodeStats* st, size_t* n_out);
 
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform

@@ -612,9 +612,20 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
-    // :287-336 on the host (tdc_repair_decode: the rules expanded with an explicit stack; there is no device decoder yet)
+    // :287-336 -- the host loop (tdc_repair_decode: the rules expanded with an explicit stack), which needs no device; dec=gpu (an
+    // addition, as for lzss): the device decoder (tdc_gpu_repair_decompress, which keeps the host loop for coder=ascii).  The stream is
+    // the same either way.
     void decompress(Input& input, Output& output) override {
         const bytes& in = input.raw();
+        if (m_opts.get("dec", "host") == "gpu") {
+            if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+            uint8_t* out = nullptr; size_t out_len = 0;
+            const int rc = tdc_gpu_repair_decompress(m_ctx->h, in.data(), in.size(), m_coder, &out, &out_len);
+            if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+            output.write(out, out_len);
+            tdc_gpu_free(out);
+            return;
+        }
         size_t n = 0;
         int rc = tdc_repair_decode(in.data(), in.size(), m_coder, nullptr, 0, &n);
         bytes text(n ? n : 1);
@@ -815,6 +826,7 @@ inline std::vector<std::string> registered_algorithms() {
              "lzss(coder=bit | ascii | gamma | delta, window=16, threshold=3)             [sliding-window LZ77 factorized on the MI355X, window 1 .. 4096; host decoder]",
              "lzss(coder=bit | gamma | delta, dec=gpu)                                    [decompression parsed and resolved on the MI355X for streams of 1 MiB and more; ascii: host loop]",
              "repair(coder=bit | ascii | gamma | delta, max_rules=0)                      [Re-Pair grammar built on the MI355X: digram table, one rule per round; host decoder]",
+             "repair(coder=bit | gamma | delta, dec=gpu)                                  [decompression on the MI355X for streams of 1 MiB and more: tokens parsed side by side, grammar -> factor list; ascii: host loop]",
              "bwt                                                                         [MI355X: suffix array + one gather; host inverse loop]",
              "bwt(dec=gpu)                                                                [inverse on the MI355X: LF by a counting rank + list ranking of its cycle]",
              "rle                                                                         [MI355X; host decoder]",
@@ -859,7 +871,7 @@ inline Selection select_algorithm(const std::string& id, std::shared_ptr<GpuCont
         return s;
     }
     if (av.name == "repair") {
-        auto z = std::make_unique<RePairCompressor>(parse_algorithm_id(id, {"coder", "max_rules"}), std::move(ctx));
+        auto z = std::make_unique<RePairCompressor>(parse_algorithm_id(id, {"coder", "max_rules", "dec"}), std::move(ctx));
         z->set_device(device);
         s.compressor = std::move(z);
         return s;
