@@ -1,6 +1,6 @@
 // api_decompress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw, lzss and repair decompression.
 #include "api.hpp"
-#include "decode.hpp"
+#include "stream_parse.hpp"
 #include "../host/tdc_coders.hpp"
 
 #include <chrono>
@@ -95,7 +95,7 @@ void lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int
     size_t n = 0, need = 0;
     bool dev = false;
     if (coder != TDC_GPU_CODER_ASCII) {
-        const int kind = coder == TDC_GPU_CODER_BIT ? 0 : coder == TDC_GPU_CODER_GAMMA ? 1 : 2;
+        const int kind = dec_kind(coder);
         dev = run_decoder(s, "lzss: the stream decodes to more than 2^32 - 2 bytes", &need,
                           [&] { return (size_t)decode_lzss_sw(ctx->c, stream, len, kind, window, s, &need, &ds, &n); }) != 0;
     }
@@ -129,7 +129,7 @@ void repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int 
     size_t n = 0, need = 0;
     bool dev = false;
     if (coder == TDC_GPU_CODER_BIT || coder == TDC_GPU_CODER_GAMMA || coder == TDC_GPU_CODER_DELTA) {
-        const int kind = coder == TDC_GPU_CODER_BIT ? 0 : coder == TDC_GPU_CODER_GAMMA ? 1 : 2;
+        const int kind = dec_kind(coder);
         dev = run_decoder(s, "repair: the stream decodes to more than 2^32 - 2 bytes", &need,
                           [&] { return (size_t)decode_repair(ctx->c, stream, len, kind, s, &need, &rs, &n); }) != 0;
     }

@@ -876,6 +876,37 @@ void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d
     tick("download");
 }
 
+// The arena is too small for what follows: the live arrays travel to the host and back into an arena of `bytes` (the size this call
+// would have needed without moving, so that the next call of the same size on this context does not move again).
+void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live) {
+    std::vector<std::vector<u8>> keep;
+    for (const auto& a : live) {
+        keep.emplace_back(a.second);
+        if (a.second) HIP_TRY(hipMemcpyAsync(keep.back().data(), *a.first, a.second, hipMemcpyDeviceToHost, c.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    c.ensure_arena(bytes);
+    size_t i = 0;
+    for (const auto& a : live) {
+        *a.first = c.arena.alloc(a.second + 64);
+        if (a.second) HIP_TRY(hipMemcpyAsync(*a.first, keep[i].data(), a.second, hipMemcpyHostToDevice, c.stream));
+        ++i;
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+}
+
+DecTick dec_ticker(Ctx& c, const char* who) {
+    if (!c.dec_log) return [](const char*) {};
+    auto t_last = std::make_shared<std::chrono::steady_clock::time_point>(std::chrono::steady_clock::now());
+    hipStream_t s = c.stream;
+    return [=](const char* what) {                                                       // stage times on stderr (synchronises)
+        (void)hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s: %-26s %8.2f ms\n", who, what, std::chrono::duration<double, std::milli>(now - *t_last).count());
+        *t_last = now;
+    };
+}
+
 // What the device parse needs to know of a coder: its table and the widths of its variable fields.
 template <typename Tab> struct DevCoder {
     Tab tab;                                  // as the kernels read it

@@ -1,5 +1,6 @@
-// decode.hpp -- pieces of the lcpcomp decoder (decode.hip) that the LZ78 decoder (lz78_decode.hip) shares: the MSB-first bit
-// readers with the reference's terminator rule, and the device reference resolver behind both parses.
+// decode.hpp -- pieces of the lcpcomp decoder (decode.hip) that the other device decoders share: the MSB-first bit readers with the
+// reference's terminator rule, the device reference resolver behind every parse, the arena's move and the stage log.  The parse of
+// the token streams itself (lz78, lzw, lzss, repair) is stream_parse.hpp.
 #pragma once
 #include "stages.hpp"
 
@@ -19,17 +20,23 @@ constexpr unsigned DEC_MAX_BLOCKS = (1u << 24) - 1;
 static_assert((unsigned long long)DEC_MAX_BLOCKS * 256ull < (1ull << 32), "dispatch grid must stay below 2^32 work-items");
 inline unsigned dec_grid(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, DEC_MAX_BLOCKS); }
 
-// MSB-first reader over the reference's bit stream incl. its terminator rule (io/BitIStream.hpp:27-63, :191-193):
-// the low 3 bits of the last byte give the number of valid bits of the final data byte (6 and 7 live in an extra byte).
+// The reference's terminator rule (io/BitIStream.hpp:27-63, :191-193): the low 3 bits of the last byte give the number of valid bits
+// of the final data byte (6 and 7 live in an extra byte).  A stream of one byte holds the bits its low three bits announce, whatever
+// their number.
+inline u64 payload_bits(const u8* in, size_t n) {
+    if (n == 0) return 0;
+    const unsigned fb = in[n - 1] & 7u;
+    if (n == 1) return fb;
+    return fb >= 6 ? 8ull * (n - 2) + fb : 8ull * (n - 1) + fb;
+}
+
+// MSB-first reader over the reference's bit stream; a one-byte stream that announces 6 or 7 bits is refused
 struct FastBits {
     const u8* p;
     size_t nbytes;
     u64 total = 0, pos = 0;
-    FastBits(const u8* in, size_t n) : p(in), nbytes(n) {
-        if (n == 0) return;
-        const unsigned fb = in[n - 1] & 7u;
-        if (fb >= 6) { if (n < 2) throw StreamFormatError{"truncated stream"}; total = 8ull * (n - 2) + fb; }
-        else total = 8ull * (n - 1) + fb;
+    FastBits(const u8* in, size_t n) : p(in), nbytes(n), total(payload_bits(in, n)) {
+        if (n == 1 && total >= 6) throw StreamFormatError{"truncated stream"};
     }
     bool eof() const { return pos >= total; }
     // next 57 bits, left-aligned in the result's top bits (zeros beyond the end, like BitIStream::read_bit at eof)
@@ -61,6 +68,7 @@ struct FastBits {
 // 64 stream bits from absolute bit position x on (MSB first), zeros behind `total` (BitIStream reads zeros at eof).  `words` are the
 // stream's 32-bit words, byte-swapped so that bit 31 of word k is stream bit 32 k; word index kb is words[0].
 struct BitWin {
+    static constexpr u32 PEEK_WORDS = 3;                         // a peek at bit x touches the words of bits x .. x + 95 at most
     const u32* words; u64 kb; u64 total;
     __device__ __forceinline__ u64 peek(u64 x) const {
         if (x >= total) return 0ull;
@@ -97,15 +105,18 @@ u8* decode_dest(Sink& o, size_t n);
 void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
                           u32* d_changed, Sink& out, DecodeStats* st);
 
-
-// ---- what the LZ78 and the LZW decoder share (lz78_decode.hip) ---------------------------------------------------------------------
 // option dec_log: the time since the previous call, on stderr under `who` (synchronises the stream); nothing without the option
 using DecTick = std::function<void(const char*)>;
 DecTick dec_ticker(Ctx& c, const char* who);
+// The arena is too small for what follows: the live arrays (pointer, bytes) travel to the host and back into an arena of `bytes`;
+// the pointers are updated, everything else in the arena is gone.
+void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live);
+
+// ---- what the LZ78 and the LZW decoder share (lz78_decode.hip) ---------------------------------------------------------------------
 // Items of nv self-delimiting gamma codes (2: LZ78's (id, char) pairs, 1: one LZW code) from bit 0 of the uploaded stream s32 (padded
-// with 64 zero bytes) to bit `total`: next() of every bit position, the orbit of bit 0, the items decoded side by side -- segment by
-// segment (option dec_seg).  ids[k] (and chars[k], nv == 2) receive item k; item k must hold an id <= k + slack.  Returns the number
-// of items.  Malformed input: StreamFormatError; more than zcap items: DecodeItemOverflow, before anything is written behind zcap.
+// with 64 zero bytes) to bit `total`, by the segment loop of stream_parse.hpp.  ids[k] (and chars[k], nv == 2) receive item k; item k
+// must hold an id <= k + slack.  Returns the number of items.  Malformed input: StreamFormatError; more than zcap items:
+// DecodeItemOverflow, before anything is written behind zcap.
 struct DecodeItemOverflow { u64 items; };
 size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick);
 // Phrases -> text.  LZ78 (lzw = false): phrase k is phrase ids[k] - 1 (none for 0) followed by chars[k].  LZW: phrase k is the byte
@@ -115,8 +126,5 @@ size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, s
 // out.into is too small.  ids / chars lie in the arena, nothing above them is live.
 size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
                       const DecTick& tick);
-// The arena is too small for what follows: the live arrays (pointer, bytes) travel to the host and back into an arena of `bytes`;
-// the pointers are updated, everything else in the arena is gone (lz78_decode.hip).
-void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live);
 
 }  // namespace tdc

@@ -5,7 +5,8 @@
 // code is self-delimiting, so "where does the pair that starts at bit x end" depends on the bits behind x alone: next(x) is
 // evaluated for every bit position, the pair starts are the orbit of position 0 under next() (prim.hip mark_orbit_u32, the general
 // marking of the lcpcomp parse in decode.hip), and the pairs are decoded side by side.  Streams of more bit positions than one segment
-// (2^30, option dec_seg) take several segments; the exit of one is the entry of the next.
+// (2^30, option dec_seg) take several segments; the exit of one is the entry of the next.  The next() kernel, the segment loop and
+// the gamma reader are stream_parse.hpp's; lz_pair is the format.
 //
 // Phrase k is phrase id_k (1-based, 0 = the empty phrase) followed by c_k, so len_k = 1 + len_{id_k - 1} (1 for id_k = 0).  Ids point
 // backwards: pointer jumping over the parent links gives every length in O(log depth) rounds, a 64-bit exclusive scan gives every
@@ -23,19 +24,13 @@
 // below that) beside the LZ78 one.
 #include "stages.hpp"
 #include "prim.hpp"
-#include "decode.hpp"
-
-#include <chrono>
-#include <memory>
-#include <vector>
+#include "stream_parse.hpp"
 
 namespace tdc {
 
 namespace {
 
-constexpr u32 LZD_TILE = 32768;                                   // bit positions per workgroup of the next() pass
-constexpr u32 LZD_REACH = 2 * 32 + 1 + 2 * 64 + 1 + 64;           // bits behind a candidate that lz_pair may peek at (pair + window)
-constexpr u32 LZD_NW = (LZD_TILE + LZD_REACH + 31) / 32 + 4;      // stream words per workgroup
+constexpr u32 LZD_ID_BITS = 32, LZD_CHAR_BITS = 64;               // most value bits of the id field (a factorid_t) and of the char field
 #ifndef TDC_LZD_HOPS
 #define TDC_LZD_HOPS 16
 #endif
@@ -44,13 +39,10 @@ constexpr u32 LZD_NW = (LZD_TILE + LZD_REACH + 31) / 32 + 4;      // stream word
 // NV == 1: the item is the first code alone.
 template <int NV, typename Win>
 __device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end, u32& id, u32& ch) {
-    end = x; id = 0; ch = 0;
-    const u64 w = bw.peek(x);                                     // (zeros behind the end of the stream)
-    if (w == 0) return -1;
-    const u32 b1 = (u32)__builtin_clzll(w);
-    if (b1 > 32) return -1;                                       // id field wider than a factorid_t
-    if (b1) id = (u32)(bw.peek(x + b1 + 1) >> (64 - b1));
-    const u64 y = x + 2 * b1 + 1;
+    end = x; ch = 0;
+    u32 used;
+    if (read_field<DEC_GAMMA>(bw, x, LZD_ID_BITS, 0u, used, id) != FIELD_READ) return -1;     // (zeros up to the end, or wider than a factorid_t)
+    const u64 y = x + used;
     if (NV == 1) { end = y; return end > total ? -3 : 0; }
     const u64 v = bw.peek(y);
     u32 b2;
@@ -63,25 +55,16 @@ __device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end
     return 0;
 }
 
-// next() for the bit positions x_in .. x_in + m - 1 (index = position - x_in); m: the pair leaves the segment, or there is no pair
+// what stream_next_kernel asks (stream_parse.hpp)
 template <int NV>
-__global__ __launch_bounds__(256) void lz_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, u64 total, u32* __restrict__ next) {
-    __shared__ u32 sw[LZD_NW];
-    const u32 i0 = blockIdx.x * LZD_TILE;
-    const u64 kb = (x_in + i0) >> 5;
-    const u64 wmax = (total + 31) / 32 + 3;                       // (the buffer is padded: words up to here exist)
-    for (u32 k = threadIdx.x; k < LZD_NW; k += 256) sw[k] = (kb + k < wmax) ? __builtin_bswap32(s32[kb + k]) : 0u;
-    __syncthreads();
-    const BitWin bw{sw, kb, total};
-    for (u32 i = threadIdx.x; i < LZD_TILE; i += 256) {
-        const u32 idx = i0 + i;
-        if (idx >= m) break;
-        u64 end; u32 id, ch;
-        u32 r = m;
-        if (lz_pair<NV>(bw, x_in + idx, total, end, id, ch) == 0) { const u64 d = end - x_in; r = d < (u64)m ? (u32)d : m; }
-        next[idx] = r;
+struct LzTok {
+    static constexpr u32 REACH = field_span(DEC_GAMMA, LZD_ID_BITS, 0) + (NV == 2 ? 2 * LZD_CHAR_BITS + 1 : 0);
+    template <typename Win>
+    __device__ __forceinline__ bool at(const Win& bw, u64 x, u64& end) const {
+        u32 id, ch;
+        return lz_pair<NV>(bw, x, bw.total, end, id, ch) == 0;
     }
-}
+};
 
 struct LzScalars { u64 exit_bit; u32 err; u32 pad; };
 
@@ -179,71 +162,34 @@ __global__ void lzw_literal_kernel(const u32* __restrict__ fpos, const u32* __re
         if (codes[k] < 256u) text[fpos[k]] = (u8)codes[k];
 }
 
-}  // namespace
-
-// The arena is too small for what follows: the live arrays travel to the host and back into an arena of `bytes` (the size this call
-// would have needed without moving, so that the next call of the same size on this context does not move again).
-void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live) {
-    std::vector<std::vector<u8>> keep;
-    for (const auto& a : live) {
-        keep.emplace_back(a.second);
-        if (a.second) HIP_TRY(hipMemcpyAsync(keep.back().data(), *a.first, a.second, hipMemcpyDeviceToHost, c.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    c.ensure_arena(bytes);
-    size_t i = 0;
-    for (const auto& a : live) {
-        *a.first = c.arena.alloc(a.second + 64);
-        if (a.second) HIP_TRY(hipMemcpyAsync(*a.first, keep[i].data(), a.second, hipMemcpyHostToDevice, c.stream));
-        ++i;
-    }
-    HIP_TRY(hipStreamSynchronize(c.stream));
+template <int NV>
+size_t parse_items(Ctx& c, const u32* s32, u64 total, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick) {
+    constexpr bool PAIR = NV == 2;
+    hipStream_t s = c.stream;
+    LzScalars* d_sc = (LzScalars*)c.arena.alloc(sizeof(LzScalars));
+    HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(LzScalars), s));
+    size_t z = 0;
+    parse_segments(c, s32, total, 0, PAIR ? "pair list" : "code list", PAIR ? "corrupt stream: pair chain" : "corrupt stream: code chain", tick,
+        [](u64, u64&) { return LzTok<NV>{}; },
+        [&](u64 x_in, const u32* idx, u32 cnt, u32*) {
+            if (z + cnt > zcap) throw DecodeItemOverflow{z + cnt};
+            const unsigned g = std::min<u32>(cdiv(cnt, 256), 4096u);
+            lz_pairs_kernel<NV><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, slack, ids, chars, d_sc);
+            LAUNCH_CHECK();
+            const LzScalars h = c.read(d_sc);
+            tick(PAIR ? "pair decode" : "code decode");
+            z += cnt;
+            if (h.err & 1u) throw StreamFormatError{PAIR ? "corrupt stream: malformed or cut-off pair" : "corrupt stream: malformed or cut-off code"};
+            if (h.err & 2u) throw StreamFormatError{PAIR ? "corrupt stream: phrase id out of range" : "corrupt stream: invalid compressed code"};
+            return h.exit_bit;
+        });
+    return z;
 }
 
+}  // namespace
+
 size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, size_t zcap, u32* ids, u8* chars, const DecTick& tick) {
-    hipStream_t s = c.stream;
-    const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;                      // (tests shrink the segments)
-    LzScalars* d_sc = (LzScalars*)c.arena.alloc(sizeof(LzScalars));
-    u32* d_cnt = c.arena.get<u32>(2);
-    HIP_TRY(hipMemsetAsync(d_sc, 0, sizeof(LzScalars), s));
-    static const char* const BAD_CHAIN[2] = {"corrupt stream: code chain", "corrupt stream: pair chain"};
-    static const char* const BAD_ITEM[2] = {"corrupt stream: malformed or cut-off code", "corrupt stream: malformed or cut-off pair"};
-    static const char* const BAD_ID[2] = {"corrupt stream: invalid compressed code", "corrupt stream: phrase id out of range"};
-    size_t z = 0;
-    u64 x_in = 0;
-    while (x_in < total) {
-        const u32 m = (u32)std::min<u64>(seg_bits, total - x_in);
-        const size_t mk = c.arena.mark();
-        u32* next = c.arena.get<u32>(m);
-        u32* e1 = c.arena.get<u32>(m), *e2 = c.arena.get<u32>(m);
-        u8* mark = c.arena.get<u8>(m);
-        if (nv == 2) lz_next_kernel<2><<<cdiv(m, LZD_TILE), 256, 0, s>>>(s32, x_in, m, total, next);
-        else lz_next_kernel<1><<<cdiv(m, LZD_TILE), 256, 0, s>>>(s32, x_in, m, total, next);
-        LAUNCH_CHECK();
-        tick("next() of every bit");
-        mark_orbit_u32(c, next, m, mark, e1, e2);
-        tick("chain marking");
-        u32* idx = e1;                                                                  // (the exit arrays are free again)
-        select_by_class(c, mark, 1, m, nullptr, idx, nullptr, nullptr, d_cnt);
-        const u32 cnt = c.read(d_cnt);
-        tick(nv == 2 ? "pair list" : "code list");
-        if (cnt == 0) throw StreamFormatError{BAD_CHAIN[nv - 1]};
-        if (z + cnt > zcap) throw DecodeItemOverflow{z + cnt};
-        const unsigned g = std::min<u32>(cdiv(cnt, 256), 4096u);
-        if (nv == 2) lz_pairs_kernel<2><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, slack, ids, chars, d_sc);
-        else lz_pairs_kernel<1><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, (u64)z, slack, ids, chars, d_sc);
-        LAUNCH_CHECK();
-        const LzScalars h = c.read(d_sc);
-        tick(nv == 2 ? "pair decode" : "code decode");
-        c.arena.release(mk);
-        z += cnt;
-        if (h.err & 1u) throw StreamFormatError{BAD_ITEM[nv - 1]};
-        if (h.err & 2u) throw StreamFormatError{BAD_ID[nv - 1]};
-        if (h.exit_bit >= total) break;
-        if (h.exit_bit <= x_in) throw StreamFormatError{BAD_CHAIN[nv - 1]};
-        x_in = h.exit_bit;
-    }
-    return z;
+    return nv == 2 ? parse_items<2>(c, s32, total, slack, zcap, ids, chars, tick) : parse_items<1>(c, s32, total, slack, zcap, ids, chars, tick);
 }
 
 size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
@@ -340,18 +286,6 @@ size_t decode_lz78_gamma(Ctx& c, const u8* stream, size_t len, Sink& out, size_t
     catch (const DecodeItemOverflow& e) { throw DecodeTooLarge{e.items}; }              // (more pairs than 2^32 - 2: more bytes)
     st->factors = z;
     return expand_phrases(c, ids, chars, z, false, "lz78 decode: the caller's buffer is too small for the text", out, need, st, tick);
-}
-
-DecTick dec_ticker(Ctx& c, const char* who) {
-    if (!c.dec_log) return [](const char*) {};
-    auto t_last = std::make_shared<std::chrono::steady_clock::time_point>(std::chrono::steady_clock::now());
-    hipStream_t s = c.stream;
-    return [=](const char* what) {                                                       // stage times on stderr (synchronises)
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "%s: %-26s %8.2f ms\n", who, what, std::chrono::duration<double, std::milli>(now - *t_last).count());
-        *t_last = now;
-    };
 }
 
 }  // namespace tdc

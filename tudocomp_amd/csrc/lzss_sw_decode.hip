@@ -4,7 +4,7 @@
 //
 // The stream has no header: tokens until it ends, a literal = flag 0 + the byte, a factor = flag 1 + (p - s) + the length, p the text
 // position of the token.  Under gamma / delta every field is self-delimiting, so where the token that starts at bit x ends depends on
-// the bits behind x alone -- the situation of lz78_decode.hip: next(x) for every bit position, the orbit of the first bit, the tokens
+// the bits behind x alone -- the parse of stream_parse.hpp: next(x) for every bit position, the orbit of the first bit, the tokens
 // decoded side by side, segment by segment.  Under bit the distance takes bits_for(p) bits, which is constant while p stays in
 // [2^(k-1), 2^k): the segment loop carries the text position beside the bit position, evaluates next() with k = bits_for(p_in) for the
 // whole segment, and lets the first token whose text position has reached 2^k end the segment -- it and everything behind it are
@@ -20,10 +20,11 @@
 // (pos, pos - dist, len) to resolve_and_download, which takes sources that overlap their targets.
 //
 // Device caps (gamma / delta): a distance or length field of at most 32 value bits, a literal code of at most 8.  A wider field is no
-// token here, although the host loop reads it -- no encoder writes one; the caps bound how far next() looks behind a bit position.
+// token here, although the host loop reads it -- no encoder writes one; the caps bound how far next() looks behind a bit position
+// (SwdTok::REACH).
 #include "stages.hpp"
 #include "prim.hpp"
-#include "decode.hpp"
+#include "stream_parse.hpp"
 
 #include <stdio.h>
 #include <vector>
@@ -32,34 +33,14 @@ namespace tdc {
 
 namespace {
 
-constexpr u32 SWD_TILE = 32768;                                   // bit positions per LDS image of the next() pass
-constexpr u32 SWD_REACH = 256;                                    // bits behind a candidate that a token may peek at: flag + two fields of
-                                                                  // 32 + 1 + 32 bits (gamma; delta 6 + 1 + 6 + 32) + one 64-bit window
-constexpr u32 SWD_NW = (SWD_TILE + SWD_REACH + 31) / 32 + 4;      // stream words per image
 constexpr u64 SWD_TEXT_MAX = 0xFFFFFFFEull;
 constexpr u8 SWD_LIT = 0, SWD_FAC = 1, SWD_BAD = 2;               // class byte of a token
-constexpr int SWD_BIT = 0, SWD_GAMMA = 1, SWD_DELTA = 2;
+// the device caps: most value bits of a distance or length and of a literal code, and of delta's width code in front of each (bits_for
+// of the former)
+constexpr u32 SWD_FIELD_BITS = 32, SWD_FIELD_WBITS = 6, SWD_LIT_BITS = 8, SWD_LIT_WBITS = 4;
 
-// one gamma / delta field from bit y on: bits used (0: no token), value.  cap = most value bits (8 or 32).
-template <int KIND, typename Win>
-__device__ __forceinline__ u32 swd_field(const Win& bw, u64 y, u32 cap, u32& val) {
-    val = 0;
-    const u64 w = bw.peek(y);
-    if (!w) return 0u;                                            // zeros up to the window's or the stream's end
-    u32 b = (u32)__builtin_clzll(w), used = b + 1;
-    if (KIND == SWD_DELTA) {
-        if (b > 32u - (u32)__builtin_clz(cap)) return 0u;         // gamma(width), width <= cap: at most bits_for(cap) <= 6 bits
-        const u32 width = b ? (u32)((w << (b + 1)) >> (64 - b)) : 0u;
-        used += b;
-        b = width;
-    }
-    if (b > cap) return 0u;
-    if (b) val = (u32)(bw.peek(y + used) >> (64 - b));
-    return used + b;
-}
-
-// The token that starts at bit x: 0 and its end, kind, distance, length or byte; < 0: no token (malformed, or cut off by the end of
-// the stream).  k = bits_for(text position), lb = bits_for(window): the widths of the two fields of a factor under bit.
+// The token that starts at bit x: 0 and its end, kind, distance, length or byte; < 0: no token (malformed, beyond a cap, or cut off by
+// the end of the stream).  k = bits_for(text position), lb = bits_for(window): the widths of the two fields of a factor under bit.
 template <int KIND, typename Win>
 __device__ __forceinline__ int swd_token(const Win& bw, u64 x, u64 total, u32 k, u32 lb, u64& end, u32& fac, u32& dist, u32& val) {
     end = x; fac = 0; dist = 0; val = 0;
@@ -67,22 +48,20 @@ __device__ __forceinline__ int swd_token(const Win& bw, u64 x, u64 total, u32 k,
     const u64 w = bw.peek(x);
     fac = (u32)(w >> 63);
     u64 y = x + 1;
-    if (KIND == SWD_BIT) {
+    u32 u;
+    if (KIND == DEC_BIT) {
         if (!fac) { val = (u32)((w << 1) >> 56); y += 8; }
         else {
             dist = (u32)(bw.peek(y) >> (64 - k)); y += k;
             val = (u32)(bw.peek(y) >> (64 - lb)); y += lb;
         }
     } else if (!fac) {
-        const u32 u = swd_field<KIND>(bw, y, 8u, val);
-        if (!u) return -2;
+        if (read_field<KIND>(bw, y, SWD_LIT_BITS, SWD_LIT_WBITS, u, val) != FIELD_READ) return -2;
         y += u;
     } else {
-        u32 u = swd_field<KIND>(bw, y, 32u, dist);
-        if (!u) return -2;
+        if (read_field<KIND>(bw, y, SWD_FIELD_BITS, SWD_FIELD_WBITS, u, dist) != FIELD_READ) return -2;
         y += u;
-        u = swd_field<KIND>(bw, y, 32u, val);
-        if (!u) return -2;
+        if (read_field<KIND>(bw, y, SWD_FIELD_BITS, SWD_FIELD_WBITS, u, val) != FIELD_READ) return -2;
         y += u;
     }
     if (y > total) return -3;
@@ -90,29 +69,17 @@ __device__ __forceinline__ int swd_token(const Win& bw, u64 x, u64 total, u32 k,
     return 0;
 }
 
-// next() for the bit positions x_in .. x_in + m - 1 (index = position - x_in); m: the token leaves the segment, or there is none
+// what stream_next_kernel asks (stream_parse.hpp); a factor is the longer token
 template <int KIND>
-__global__ __launch_bounds__(256) void swd_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, u64 total, u32 k, u32 lb, u32 tiles,
-                                                        u32* __restrict__ next) {
-    __shared__ u32 sw[SWD_NW];
-    const u64 wmax = (total + 31) / 32 + 3;                       // (the buffer is padded with 64 zero bytes: words up to here exist)
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u32 i0 = tile * SWD_TILE;
-        const u64 kb = (x_in + i0) >> 5;
-        for (u32 j = threadIdx.x; j < SWD_NW; j += 256) sw[j] = (kb + j < wmax) ? __builtin_bswap32(s32[kb + j]) : 0u;
-        __syncthreads();
-        const BitWin bw{sw, kb, total};
-        for (u32 i = threadIdx.x; i < SWD_TILE; i += 256) {
-            const u32 idx = i0 + i;
-            if (idx >= m) break;
-            u64 end; u32 fac, dist, val;
-            u32 r = m;
-            if (swd_token<KIND>(bw, x_in + idx, total, k, lb, end, fac, dist, val) == 0) { const u64 d = end - x_in; r = d < (u64)m ? (u32)d : m; }
-            next[idx] = r;
-        }
-        __syncthreads();
+struct SwdTok {
+    static constexpr u32 REACH = 1 + (KIND == DEC_BIT ? 32 + 32 : 2 * field_span(KIND, SWD_FIELD_BITS, SWD_FIELD_WBITS));
+    u32 k, lb;
+    template <typename Win>
+    __device__ __forceinline__ bool at(const Win& bw, u64 x, u64& end) const {
+        u32 fac, dist, val;
+        return swd_token<KIND>(bw, x, bw.total, k, lb, end, fac, dist, val) == 0;
     }
-}
+};
 
 // first_bad / cut: index of the first refused token / of the first token at or behind 2^k in the segment's list (NONE32: none);
 // cut_x / cut_p: that token's bit offset in the segment and its text position; exit_bit: where the last listed token ends;
@@ -170,101 +137,60 @@ __global__ __launch_bounds__(256) void swd_literal_kernel(const u32* __restrict_
         if (cls[j] == SWD_LIT && (size_t)tpos[j] < n) text[tpos[j]] = (u8)tval[j];
 }
 
-inline u32 swd_bits_for(u64 v) { return v ? 64u - (u32)__builtin_clzll(v) : 1u; }
+struct SwdParse { size_t z = 0; u64 n = 0; SegCount seg; };
 
-// payload bits of the stream as BitIStream counts them (io/BitIStream.hpp:27-63): a stream of one byte holds the bits its low three
-// bits announce, whatever their number
-u64 swd_total_bits(const u8* in, size_t n) {
-    if (n == 0) return 0;
-    const unsigned fb = in[n - 1] & 7u;
-    if (n == 1) return fb;
-    return fb >= 6 ? 8ull * (n - 2) + fb : 8ull * (n - 1) + fb;
-}
-
-struct SwdParse { size_t z = 0; u64 n = 0; u32 segments = 0; u64 evaluated = 0; };
-
+// The segments of the stream (stream_parse.hpp).  tpos / tdist / tval / cls: zcap entries each.  More tokens than zcap:
+// DecodeItemOverflow, before anything is written behind zcap.
 template <int KIND>
-void swd_launch_next(hipStream_t s, const u32* s32, u64 x_in, u32 m, u64 total, u32 k, u32 lb, u32* next) {
-    const u32 tiles = cdiv(m, SWD_TILE);
-    swd_next_kernel<KIND><<<dec_grid((size_t)tiles * 256), 256, 0, s>>>(s32, x_in, m, total, k, lb, tiles, next);
-}
-template <int KIND>
-void swd_launch_tokens(hipStream_t s, unsigned g, const u32* s32, u64 x_in, const u32* idx, u32 cnt, u64 total, u32 k, u32 lb, u32* tdist,
-                       u32* tval, u8* cls, u64* adv, SwdScalars* sc) {
-    swd_tokens_kernel<KIND><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, k, lb, tdist, tval, cls, adv, sc);
-}
-
-// The segment loop.  tpos / tdist / tval / cls: zcap entries each.  More tokens than zcap: DecodeItemOverflow, before anything is written
-// behind zcap.
-SwdParse swd_parse(Ctx& c, const u32* s32, u64 total, int kind, u32 lb, size_t zcap, u32* tpos, u32* tdist, u32* tval, u8* cls, const DecTick& tick) {
+SwdParse swd_parse(Ctx& c, const u32* s32, u64 total, u32 lb, size_t zcap, u32* tpos, u32* tdist, u32* tval, u8* cls, const DecTick& tick) {
     hipStream_t s = c.stream;
-    const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;
     SwdScalars* d_sc = (SwdScalars*)c.arena.alloc(sizeof(SwdScalars));
-    u32* d_cnt = c.arena.get<u32>(2);
     SwdParse r;
-    u64 x_in = 0, p_in = 0;
+    u64 p_in = 0, lim = 0;
+    u32 k = 0;
     double rate = 9.0;                                            // bits per text position, as the segment before had them (bit: a literal's)
-    while (x_in < total) {
-        u64 mm = std::min<u64>(seg_bits, total - x_in);
-        u32 k = 0;
-        u64 lim = 0;
-        if (kind == SWD_BIT) {
-            k = swd_bits_for(p_in);                               // (p_in <= 2^32 - 2: k <= 32)
-            if (k < 32) {
-                lim = 1ull << k;
-                const double est = (double)(lim - p_in) * rate * (1.0 + 1.0 / 64) + 4096.0;     // what the rest of the stretch should hold
-                if (est < (double)mm) mm = (u64)est;
+    r.seg = parse_segments(c, s32, total, 0, "token list", "corrupt stream: token chain", tick,
+        [&](u64, u64& mm) {
+            k = 0; lim = 0;
+            if (KIND == DEC_BIT) {
+                k = bits_for(p_in);                               // (p_in <= 2^32 - 2: k <= 32)
+                if (k < 32) {
+                    lim = 1ull << k;
+                    const double est = (double)(lim - p_in) * rate * (1.0 + 1.0 / 64) + 4096.0;     // what the rest of the stretch should hold
+                    if (est < (double)mm) mm = (u64)est;
+                }
             }
-        }
-        const u32 m = (u32)mm;
-        const size_t mk = c.arena.mark();
-        u32* next = c.arena.get<u32>(m);
-        u32* e1 = c.arena.get<u32>(m), *e2 = c.arena.get<u32>((size_t)m + 4);
-        u8* mark = c.arena.get<u8>(m);
-        if (kind == SWD_BIT) swd_launch_next<SWD_BIT>(s, s32, x_in, m, total, k, lb, next);
-        else if (kind == SWD_GAMMA) swd_launch_next<SWD_GAMMA>(s, s32, x_in, m, total, k, lb, next);
-        else swd_launch_next<SWD_DELTA>(s, s32, x_in, m, total, k, lb, next);
-        LAUNCH_CHECK();
-        tick("next() of every bit");
-        mark_orbit_u32(c, next, m, mark, e1, e2);
-        tick("chain marking");
-        u32* idx = e1;                                            // (the exit arrays are free again)
-        select_by_class(c, mark, 1, m, nullptr, idx, nullptr, nullptr, d_cnt);
-        const u32 cnt = c.read(d_cnt);
-        tick("token list");
-        if (cnt == 0) throw StreamFormatError{"corrupt stream: token chain"};
-        if (r.z + cnt > zcap) throw DecodeItemOverflow{r.z + cnt};
-        u64* adv = (u64*)e2;                                      // (a token takes 2 bits at least: cnt <= m / 2 + 1 entries fit m + 4 words)
-        HIP_TRY(hipMemsetAsync(d_sc, 0xFF, sizeof(SwdScalars), s));
-        const unsigned g = dec_grid(cnt);
-        if (kind == SWD_BIT) swd_launch_tokens<SWD_BIT>(s, g, s32, x_in, idx, cnt, total, k, lb, tdist + r.z, tval + r.z, cls + r.z, adv, d_sc);
-        else if (kind == SWD_GAMMA) swd_launch_tokens<SWD_GAMMA>(s, g, s32, x_in, idx, cnt, total, k, lb, tdist + r.z, tval + r.z, cls + r.z, adv, d_sc);
-        else swd_launch_tokens<SWD_DELTA>(s, g, s32, x_in, idx, cnt, total, k, lb, tdist + r.z, tval + r.z, cls + r.z, adv, d_sc);
-        LAUNCH_CHECK();
-        exclusive_sum_u64(c, adv, adv, cnt, &d_sc->sum);
-        swd_place_kernel<<<g, 256, 0, s>>>(idx, adv, cnt, p_in, lim, tdist + r.z, cls + r.z, tpos + r.z, d_sc);
-        LAUNCH_CHECK();
-        const SwdScalars h = c.read(d_sc);
-        tick("token decode + positions");
-        const u32 keep = h.cut < cnt ? h.cut : cnt;               // the tokens in front of the cut
-        if (h.first_bad < keep) {
-            // the host loop meets the tokens one by one: a text that has outgrown the format in front of the refused token is what it reports
-            const u64 p_bad = p_in + c.read(adv + h.first_bad);
-            if (p_bad > SWD_TEXT_MAX) throw DecodeTooLarge{p_bad};
-            throw StreamFormatError{"corrupt stream: malformed or cut-off token, or a factor source out of range"};
-        }
-        c.arena.release(mk);
-        r.segments += 1;
-        r.evaluated += m;
-        u64 x_out, p_out;
-        if (h.cut < cnt) { x_out = x_in + h.cut_x; p_out = h.cut_p; }
-        else { x_out = h.exit_bit; p_out = p_in + h.sum; }
-        r.z += keep;
-        if (x_out <= x_in) throw StreamFormatError{"corrupt stream: token chain"};
-        if (p_out > p_in) rate = std::max(0.01, (double)(x_out - x_in) / (double)(p_out - p_in));
-        x_in = x_out; p_in = p_out;
-        if (p_in > SWD_TEXT_MAX) throw DecodeTooLarge{p_in};        // (also keeps bits_for(p_in) <= 32)
-    }
+            return SwdTok<KIND>{k, lb};
+        },
+        [&](u64 x_in, const u32* idx, u32 cnt, u32* e2) {
+            if (r.z + cnt > zcap) throw DecodeItemOverflow{r.z + cnt};
+            u64* adv = (u64*)e2;                                  // (a token takes 2 bits at least: cnt <= m / 2 + 1 entries fit m + 4 words)
+            HIP_TRY(hipMemsetAsync(d_sc, 0xFF, sizeof(SwdScalars), s));
+            const unsigned g = dec_grid(cnt);
+            swd_tokens_kernel<KIND><<<g, 256, 0, s>>>(s32, x_in, idx, cnt, total, k, lb, tdist + r.z, tval + r.z, cls + r.z, adv, d_sc);
+            LAUNCH_CHECK();
+            exclusive_sum_u64(c, adv, adv, cnt, &d_sc->sum);
+            swd_place_kernel<<<g, 256, 0, s>>>(idx, adv, cnt, p_in, lim, tdist + r.z, cls + r.z, tpos + r.z, d_sc);
+            LAUNCH_CHECK();
+            const SwdScalars h = c.read(d_sc);
+            tick("token decode + positions");
+            const u32 keep = h.cut < cnt ? h.cut : cnt;           // the tokens in front of the cut
+            if (h.first_bad < keep) {
+                // the host loop meets the tokens one by one: a text that has outgrown the format in front of the refused token is what it reports
+                const u64 p_bad = p_in + c.read(adv + h.first_bad);
+                if (p_bad > SWD_TEXT_MAX) throw DecodeTooLarge{p_bad};
+                throw StreamFormatError{"corrupt stream: malformed or cut-off token, or a factor source out of range"};
+            }
+            // every token in front of x_out was read, and the cut is not the first one (p_in < 2^k): x_out > x_in
+            u64 x_out, p_out;
+            if (h.cut < cnt) { x_out = x_in + h.cut_x; p_out = h.cut_p; }
+            else { x_out = h.exit_bit; p_out = p_in + h.sum; }
+            r.z += keep;
+            if (p_out > p_in) rate = std::max(0.01, (double)(x_out - x_in) / (double)(p_out - p_in));
+            p_in = p_out;
+            if (p_in > SWD_TEXT_MAX) throw DecodeTooLarge{p_in};    // (also keeps bits_for(p_in) <= 32)
+            return x_out;
+        });
     r.n = p_in;
     return r;
 }
@@ -278,11 +204,11 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
     *n_out = 0;
     // option dec_parse: 1 = the device for streams of 1 MiB and more, 2 = every stream, 0 = the host loop
     if (!c.dec_parse || (c.dec_parse < 2 && len < ((size_t)1 << 20))) return false;
-    const u64 total = swd_total_bits(stream, len);
+    const u64 total = payload_bits(stream, len);
     if (total == 0) { decode_dest(out, 0); if (need) *need = 0; return true; }           // no token: the empty text
     hipStream_t s = c.stream;
     const DecTick tick = dec_ticker(c, "lzss decode");
-    const u32 lb = swd_bits_for(window);
+    const u32 lb = bits_for(window);
     const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;
     const size_t seg = (size_t)std::min<u64>(seg_bits, total);
     const size_t slack = (size_t)16 << 20;
@@ -291,8 +217,8 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
     // (they count until the cut is known) -- one per 8 bits leaves room for those.  gamma / delta: an encoder's shortest token is a
     // literal below 2 in 4 bits, the shortest the decoder reads "0" "1", the byte 0, in 2.  The arrays are sized for the first figure
     // and the parse starts over with room for the second where a stream needs it.
-    u64 zcap = kind == SWD_BIT ? total / 8 + 4096 : total / 4 + 2;
-    const u64 zmax = kind == SWD_BIT ? total / 3 + 4096 : total / 2 + 2;
+    u64 zcap = kind == DEC_BIT ? total / 8 + 4096 : total / 4 + 2;
+    const u64 zmax = kind == DEC_BIT ? total / 3 + 4096 : total / 2 + 2;
     SwdParse P;
     u32* tpos = nullptr, *tdist = nullptr, *tval = nullptr;
     u8* cls = nullptr;
@@ -307,7 +233,10 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
         tick("upload");
         tpos = c.arena.get<u32>(zcap); tdist = c.arena.get<u32>(zcap); tval = c.arena.get<u32>(zcap);
         cls = c.arena.get<u8>(zcap);
-        try { P = swd_parse(c, (const u32*)d_stream, total, kind, lb, (size_t)zcap, tpos, tdist, tval, cls, tick); break; }   // (arena allocations are 256-byte aligned)
+        try {                                                     // (arena allocations are 256-byte aligned)
+            P = with_dec_kind(kind, [&](auto K) { return swd_parse<decltype(K)::value>(c, (const u32*)d_stream, total, lb, (size_t)zcap, tpos, tdist, tval, cls, tick); });
+            break;
+        }
         catch (const DecodeItemOverflow&) {
             if (zcap >= zmax) throw HipError{hipErrorUnknown, "lzss decode: more tokens than the stream can hold", (int)__LINE__};
             zcap = zmax;
@@ -316,8 +245,8 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
     st->device_parse = 1;
     const size_t z = P.z, n = (size_t)P.n;
     if (c.dec_log)
-        fprintf(stderr, "lzss decode: %u segments, next() evaluated for %llu bit positions (%.4f of the stream's %llu), %zu tokens\n", P.segments,
-                (unsigned long long)P.evaluated, (double)P.evaluated / (double)total, (unsigned long long)total, z);
+        fprintf(stderr, "lzss decode: %u segments, next() evaluated for %llu bit positions (%.4f of the stream's %llu), %zu tokens\n", P.seg.segments,
+                (unsigned long long)P.seg.evaluated, (double)P.seg.evaluated / (double)total, (unsigned long long)total, z);
     if (need) *need = n;
     *n_out = n;
     if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, "lzss decode: the caller's buffer is too small for the text", (int)__LINE__};

@@ -6,7 +6,7 @@
 //
 // The stream: the number of rules R, both sides of rule 0 .. R - 1, the start sequence until the stream ends.  A side or start symbol is a
 // token: a flag, then a byte or a rule index.  The host reads R.  Under gamma / delta every field is self-delimiting: next() for every bit
-// position, the orbit of the first token's bit, the tokens decoded side by side, segment by segment, as in lzss_sw_decode.hip; token
+// position, the orbit of the first token's bit, the tokens decoded side by side, segment by segment (stream_parse.hpp); token
 // ordinal 2 R is where the start sequence begins.  Under bit the index of a side of rule i takes bits_for(i) bits, constant over
 // [2^(w-1), 2^w), and bits_for(R) in the start sequence: a segment reads with ONE width and takes from its token list exactly the tokens
 // the stretch still holds (their number is known: twice its rules) -- everything behind was read with the wrong width, the next segment
@@ -22,7 +22,7 @@
 // one).  A token that crosses one is classed RPD_WIDE and the whole stream goes to the host loop.
 #include "stages.hpp"
 #include "prim.hpp"
-#include "decode.hpp"
+#include "stream_parse.hpp"
 
 #include <chrono>
 #include <stdio.h>
@@ -32,38 +32,16 @@ namespace tdc {
 
 namespace {
 
-constexpr u32 RPD_TILE = 32768;                                   // bit positions per LDS image of the next() pass
-constexpr u32 RPD_REACH = 256;                                    // bits behind a candidate that a token may peek at: flag + 33 + 32 bits
-                                                                  // (gamma; delta 7 + 6 + 32) + one 64-bit window
-constexpr u32 RPD_NW = (RPD_TILE + RPD_REACH + 31) / 32 + 4;      // stream words per image
 constexpr u64 RPD_TEXT_MAX = 0xFFFFFFFEull;
 constexpr u32 RPD_NONE = 0xFFFFFFFFu;
 constexpr u32 RPD_HOST_RULES = 4096;                              // bit: the host reads the rules below this index
 constexpr u32 RPD_BATCH = 8;                                      // rounds per read-back of the change flags
-constexpr int RPD_OK = 0, RPD_BAD = 1, RPD_WIDE = 2;              // class of a token: read, refused by the host loop too, beyond a device cap
-constexpr int RPD_BIT = 0, RPD_GAMMA = 1, RPD_DELTA = 2;
+// class of a token: read, refused by the host loop too (a field of zeros up to the end of the stream, a cut-off token), beyond a device cap
+constexpr int RPD_OK = FIELD_READ, RPD_BAD = FIELD_END, RPD_WIDE = FIELD_WIDE;
+// the device caps: most value bits of an index and of a literal code, and of delta's width code in front of either
+constexpr u32 RPD_INDEX_BITS = 32, RPD_LIT_BITS = 8, RPD_WBITS = 6;
 
 struct RpdToHost {};                                              // the host loop has the verdict on this stream
-
-// one gamma / delta field from bit y on: its class, bits used, value.  cap = most value bits (8 or 32).  RPD_BAD only where the host
-// loop refuses for certain (zeros up to the end of the stream); whatever else is not read here is RPD_WIDE.
-template <int KIND, typename Win>
-__device__ __forceinline__ int rpd_field(const Win& bw, u64 y, u64 total, u32 cap, u32& used, u32& val) {
-    used = 0; val = 0;
-    const u64 w = bw.peek(y);
-    if (!w) return y + 64 > total ? RPD_BAD : RPD_WIDE;
-    u32 b = (u32)__builtin_clzll(w), u = b + 1;
-    if (KIND == RPD_DELTA) {
-        if (b > 6u) return RPD_WIDE;                              // gamma(width) with more than 6 value bits
-        const u32 width = b ? (u32)((w << (b + 1)) >> (64 - b)) : 0u;
-        u += b;
-        b = width;
-    }
-    if (b > cap) return RPD_WIDE;
-    if (b) val = (u32)(bw.peek(y + u) >> (64 - b));
-    used = u + b;
-    return RPD_OK;
-}
 
 // The token that starts at bit x: class, end, flag (1: a rule index) and value.  w: width of an index under bit.  A token cut off by the
 // end of the stream is RPD_BAD.
@@ -74,12 +52,12 @@ __device__ __forceinline__ int rpd_token(const Win& bw, u64 x, u64 total, u32 w,
     const u64 win = bw.peek(x);
     rule = (u32)(win >> 63);
     u64 y = x + 1;
-    if (KIND == RPD_BIT) {
+    if (KIND == DEC_BIT) {
         if (!rule) { val = (u32)((win << 1) >> 56); y += 8; }
         else { val = (u32)(bw.peek(y) >> (64 - w)); y += w; }
     } else {
         u32 used;
-        const int st = rpd_field<KIND>(bw, y, total, rule ? 32u : 8u, used, val);
+        const int st = read_field<KIND>(bw, y, rule ? RPD_INDEX_BITS : RPD_LIT_BITS, RPD_WBITS, used, val);
         if (st != RPD_OK) return st;
         y += used;
     }
@@ -88,29 +66,17 @@ __device__ __forceinline__ int rpd_token(const Win& bw, u64 x, u64 total, u32 w,
     return RPD_OK;
 }
 
-// next() for the bit positions x_in .. x_in + m - 1 (index = position - x_in); m: the token leaves the segment, or there is none
+// what stream_next_kernel asks (stream_parse.hpp); an index is the longer token
 template <int KIND>
-__global__ __launch_bounds__(256) void rpd_next_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, u64 total, u32 w, u32 tiles,
-                                                        u32* __restrict__ next) {
-    __shared__ u32 sw[RPD_NW];
-    const u64 wmax = (total + 31) / 32 + 3;                       // (the buffer is padded with 64 zero bytes: words up to here exist)
-    for (u32 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const u32 i0 = tile * RPD_TILE;
-        const u64 kb = (x_in + i0) >> 5;
-        for (u32 j = threadIdx.x; j < RPD_NW; j += 256) sw[j] = (kb + j < wmax) ? __builtin_bswap32(s32[kb + j]) : 0u;
-        __syncthreads();
-        const BitWin bw{sw, kb, total};
-        for (u32 i = threadIdx.x; i < RPD_TILE; i += 256) {
-            const u32 idx = i0 + i;
-            if (idx >= m) break;
-            u64 end; u32 rule, val;
-            u32 r = m;
-            if (rpd_token<KIND>(bw, x_in + idx, total, w, end, rule, val) == RPD_OK) { const u64 d = end - x_in; r = d < (u64)m ? (u32)d : m; }
-            next[idx] = r;
-        }
-        __syncthreads();
+struct RpdTok {
+    static constexpr u32 REACH = 1 + (KIND == DEC_BIT ? 32 : field_span(KIND, RPD_INDEX_BITS, RPD_WBITS));
+    u32 w;
+    template <typename Win>
+    __device__ __forceinline__ bool at(const Win& bw, u64 x, u64& end) const {
+        u32 rule, val;
+        return rpd_token<KIND>(bw, x, bw.total, w, end, rule, val) == RPD_OK;
     }
-}
+};
 
 // first_bad: (index << 2 | class) of the first token of the segment's list that is not RPD_OK (all ones: none); exit_bit: where the
 // last taken token ends
@@ -222,15 +188,6 @@ __global__ __launch_bounds__(256) void rpd_factor_kernel(const u32* __restrict__
     }
 }
 
-// payload bits of the stream as BitIStream counts them (io/BitIStream.hpp:27-63): a stream of one byte holds the bits its low three
-// bits announce, whatever their number
-u64 rpd_total_bits(const u8* in, size_t n) {
-    if (n == 0) return 0;
-    const unsigned fb = in[n - 1] & 7u;
-    if (n == 1) return fb;
-    return fb >= 6 ? 8ull * (n - 2) + fb : 8ull * (n - 1) + fb;
-}
-
 // nb <= 32 bits from bit `pos` on; the caller has checked pos + nb <= total
 u32 rpd_host_bits(const u8* in, u64 pos, u32 nb) {
     u32 v = 0;
@@ -251,7 +208,7 @@ bool rpd_host_code(const u8* in, u64 total, int kind, u64& pos, u32& val) {
         pos += b;
         return true;
     };
-    if (kind == RPD_GAMMA) return gamma(32, val);
+    if (kind == DEC_GAMMA) return gamma(32, val);
     u32 width;
     if (!gamma(6, width) || width > 32 || pos + width > total) return false;
     val = rpd_host_bits(in, pos, width);
@@ -259,80 +216,53 @@ bool rpd_host_code(const u8* in, u64 total, int kind, u64& pos, u32& val) {
     return true;
 }
 
-struct RpdParse { size_t z = 0; u32 segments = 0; u64 evaluated = 0; };
+struct RpdParse { size_t z = 0; SegCount seg; };
 
+// The segments from bit x0 and token ordinal t_in on (stream_parse.hpp).  sym: zcap entries, the first t_in are filled.  More tokens
+// than zcap: DecodeItemOverflow, before anything is written behind zcap.
 template <int KIND>
-void rpd_launch_next(hipStream_t s, const u32* s32, u64 x_in, u32 m, u64 total, u32 w, u32* next) {
-    const u32 tiles = cdiv(m, RPD_TILE);
-    rpd_next_kernel<KIND><<<dec_grid((size_t)tiles * 256), 256, 0, s>>>(s32, x_in, m, total, w, tiles, next);
-}
-
-// The segment loop from bit x_in and token ordinal t_in on.  sym: zcap entries, the first t_in are filled.  More tokens than zcap:
-// DecodeItemOverflow, before anything is written behind zcap.
-RpdParse rpd_parse(Ctx& c, const u32* s32, u64 total, int kind, u64 R, u64 x_in, u64 t_in, size_t zcap, u32* sym, const DecTick& tick) {
+RpdParse rpd_parse(Ctx& c, const u32* s32, u64 total, u64 R, u64 x0, u64 t_in, size_t zcap, u32* sym, const DecTick& tick) {
     hipStream_t s = c.stream;
-    const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;
     RpdScalars* d_sc = (RpdScalars*)c.arena.alloc(sizeof(RpdScalars));
-    u32* d_cnt = c.arena.get<u32>(2);
     RpdParse r;
     r.z = (size_t)t_in;
     double rate = 0;                                              // bits per token, as the segment before had them
-    while (x_in < total) {
-        u64 mm = std::min<u64>(seg_bits, total - x_in);
-        u32 w = 0;
-        u64 left = ~0ull;                                         // tokens the stretch still holds
-        if (kind == RPD_BIT) {
-            const u64 t = r.z;
-            if (t >= 2 * R) w = bits_for(R);
-            else {
-                const u64 i = t >> 1;
-                w = bits_for(i);
-                const u64 stop = std::min<u64>(i < 2 ? 2 : 1ull << w, R);        // the first rule of the next stretch
-                left = 2 * stop - t;
-                if (rate == 0) rate = 1.0 + std::max(8u, w);
-                const double est = (double)left * rate * (1.0 + 1.0 / 64) + 4096.0;
-                if (est < (double)mm) mm = (u64)est;
+    u32 w = 0;
+    u64 left = ~0ull;                                             // tokens the stretch still holds
+    r.seg = parse_segments(c, s32, total, x0, "token list", "corrupt stream: token chain", tick,
+        [&](u64, u64& mm) {
+            w = 0; left = ~0ull;
+            if (KIND == DEC_BIT) {
+                const u64 t = r.z;
+                if (t >= 2 * R) w = bits_for(R);
+                else {
+                    const u64 i = t >> 1;
+                    w = bits_for(i);
+                    const u64 stop = std::min<u64>(i < 2 ? 2 : 1ull << w, R);        // the first rule of the next stretch
+                    left = 2 * stop - t;
+                    if (rate == 0) rate = 1.0 + std::max(8u, w);
+                    const double est = (double)left * rate * (1.0 + 1.0 / 64) + 4096.0;
+                    if (est < (double)mm) mm = (u64)est;
+                }
             }
-        }
-        const u32 m = (u32)mm;
-        const size_t mk = c.arena.mark();
-        u32* next = c.arena.get<u32>(m);
-        u32* e1 = c.arena.get<u32>(m), *e2 = c.arena.get<u32>((size_t)m + 4);
-        u8* mark = c.arena.get<u8>(m);
-        if (kind == RPD_BIT) rpd_launch_next<RPD_BIT>(s, s32, x_in, m, total, w, next);
-        else if (kind == RPD_GAMMA) rpd_launch_next<RPD_GAMMA>(s, s32, x_in, m, total, w, next);
-        else rpd_launch_next<RPD_DELTA>(s, s32, x_in, m, total, w, next);
-        LAUNCH_CHECK();
-        tick("next() of every bit");
-        mark_orbit_u32(c, next, m, mark, e1, e2);
-        tick("chain marking");
-        u32* idx = e1;                                            // (the exit arrays are free again)
-        select_by_class(c, mark, 1, m, nullptr, idx, nullptr, nullptr, d_cnt);
-        const u32 cnt = c.read(d_cnt);
-        tick("token list");
-        if (cnt == 0) throw StreamFormatError{"corrupt stream: token chain"};
-        const u32 keep = (u32)std::min<u64>(cnt, left);
-        if (r.z + keep > zcap) throw DecodeItemOverflow{r.z + keep};
-        HIP_TRY(hipMemsetAsync(d_sc, 0xFF, sizeof(RpdScalars), s));
-        const unsigned g = dec_grid(keep);
-        if (kind == RPD_BIT) rpd_tokens_kernel<RPD_BIT><<<g, 256, 0, s>>>(s32, x_in, idx, keep, total, w, r.z, R, sym + r.z, d_sc);
-        else if (kind == RPD_GAMMA) rpd_tokens_kernel<RPD_GAMMA><<<g, 256, 0, s>>>(s32, x_in, idx, keep, total, w, r.z, R, sym + r.z, d_sc);
-        else rpd_tokens_kernel<RPD_DELTA><<<g, 256, 0, s>>>(s32, x_in, idx, keep, total, w, r.z, R, sym + r.z, d_sc);
-        LAUNCH_CHECK();
-        const RpdScalars h = c.read(d_sc);
-        tick("token decode");
-        if (h.first_bad != ~0ull) {
-            if ((h.first_bad & 3) == (u64)RPD_WIDE) throw RpdToHost{};
-            throw StreamFormatError{"corrupt stream: malformed or cut-off token, or a rule index out of range"};
-        }
-        c.arena.release(mk);
-        if (h.exit_bit <= x_in) throw StreamFormatError{"corrupt stream: token chain"};
-        rate = (double)(h.exit_bit - x_in) / (double)keep;
-        r.segments += 1;
-        r.evaluated += m;
-        r.z += keep;
-        x_in = h.exit_bit;
-    }
+            return RpdTok<KIND>{w};
+        },
+        [&](u64 x_in, const u32* idx, u32 cnt, u32*) {
+            const u32 keep = (u32)std::min<u64>(cnt, left);
+            if (r.z + keep > zcap) throw DecodeItemOverflow{r.z + keep};
+            HIP_TRY(hipMemsetAsync(d_sc, 0xFF, sizeof(RpdScalars), s));
+            rpd_tokens_kernel<KIND><<<dec_grid(keep), 256, 0, s>>>(s32, x_in, idx, keep, total, w, r.z, R, sym + r.z, d_sc);
+            LAUNCH_CHECK();
+            const RpdScalars h = c.read(d_sc);
+            tick("token decode");
+            if (h.first_bad != ~0ull) {
+                if ((h.first_bad & 3) == (u64)RPD_WIDE) throw RpdToHost{};
+                throw StreamFormatError{"corrupt stream: malformed or cut-off token, or a rule index out of range"};
+            }
+            rate = (double)(h.exit_bit - x_in) / (double)keep;
+            r.z += keep;
+            return h.exit_bit;
+        });
     return r;
 }
 
@@ -361,11 +291,11 @@ bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, si
     *n_out = 0;
     // option dec_parse: 1 = the device for streams of 1 MiB and more, 2 = every stream, 0 = the host loop
     if (!c.dec_parse || (c.dec_parse < 2 && len < ((size_t)1 << 20))) return false;
-    const u64 total = rpd_total_bits(stream, len);
+    const u64 total = payload_bits(stream, len);
 
     // ---- the host's part: the count field and, under bit, the rules below RPD_HOST_RULES
     u64 x0 = 0, R = 0;
-    if (kind == RPD_BIT) {
+    if (kind == DEC_BIT) {
         if (total < 32) throw StreamFormatError{"corrupt stream: cut-off field"};
         R = rpd_host_bits(stream, 0, 32);
         x0 = 32;
@@ -376,7 +306,7 @@ bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, si
     }
     if (R > 2 * (u64)len) throw StreamFormatError{"corrupt stream: more rules than the stream can hold"};
     std::vector<u32> head;
-    if (kind == RPD_BIT) {
+    if (kind == DEC_BIT) {
         const u32 H = (u32)std::min<u64>(R, RPD_HOST_RULES);
         head.resize(2 * (size_t)H);
         for (u32 t = 0; t < 2 * H; ++t) {
@@ -414,7 +344,7 @@ bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, si
     // decoder reads is "1" "1", the rule 0, in 2.  The array is sized for the first figure and the parse starts over with room for the
     // second where a stream needs it.
     const u64 rem = total - x0;
-    u64 zcap = head.size() + (kind == RPD_BIT ? rem / 8 + 4096 : rem / 4 + 2);
+    u64 zcap = head.size() + (kind == DEC_BIT ? rem / 8 + 4096 : rem / 4 + 2);
     const u64 zmax = head.size() + rem / 2 + 2;
     RpdParse P;
     u32* sym = nullptr;
@@ -432,7 +362,10 @@ bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, si
             if (!head.empty()) HIP_TRY(hipMemcpyAsync(sym, head.data(), head.size() * 4, hipMemcpyHostToDevice, s));
             st->ms_h2d = lap(t_lap);
             tick("upload");
-            try { P = rpd_parse(c, (const u32*)d_stream, total, kind, R, x0, head.size(), (size_t)zcap, sym, tick); break; }
+            try {
+                P = with_dec_kind(kind, [&](auto K) { return rpd_parse<decltype(K)::value>(c, (const u32*)d_stream, total, R, x0, head.size(), (size_t)zcap, sym, tick); });
+                break;
+            }
             catch (const DecodeItemOverflow&) {
                 if (zcap >= zmax) throw HipError{hipErrorUnknown, "repair decode: more tokens than the stream can hold", (int)__LINE__};
                 zcap = zmax;
@@ -477,10 +410,10 @@ bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, si
     if (need) *need = n;
     *n_out = n;
     if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, "repair decode: the caller's buffer is too small for the text", (int)__LINE__};
-    st->rules = R; st->nstart = m; st->segments = P.segments;
+    st->rules = R; st->nstart = m; st->segments = P.seg.segments;
     if (c.dec_log)
         fprintf(stderr, "repair decode: %u segments, next() evaluated for %llu bit positions (%.4f of the stream's %llu), %llu rules, %u start symbols\n",
-                P.segments, (unsigned long long)P.evaluated, (double)P.evaluated / (double)std::max<u64>(total, 1), (unsigned long long)total,
+                P.seg.segments, (unsigned long long)P.seg.evaluated, (double)P.seg.evaluated / (double)std::max<u64>(total, 1), (unsigned long long)total,
                 (unsigned long long)R, m);
     if (n == 0) { st->dec.device_parse = 1; decode_dest(out, 0); return true; }
     if (nr) {
