@@ -285,6 +285,10 @@ int tdc_gpu_prim_select_counts(tdc_gpu_ctx* ctx, const uint8_t* cls, uint8_t wan
                                uint32_t fillA, uint32_t* outA, uint32_t* count);
 /* mark_orbit_u32: mark[i] = 1 on the chain 0, next[0], next[next[0]], ... and 0 elsewhere; i < next[i] <= n for every i */
 int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, uint8_t* mark);
+/* dx_entries (the tile scheme of the device decoders): exit0[t * states + o] = the state in which the chain that enters tile t in
+ * state o enters tile t + 1, 0xFFFF: it ends in t.  entry0[t] = the state in which the chain that enters tile 0 in state 0 enters
+ * tile t, 0xFFFF behind its end.  Every exit must be < states or 0xFFFF (anything else is refused); at most 2^27 tiles */
+int tdc_gpu_prim_tile_entries(tdc_gpu_ctx* ctx, const uint16_t* exit0, size_t ntiles, uint32_t states, uint16_t* entry0);
 
 /* ---- LCPCompressor::decompress (LCPCompressor.hpp:140-150 -> decode_text_internal :23-76, HuffmanCoder::Decoder
  * coders/HuffmanCoder.hpp:572-612); lzss_lcp(coder=huff) streams have the same format (LZSSLCPCompressor.hpp:125-130).

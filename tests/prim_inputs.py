@@ -13,6 +13,8 @@ ORB_SUPER = 1 << 20
 SMALL_SORT_MAX = 2048        # sort_pairs_u64_distinct: bitonic up to here,
 MID_SORT_MAX = 8192          # one-workgroup radix up to here
 SCATTER_MIN = 1 << 20        # bucketed_scatter_u32 partitions from this many pairs
+DX_G = 512                   # dx_entries (csrc/tile_chain.hpp): tiles per group, groups per group of groups
+DX_NONE = 0xFFFF             # "the chain ends in this tile"
 
 
 def _mask(bits):
@@ -172,6 +174,44 @@ def orbit_reference(nxt):
         e = steps[e]
     mark[on] = 1
     return mark
+
+
+# ---- tile exits of the decoders' tile scheme --------------------------------------------------------------------------------------
+TILE_EXIT_NTILES = (1, DX_G - 1, DX_G, DX_G + 1, DX_G * DX_G - 1, DX_G * DX_G, DX_G * DX_G + 1)     # the group borders of every level
+TILE_EXIT_STATES = (1, 13, 22)                                                                       # sle's fewest, sle's most, rle
+TILE_EXIT_KINDS = ("random", "no_none", "all_none", "ends_in_first_group")
+TILE_EXIT_END = 100          # "ends_in_first_group": the tile whose exits are all NONE
+
+
+def tile_exits(ntiles, states, kind, rng):
+    """(ntiles, states) uint16: exit[t][o] = the state in which the chain that enters tile t in state o enters tile t + 1, DX_NONE: it
+    ends in t.  "random": about 1 NONE in 4096 and none on the chain's way through the first three groups, so that the chain from
+    state 0 crosses several groups and ends in a large table"""
+    if kind == "all_none":
+        return np.full((ntiles, states), DX_NONE, dtype=np.uint16)
+    ex = rng.integers(0, states, size=(ntiles, states), dtype=np.uint16)
+    if kind == "random":
+        ex[rng.random((ntiles, states)) < 1.0 / 4096] = DX_NONE
+        e = 0
+        for t in range(min(ntiles, 3 * DX_G)):
+            if ex[t, e] == DX_NONE:
+                ex[t, e] = rng.integers(0, states)
+            e = int(ex[t, e])
+    elif kind == "ends_in_first_group":
+        ex[min(TILE_EXIT_END, ntiles - 1)] = DX_NONE
+    return ex
+
+
+def tile_entries_reference(exits):
+    """the sequential definition: e = 0; for every tile t: entry[t] = e, then e = exit[t][e] unless e is NONE"""
+    rows = exits.tolist()
+    entry = []
+    e = 0
+    for row in rows:
+        entry.append(e)
+        if e != DX_NONE:
+            e = row[e]
+    return np.array(entry, dtype=np.uint16)
 
 
 # ---- classes of the selection ----------------------------------------------------------------------------------------------------

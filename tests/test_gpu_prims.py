@@ -282,6 +282,23 @@ def test_mark_orbit_vs_serial_walk(gpu_ctx, kind, n):
     assert np.array_equal(gpu_ctx.prim_mark_orbit(nxt), P.orbit_reference(nxt)), (kind, n)
 
 
+# ---- tile entries ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("states", P.TILE_EXIT_STATES)
+@pytest.mark.parametrize("ntiles", P.TILE_EXIT_NTILES)
+def test_tile_entries_vs_sequential_walk(gpu_ctx, ntiles, states):
+    for kind in P.TILE_EXIT_KINDS:
+        ex = P.tile_exits(ntiles, states, kind, np.random.default_rng(ntiles + states))
+        assert np.array_equal(gpu_ctx.prim_tile_entries(ex), P.tile_entries_reference(ex)), (kind, ntiles, states)
+
+
+def test_tile_entries_refuses_exits_outside_the_table(gpu_ctx):
+    u16 = lambda rows: np.array(rows, dtype=np.uint16)
+    _refused(lambda: gpu_ctx.prim_tile_entries(u16([[0, 1], [2, 0]])))                    # an exit == states
+    _refused(lambda: gpu_ctx.prim_tile_entries(u16([[0, 1], [0, 0xFFFE]])))               # ... and one just below NONE
+    _refused(lambda: gpu_ctx.prim_tile_entries(np.zeros((3, 0), dtype=np.uint16)))        # no states
+    assert gpu_ctx.prim_tile_entries(u16([[1, 0], [0xFFFF, 0xFFFF], [0, 0]])).tolist() == [0, 1, 0xFFFF]      # the context survives
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------
 def _refused(call):
     with pytest.raises(T.TdcGpuError) as e:

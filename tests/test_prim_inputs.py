@@ -142,6 +142,41 @@ def test_orbit_reference_is_the_serial_walk():
     assert P.orbit_reference(nxt).tolist() == [1, 0, 1, 0, 0, 1, 1]
 
 
+def test_tile_entries_reference_is_the_sequential_walk():
+    N = P.DX_NONE
+    ex = np.array([[1, 0], [N, 1], [0, 0], [1, N], [0, N], [0, 0]], dtype=np.uint16)
+    assert P.tile_entries_reference(ex).tolist() == [0, 1, 1, 0, 1, N]
+    assert P.tile_entries_reference(np.array([[N]], dtype=np.uint16)).tolist() == [0]      # the first tile is always entered in state 0
+
+
+@pytest.mark.parametrize("states", P.TILE_EXIT_STATES)
+@pytest.mark.parametrize("ntiles", P.TILE_EXIT_NTILES)
+def test_tile_exits(ntiles, states):
+    G = P.DX_G
+    for kind in P.TILE_EXIT_KINDS:
+        ex = P.tile_exits(ntiles, states, kind, np.random.default_rng(ntiles + states))
+        assert ex.dtype == np.uint16 and ex.shape == (ntiles, states)
+        assert ((ex < states) | (ex == P.DX_NONE)).all(), kind                # the precondition of the entry point
+        entry = P.tile_entries_reference(ex)
+        assert len(entry) == ntiles and entry[0] == 0
+        ended = np.flatnonzero(entry == P.DX_NONE)
+        assert (entry[:ended[0] if len(ended) else ntiles] < states).all()
+        assert len(ended) == 0 or (entry[ended[0]:] == P.DX_NONE).all()       # an ended chain stays ended
+        if kind == "no_none":
+            assert len(ended) == 0 and (ex != P.DX_NONE).all()
+            if states > 1 and ntiles >= G:
+                assert len(np.unique(entry)) == states                        # the chain really moves through the states
+        elif kind == "all_none":
+            assert len(ended) == ntiles - 1
+        elif kind == "ends_in_first_group":
+            assert (len(ended) == 0) == (ntiles <= P.TILE_EXIT_END + 1)
+            assert len(ended) == 0 or ended[0] == P.TILE_EXIT_END + 1 < G
+        elif ntiles >= G * G - 1:                                             # random: ends, but only after several groups
+            assert len(ended) > 0 and ended[0] > 3 * G and (ex == P.DX_NONE).sum() > 10
+        else:
+            assert len(ended) == 0
+
+
 @pytest.mark.parametrize("want", [0, 3, 255])
 def test_select_classes(want):
     rng = np.random.default_rng(want)

@@ -740,6 +740,14 @@ class Context:
         self._check(self._L.tdc_gpu_prim_mark_orbit(self._h, _ptr(a), len(a), _ptr(mark)))
         return mark
 
+    def prim_tile_entries(self, exits):
+        """dx_entries on a (ntiles, states) table of u16 exits (0xFFFF: the chain ends in the tile); returns the entries (u16)."""
+        a = np.ascontiguousarray(exits, dtype=np.uint16)
+        ntiles, states = a.shape
+        entry = np.empty(ntiles, dtype=np.uint16)
+        self._check(self._L.tdc_gpu_prim_tile_entries(self._h, _ptr(a), ntiles, states, _ptr(entry)))
+        return entry
+
     def suffix_array(self, text):
         a = _u8(text)
         sa = np.empty(len(a), dtype=np.uint32)

@@ -1,7 +1,8 @@
-// api_prims.hip -- C ABI (include/tdc_gpu.h): the shared device primitives of prim.hpp one by one, for the tests.  Every entry point
+// api_prims.hip -- C ABI (include/tdc_gpu.h): the shared device primitives of prim.hpp and tile_chain.hpp one by one, for the tests.  Every entry point
 // checks the primitive's preconditions ON THE HOST and refuses with TDC_GPU_ERR_ARG before anything is launched: a wrong test input
 // must not become a store outside a buffer.  The product never calls these.
 #include "api.hpp"
+#include "tile_chain.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -215,6 +216,22 @@ int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, ui
         u32* s1 = c.arena.get<u32>(n + 4); u32* s2 = c.arena.get<u32>(n + 4);
         mark_orbit_u32(c, d_next, n, d_mark, s1, s2);
         download(c, mark, d_mark, n);
+        HIP_TRY(hipStreamSynchronize(c.stream));
+    });
+}
+
+int tdc_gpu_prim_tile_entries(tdc_gpu_ctx* ctx, const uint16_t* exit0, size_t ntiles, uint32_t states, uint16_t* entry0) {
+    return guarded(ctx, [&] {
+        if (ntiles && (!exit0 || !entry0)) bad("exit0/entry0 is NULL");
+        if (states == 0 || states >= DX_NONE) bad("1 <= states < 0xFFFF required");
+        if (ntiles > ((size_t)1 << 27)) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "at most 2^27 tiles"};
+        for (size_t i = 0; i < ntiles * states; ++i) if (exit0[i] >= states && exit0[i] != DX_NONE) bad("every exit must be < states or 0xFFFF");
+        if (ntiles == 0) return;
+        Ctx& c = ctx->c;
+        reserve_arena(c, 2 * ntiles * states + dx_entries_scratch((u32)ntiles, states) + ((size_t)64 << 20));
+        const u16* d_exit = upload(c, exit0, ntiles * states);
+        const u16* d_entry = dx_entries(c, d_exit, (u32)ntiles, states, c.arena.alloc(dx_entries_scratch((u32)ntiles, states)));
+        download(c, entry0, d_entry, ntiles);
         HIP_TRY(hipStreamSynchronize(c.stream));
     });
 }

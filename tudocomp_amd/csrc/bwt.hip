@@ -7,8 +7,6 @@
 #include "prim.hpp"
 #include "decode.hpp"
 
-#include <chrono>
-
 namespace tdc {
 namespace {
 
@@ -271,14 +269,7 @@ size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps,
     st->sample = S; st->max_steps = M;
     hipStream_t s = c.stream;
     const bool dlog = c.bwt_log != 0;                       // stage times on stderr (synchronises)
-    auto t_last = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
-        if (!dlog) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "bwt:      %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    const DecTick tick = dec_ticker(c, "bwt", dlog);
 
     Mix mx;
     const u32 mbits = (u32)bits_for(n - 1);                  // 1 .. 31

@@ -5,10 +5,11 @@
 //         Permutations compose associatively, (a o b)[j] = a[b[j]]: reduced over groups of 256 on three levels, brought back down as the
 //         list in front of every chunk, and the output is the gather out[i] = list[chunk of i][index i].
 //   huff: next(x) = x + length of the code at bit x.  A chain can enter a tile of 2048 bit positions only within the first `longest`
-//         offsets: per tile "where does the chain that enters at offset o leave" (computed in LDS), composed over groups of 512 tiles on
-//         three levels, every tile gets its entry, then codes per tile -> 64-bit scan -> one byte per code.  No per-bit array in HBM.
-//   sle:  encode(sle) is a prefix code as well, and the length of a code follows from its first three bits: the tile scheme of huff
-//         without a table in the exit pass; a code stands for 1 or k bytes, so the count pass adds up bytes, not codes.
+//         offsets: the tile scheme of tile_chain.hpp (exits per tile in LDS, entries of every tile), then codes per tile -> 64-bit scan
+//         -> one byte per code.  No per-bit array in HBM.
+//   sle:  encode(sle) is a prefix code as well, and the length of a code follows from its first three bits: the same kernels and driver
+//         as huff under another Code policy, without a table in the exit pass; a code stands for 1 or k bytes, so the count pass adds
+//         up bytes, not codes.
 //   rle:  the parse carries one bit of state ("this data byte equals the previous data byte": a vbyte follows), a token is at most 1 + 10
 //         bytes long: the same tile scheme with the 2 x 11 states (offset, eq).  Run lengths -> 64-bit scan; every token writes its bytes
 //         up to the next 256-byte border of the output itself and leaves (end, byte) at the first border it covers; a maximum scan over
@@ -18,62 +19,13 @@
 #include "bytestages.hpp"
 #include "decode.hpp"
 #include "prim.hpp"
+#include "tile_chain.hpp"
 #include "../host/tdc_coders.hpp"
 
 #include <vector>
 
 namespace tdc {
 namespace {
-
-// ---- tile exits -> tile entries (shared by huff and rle) --------------------------------------------------------------------------------
-// exit[t * S + o] = the state in which the chain that enters tile t in state o enters tile t + 1 (DX_NONE: it ends or breaks in t)
-constexpr u32 DX_G = 512;
-constexpr u16 DX_NONE = 0xFFFFu;
-
-__global__ void __launch_bounds__(256) dx_compose_kernel(const u16* __restrict__ lo, u32 nlo, u32 nhi, u32 S, u16* __restrict__ hi) {
-    const u64 items = (u64)nhi * S;
-    for (u64 w = (u64)blockIdx.x * 256 + threadIdx.x; w < items; w += (u64)gridDim.x * 256) {
-        const u32 g = (u32)(w / S), o = (u32)(w - (u64)g * S);
-        const u32 t1 = min((g + 1) * DX_G, nlo);
-        u32 e = o;
-        for (u32 t = g * DX_G; t < t1 && e != DX_NONE; ++t) e = lo[(size_t)t * S + e];
-        hi[w] = (u16)e;
-    }
-}
-// entries of the items of every group from the group's entry (entry_hi == nullptr: one group, entered in state e0)
-__global__ void __launch_bounds__(256) dx_down_kernel(const u16* __restrict__ exit_lo, const u16* __restrict__ entry_hi, u32 nlo, u32 nhi, u32 S, u32 e0,
-                                                      u16* __restrict__ entry_lo) {
-    for (u32 g = blockIdx.x * 256 + threadIdx.x; g < nhi; g += gridDim.x * 256) {
-        const u32 t1 = entry_hi ? min((g + 1) * DX_G, nlo) : nlo;
-        u32 e = entry_hi ? entry_hi[g] : e0;
-        for (u32 t = entry_hi ? g * DX_G : 0; t < t1; ++t) {
-            entry_lo[t] = (u16)e;
-            if (e != DX_NONE) e = exit_lo[(size_t)t * S + e];
-        }
-    }
-}
-// N0 tiles of S states: at most 2^24 tiles -> 2^15 groups -> 64 groups of groups, walked by one thread
-u16* dx_entries(Ctx& c, const u16* exit0, u32 N0, u32 S) {
-    hipStream_t s = c.stream;
-    const u32 N1 = cdiv(N0, DX_G), N2 = cdiv(N1, DX_G);
-    if (N2 > DX_G) throw HipError{hipErrorUnknown, "tile entries: more than 2^27 tiles", (int)__LINE__};
-    u16* exit1 = (u16*)c.arena.alloc_top((size_t)N1 * S * 2);
-    u16* exit2 = (u16*)c.arena.alloc_top((size_t)N2 * S * 2);
-    u16* entry2 = (u16*)c.arena.alloc_top((size_t)N2 * 2);
-    u16* entry1 = (u16*)c.arena.alloc_top((size_t)N1 * 2);
-    u16* entry0 = (u16*)c.arena.alloc_top((size_t)N0 * 2);
-    dx_compose_kernel<<<dec_grid((size_t)N1 * S), 256, 0, s>>>(exit0, N0, N1, S, exit1);
-    LAUNCH_CHECK();
-    dx_compose_kernel<<<dec_grid((size_t)N2 * S), 256, 0, s>>>(exit1, N1, N2, S, exit2);
-    LAUNCH_CHECK();
-    dx_down_kernel<<<1, 256, 0, s>>>(exit2, nullptr, N2, 1, S, 0, entry2);
-    LAUNCH_CHECK();
-    dx_down_kernel<<<dec_grid(N2), 256, 0, s>>>(exit1, entry2, N1, N2, S, 0, entry1);
-    LAUNCH_CHECK();
-    dx_down_kernel<<<dec_grid(N1), 256, 0, s>>>(exit0, entry1, N0, N1, S, 0, entry0);
-    LAUNCH_CHECK();
-    return entry0;
-}
 
 // the output of a stage, from the bottom of the arena
 u8* stage_out(Ctx& c, u64 len) {
@@ -202,17 +154,44 @@ __device__ __forceinline__ u32 hd_code(const HuffDecTab* T, const Win& bw, u64 x
     sym = T->order[T->prefix[length] + off];
     return length + 1;
 }
-__device__ __forceinline__ void hd_tab_to_lds(const HuffDecTab* __restrict__ g, HuffDecTab* l) {
-    for (u32 k = threadIdx.x; k < sizeof(HuffDecTab) / 4; k += blockDim.x) ((u32*)l)[k] = ((const u32*)g)[k];
-}
+
+// ---- prefix-code streams: encode(huff) and encode(sle) ----------------------------------------------------------------------------------
+// What a code is, is the coder's business.  A coder hands the two kernels a Code, a small POD passed by value (as Tok in
+// stream_parse.hpp):
+//   Tab, g                                the table of the walk as the host builds it, and its copy on the device
+//   exit_tab() / walk_tab()               what the pass keeps in LDS beside the stream image: staged here, complete behind the next barrier
+//   len(T, bw, x)                         the length of the code at bit x < total; 0: none, the chain ends there
+//   put<EMIT>(T, bw, x, dst, m)           the code at x: its length, 0: an error of the stream.  m = the bytes it stands for, written
+//                                         to dst[0 .. m) if EMIT
+struct HuffCode {
+    typedef HuffDecTab Tab;
+    const HuffDecTab* g;
+    __device__ __forceinline__ const HuffDecTab* exit_tab() const {
+        __shared__ HuffDecTab T;
+        for (u32 k = threadIdx.x; k < sizeof(HuffDecTab) / 4; k += blockDim.x) ((u32*)&T)[k] = ((const u32*)g)[k];
+        return &T;
+    }
+    __device__ __forceinline__ const HuffDecTab* walk_tab() const { return exit_tab(); }
+    template <typename Win>
+    __device__ __forceinline__ u32 len(const HuffDecTab* T, const Win& bw, u64 x) const { u32 sym; return hd_code(T, bw, x, sym); }
+    template <bool EMIT, typename Win>
+    __device__ __forceinline__ u32 put(const HuffDecTab* T, const Win& bw, u64 x, u8* dst, u32& m) const {   // a code outside the table is the error
+        u32 sym;
+        const u32 d = hd_code(T, bw, x, sym);
+        m = 1;
+        if (!d) return 0u;
+        if (EMIT) *dst = (u8)sym;
+        return d;
+    }
+};
 
 // s32: the stream's words (nw32 of them readable), hb: first bit of the body, total: bits in front of the terminator
-__global__ void __launch_bounds__(256) hd_exit_kernel(const u32* __restrict__ s32, u64 nw32, u64 hb, u64 total, const HuffDecTab* __restrict__ gT, u32 LA,
-                                                      u32 nchunks, u32 ntiles, u16* __restrict__ exit0) {
-    __shared__ HuffDecTab T;
+template <class Code>
+__global__ void __launch_bounds__(256) code_exit_kernel(const Code code, const u32* __restrict__ s32, u64 nw32, u64 hb, u64 total, u32 LA, u32 nchunks,
+                                                        u32 ntiles, u16* __restrict__ exit0) {
     __shared__ u32 sw[HD_CH / 32 + 16];
     __shared__ u8 nxl[HD_CH];                                  // next(x) - x; 0: no code starts at x
-    hd_tab_to_lds(gT, &T);
+    const auto T = code.exit_tab();
     for (u32 chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         __syncthreads();
         const u64 a0 = hb + (u64)chunk * HD_CH;
@@ -220,38 +199,18 @@ __global__ void __launch_bounds__(256) hd_exit_kernel(const u32* __restrict__ s3
         for (u32 k = threadIdx.x; k < HD_CH / 32 + 16; k += 256) sw[k] = kb + k < nw32 ? __builtin_bswap32(s32[kb + k]) : 0u;
         __syncthreads();
         const BitWin bw{sw, kb, total};
-        for (u32 i = threadIdx.x; i < HD_CH; i += 256) {
-            u32 d = 0, sym;
-            if (a0 + i < total) d = hd_code(&T, bw, a0 + i, sym);
-            nxl[i] = (u8)d;
-        }
+        for (u32 i = threadIdx.x; i < HD_CH; i += 256) nxl[i] = (u8)(a0 + i < total ? code.len(T, bw, a0 + i) : 0u);
         __syncthreads();
-        constexpr u32 TPW = HD_CH / HD_T;
-        for (u32 w = threadIdx.x; w < TPW * LA; w += 256) {
-            const u32 tt = w / LA, o = w - tt * LA;
-            const u32 tile = chunk * TPW + tt;
-            if (tile >= ntiles) continue;
-            const u32 tend = (tt + 1) * HD_T;
-            u32 e = tt * HD_T + o, res = DX_NONE;
-            for (u32 guard = 0; guard <= HD_T; ++guard) {
-                if (e >= tend) { res = e - tend; break; }
-                const u32 d = nxl[e];
-                if (!d) break;
-                e += d;
-            }
-            exit0[(size_t)tile * LA + o] = (u16)res;
-        }
+        tile_exits<HD_T, HD_CH / HD_T>(nxl, LA, chunk * (HD_CH / HD_T), ntiles, exit0);
     }
 }
 
-// the codes of every tile from its entry: EMIT = false counts them (tcount[t]; *err |= 1 for a code outside the table), EMIT = true:
-// tcount[] holds the exclusive sums, one byte per code
-template <bool EMIT>
-__global__ void __launch_bounds__(256) hd_walk_kernel(const u32* __restrict__ s32, u64 hb, u64 total, const HuffDecTab* __restrict__ gT,
-                                                      const u16* __restrict__ tile_entry, u32 ntiles, u64* __restrict__ tcount, u8* __restrict__ out,
-                                                      u32* __restrict__ err) {
-    __shared__ HuffDecTab T;
-    hd_tab_to_lds(gT, &T);
+// the codes of every tile from its entry: EMIT = false adds up the bytes they stand for (tcount[t]; *err |= 1 for a code that
+// Code::put refuses), EMIT = true: tcount[] holds the exclusive sums, the bytes go to out
+template <class Code, bool EMIT>
+__global__ void __launch_bounds__(256) code_walk_kernel(const Code code, const u32* __restrict__ s32, u64 hb, u64 total, const u16* __restrict__ tile_entry,
+                                                        u32 ntiles, u64* __restrict__ tcount, u8* __restrict__ out, u32* __restrict__ err) {
+    const auto T = code.walk_tab();
     __syncthreads();
     const BitWinG bw{s32, total};
     for (u32 t = blockIdx.x * 256 + threadIdx.x; t < ntiles; t += gridDim.x * 256) {
@@ -262,11 +221,10 @@ __global__ void __launch_bounds__(256) hd_walk_kernel(const u32* __restrict__ s3
             const u64 tile_end = min(hb + (u64)(t + 1) * HD_T, total);
             u8* dst = EMIT ? out + tcount[t] : nullptr;
             for (u32 guard = 0; x < tile_end && guard <= HD_T; ++guard) {
-                u32 sym;
-                const u32 d = hd_code(&T, bw, x, sym);
+                u32 m;
+                const u32 d = code.template put<EMIT>(T, bw, x, EMIT ? dst + cnt : nullptr, m);
                 if (!d) { if (!EMIT) atomicOr(err, 1u); break; }
-                if (EMIT) dst[cnt] = (u8)sym;
-                ++cnt;
+                cnt += m;
                 x += d;
             }
         }
@@ -345,85 +303,38 @@ int hd_parse_header(const u8* pre, size_t pre_len, bool whole, u64 total, HuffDe
 
 // ---- encode(sle) ------------------------------------------------------------------------------------------------------------------------
 // A pure prefix-code stream behind the ranking: the length of a code follows from its first three bits and sigma_bits
-// (tdc_amd::sle_code_len), so next(x) needs no table; a rank stands for 1 or k bytes.  The tile scheme of encode(huff) with the same
+// (tdc_amd::sle_code_len), so next(x) needs no table; a rank stands for 1 or k bytes.  The kernels of encode(huff) with the same
 // tile and chunk sizes; the states are the first LA = longest code (at most 13) offsets of a tile.
-struct SleDecTab {
-    u64 ent[tdc_amd::SLE_MAX_SIGMA];                         // rank -> its bytes (first byte most significant) | their number << 56
-    u32 sigma, sb, pad0, pad1;
-};
+struct SleDecTab { u64 ent[tdc_amd::SLE_MAX_SIGMA]; };      // rank -> its bytes (first byte most significant) | their number << 56
 static_assert(sizeof(SleDecTab) % 4 == 0, "copied word by word");
 
-__global__ void __launch_bounds__(256) sd_exit_kernel(const u32* __restrict__ s32, u64 nw32, u64 hb, u64 total, u32 sb, u32 LA, u32 nchunks, u32 ntiles,
-                                                      u16* __restrict__ exit0) {
-    __shared__ u32 sw[HD_CH / 32 + 16];
-    __shared__ u8 nxl[HD_CH];                                  // next(x) - x; 0: the code at x is cut off by the end of the stream
-    for (u32 chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        __syncthreads();
-        const u64 a0 = hb + (u64)chunk * HD_CH;
-        const u64 kb = a0 >> 5;
-        for (u32 k = threadIdx.x; k < HD_CH / 32 + 16; k += 256) sw[k] = kb + k < nw32 ? __builtin_bswap32(s32[kb + k]) : 0u;
-        __syncthreads();
-        const BitWin bw{sw, kb, total};
-        for (u32 i = threadIdx.x; i < HD_CH; i += 256) {
-            u32 d = 0;
-            if (a0 + i < total) {
-                d = tdc_amd::sle_code_len(sb, (u32)(bw.peek(a0 + i) >> 61));
-                if (a0 + i + d > total) d = 0;
-            }
-            nxl[i] = (u8)d;
-        }
-        __syncthreads();
-        constexpr u32 TPW = HD_CH / HD_T;
-        for (u32 w = threadIdx.x; w < TPW * LA; w += 256) {
-            const u32 tt = w / LA, o = w - tt * LA;
-            const u32 tile = chunk * TPW + tt;
-            if (tile >= ntiles) continue;
-            const u32 tend = (tt + 1) * HD_T;
-            u32 e = tt * HD_T + o, res = DX_NONE;
-            for (u32 guard = 0; guard <= HD_T; ++guard) {
-                if (e >= tend) { res = e - tend; break; }
-                const u32 d = nxl[e];
-                if (!d) break;
-                e += d;
-            }
-            exit0[(size_t)tile * LA + o] = (u16)res;
-        }
+struct SleCode {
+    typedef SleDecTab Tab;
+    const SleDecTab* g;
+    u32 sb, sigma;
+    __device__ __forceinline__ int exit_tab() const { return 0; }                              // (sb is all the exit pass needs)
+    __device__ __forceinline__ const u64* walk_tab() const {
+        __shared__ SleDecTab T;
+        for (u32 k = threadIdx.x; k < sizeof(SleDecTab) / 4; k += blockDim.x) ((u32*)&T)[k] = ((const u32*)g)[k];
+        return T.ent;
     }
-}
-
-// the codes of every tile from its entry: EMIT = false adds up the bytes they stand for (tcount[t]; *err |= 1 for a code that is cut off
-// or whose rank lies outside the ranking), EMIT = true: tcount[] holds the exclusive sums, 1 or k bytes per code
-template <bool EMIT>
-__global__ void __launch_bounds__(256) sd_walk_kernel(const u32* __restrict__ s32, u64 hb, u64 total, const SleDecTab* __restrict__ gT,
-                                                      const u16* __restrict__ tile_entry, u32 ntiles, u64* __restrict__ tcount, u8* __restrict__ out,
-                                                      u32* __restrict__ err) {
-    __shared__ SleDecTab T;
-    for (u32 k = threadIdx.x; k < sizeof(SleDecTab) / 4; k += blockDim.x) ((u32*)&T)[k] = ((const u32*)gT)[k];
-    __syncthreads();
-    const BitWinG bw{s32, total};
-    const u32 sb = T.sb, sigma = T.sigma;
-    for (u32 t = blockIdx.x * 256 + threadIdx.x; t < ntiles; t += gridDim.x * 256) {
-        const u32 e = tile_entry[t];
-        u64 cnt = 0;
-        if (e != DX_NONE) {
-            u64 x = hb + (u64)t * HD_T + e;
-            const u64 tile_end = min(hb + (u64)(t + 1) * HD_T, total);
-            u8* dst = EMIT ? out + tcount[t] : nullptr;
-            for (u32 guard = 0; x < tile_end && guard <= HD_T; ++guard) {
-                const u64 w = bw.peek(x);
-                const u32 d = tdc_amd::sle_code_len(sb, (u32)(w >> 61));
-                const u32 rank = tdc_amd::sle_code_rank(sb, d, (u32)(w >> (64 - d)));
-                if (x + d > total || rank >= sigma) { if (!EMIT) atomicOr(err, 1u); break; }
-                const u64 ent = T.ent[rank];
-                const u32 m = (u32)(ent >> 56);
-                if (EMIT) for (u32 j = 0; j < m; ++j) dst[cnt + j] = (u8)(ent >> (8 * (m - 1 - j)));
-                cnt += m;
-                x += d;
-            }
-        }
-        if (!EMIT) tcount[t] = cnt;
+    template <typename Win>
+    __device__ __forceinline__ u32 len(int, const Win& bw, u64 x) const {                      // 0: cut off by the end of the stream
+        const u32 d = tdc_amd::sle_code_len(sb, (u32)(bw.peek(x) >> 61));
+        return x + d > bw.total ? 0u : d;
     }
-}
+    template <bool EMIT, typename Win>
+    __device__ __forceinline__ u32 put(const u64* T, const Win& bw, u64 x, u8* dst, u32& m) const {   // cut off, or a rank outside the ranking: the error
+        const u64 w = bw.peek(x);
+        const u32 d = tdc_amd::sle_code_len(sb, (u32)(w >> 61));                               // >= 1
+        const u32 rank = tdc_amd::sle_code_rank(sb, d, (u32)(w >> (64 - d)));
+        if (x + d > bw.total || rank >= sigma) return 0u;
+        const u64 ent = T[rank];
+        m = (u32)(ent >> 56);
+        if (EMIT) for (u32 j = 0; j < m; ++j) dst[j] = (u8)(ent >> (8 * (m - 1 - j)));
+        return d;
+    }
+};
 
 // ---- rle --------------------------------------------------------------------------------------------------------------------------------
 constexpr u32 RLD_T = 512;                  // input bytes per tile
@@ -587,6 +498,39 @@ StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n) {
     return r;
 }
 
+// The body of a prefix-code stream behind its parsed header: bits [hb, total) of the n bytes at s32, no code longer than LA; `tab`
+// (alive until this returns) goes up and becomes code.g.
+template <class Code>
+StageOut code_decode_device(Ctx& c, Code code, const typename Code::Tab& tab, const u32* s32, size_t n, u64 hb, u64 total, u32 LA) {
+    typedef typename Code::Tab Tab;
+    hipStream_t s = c.stream;
+    StageOut r;
+    const u64 m = total - hb;
+    if (m == 0) { r.d = stage_out(c, 0); return r; }
+    const u32 ntiles = cdiv(m, HD_T), nchunks = cdiv(m, HD_CH);
+    Tab* d_tab = (Tab*)c.arena.alloc_top(sizeof(Tab));
+    u32* d_err = (u32*)c.arena.alloc_top(256);
+    u64* tcount = (u64*)c.arena.alloc_top(((size_t)ntiles + 1) * 8);
+    u16* exit0 = (u16*)c.arena.alloc_top((size_t)ntiles * LA * 2);
+    HIP_TRY(hipMemcpyAsync(d_tab, &tab, sizeof(Tab), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
+    code.g = d_tab;
+    code_exit_kernel<Code><<<std::min<u32>(nchunks, DEC_MAX_BLOCKS), 256, 0, s>>>(code, s32, ((u64)n + 60) / 4, hb, total, LA, nchunks, ntiles, exit0);
+    LAUNCH_CHECK();
+    const u16* entry = dx_entries(c, exit0, ntiles, LA, c.arena.alloc_top(dx_entries_scratch(ntiles, LA)));
+    code_walk_kernel<Code, false><<<dec_grid(ntiles), 256, 0, s>>>(code, s32, hb, total, entry, ntiles, tcount, nullptr, d_err);
+    LAUNCH_CHECK();
+    exclusive_sum_u64(c, tcount, tcount, ntiles, tcount + ntiles);
+    const u32 err = c.read(d_err);                              // (synchronises: the table lives on the caller's frame)
+    r.len = c.read(tcount + ntiles);
+    if (err) throw StreamFormatError{"pipeline: malformed stream"};
+    if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
+    r.d = stage_out(c, r.len);
+    code_walk_kernel<Code, true><<<dec_grid(ntiles), 256, 0, s>>>(code, s32, hb, total, entry, ntiles, tcount, r.d, d_err);
+    LAUNCH_CHECK();
+    return r;
+}
+
 StageOut huff_decode_device(Ctx& c, const u8* d_in, size_t n) {
     const StreamFormatError bad{"pipeline: malformed stream"};
     if (!n) throw bad;
@@ -607,38 +551,15 @@ StageOut huff_decode_device(Ctx& c, const u8* d_in, size_t n) {
     if (kind < 0) throw StageHostOnly{};
     if (kind == 0) throw bad;
     const u32* s32 = (const u32*)d_in;                          // (arena allocations are 256-byte aligned, 64 bytes of slack behind n)
-    StageOut r;
     if (kind == 1) {
+        StageOut r;
         r.len = (total - 1 + 7) / 8;
         if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
         r.d = stage_out(c, r.len);
         if (r.len) { hd_raw_kernel<<<dec_grid(r.len), 256, 0, s>>>(s32, total, r.len, r.d); LAUNCH_CHECK(); }
         return r;
     }
-    const u64 m = total - hb;
-    if (m == 0) { r.d = stage_out(c, 0); return r; }
-    const u32 LA = tab[0].longest;
-    const u32 ntiles = cdiv(m, HD_T), nchunks = cdiv(m, HD_CH);
-    HuffDecTab* d_tab = (HuffDecTab*)c.arena.alloc_top(sizeof(HuffDecTab));
-    u32* d_err = (u32*)c.arena.alloc_top(256);
-    u64* tcount = (u64*)c.arena.alloc_top(((size_t)ntiles + 1) * 8);
-    u16* exit0 = (u16*)c.arena.alloc_top((size_t)ntiles * LA * 2);
-    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(HuffDecTab), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
-    hd_exit_kernel<<<std::min<u32>(nchunks, DEC_MAX_BLOCKS), 256, 0, s>>>(s32, ((u64)n + 60) / 4, hb, total, d_tab, LA, nchunks, ntiles, exit0);
-    LAUNCH_CHECK();
-    const u16* entry = dx_entries(c, exit0, ntiles, LA);
-    hd_walk_kernel<false><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, nullptr, d_err);
-    LAUNCH_CHECK();
-    exclusive_sum_u64(c, tcount, tcount, ntiles, tcount + ntiles);
-    const u32 err = c.read(d_err);                              // (synchronises: the table lives on this frame)
-    r.len = c.read(tcount + ntiles);
-    if (err) throw bad;
-    if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
-    r.d = stage_out(c, r.len);
-    hd_walk_kernel<true><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, r.d, d_err);
-    LAUNCH_CHECK();
-    return r;
+    return code_decode_device(c, HuffCode{nullptr}, tab[0], s32, n, hb, total, tab[0].longest);
 }
 
 StageOut sle_decode_device(Ctx& c, const u8* d_in, size_t n, u32 kmer) {
@@ -656,37 +577,11 @@ StageOut sle_decode_device(Ctx& c, const u8* d_in, size_t n, u32 kmer) {
     tdc_amd::SleRanking R;
     try { tdc_amd::sle_parse_ranking(pre.data(), pre.size(), tdc_amd::sle_total_bits(n, last), kmer, R); }
     catch (const std::runtime_error&) { throw bad; }
-    const u64 total = R.total, hb = R.body;
-    const u32* s32 = (const u32*)d_in;                          // (arena allocations are 256-byte aligned, 64 bytes of slack behind n)
-    StageOut r;
-    const u64 m = total - hb;
-    if (m == 0) { r.d = stage_out(c, 0); return r; }
     std::vector<SleDecTab> tab(1);
     memset(&tab[0], 0, sizeof(SleDecTab));
     for (u32 i = 0; i < R.sigma; ++i) tab[0].ent[i] = R.ent[i];
-    tab[0].sigma = R.sigma; tab[0].sb = R.sb;
-    const u32 LA = tdc_amd::sle_code_len(R.sb, 7);              // the longest code
-    const u32 ntiles = cdiv(m, HD_T), nchunks = cdiv(m, HD_CH);
-    SleDecTab* d_tab = (SleDecTab*)c.arena.alloc_top(sizeof(SleDecTab));
-    u32* d_err = (u32*)c.arena.alloc_top(256);
-    u64* tcount = (u64*)c.arena.alloc_top(((size_t)ntiles + 1) * 8);
-    u16* exit0 = (u16*)c.arena.alloc_top((size_t)ntiles * LA * 2);
-    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(SleDecTab), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
-    sd_exit_kernel<<<std::min<u32>(nchunks, DEC_MAX_BLOCKS), 256, 0, s>>>(s32, ((u64)n + 60) / 4, hb, total, R.sb, LA, nchunks, ntiles, exit0);
-    LAUNCH_CHECK();
-    const u16* entry = dx_entries(c, exit0, ntiles, LA);
-    sd_walk_kernel<false><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, nullptr, d_err);
-    LAUNCH_CHECK();
-    exclusive_sum_u64(c, tcount, tcount, ntiles, tcount + ntiles);
-    const u32 err = c.read(d_err);                              // (synchronises: the table lives on this frame)
-    r.len = c.read(tcount + ntiles);
-    if (err) throw bad;
-    if (r.len > STAGE_MAX_BYTES) throw StageTooLarge{r.len};
-    r.d = stage_out(c, r.len);
-    sd_walk_kernel<true><<<dec_grid(ntiles), 256, 0, s>>>(s32, hb, total, d_tab, entry, ntiles, tcount, r.d, d_err);
-    LAUNCH_CHECK();
-    return r;
+    // (arena allocations are 256-byte aligned, 64 bytes of slack behind n); LA: the longest code
+    return code_decode_device(c, SleCode{nullptr, R.sb, R.sigma}, tab[0], (const u32*)d_in, n, R.body, R.total, tdc_amd::sle_code_len(R.sb, 7));
 }
 
 StageOut rle_decode_device(Ctx& c, const u8* d_in, size_t n, u64 offset) {
@@ -700,7 +595,7 @@ StageOut rle_decode_device(Ctx& c, const u8* d_in, size_t n, u64 offset) {
     HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
     rld_exit_kernel<<<std::min<u32>(nblocks, DEC_MAX_BLOCKS), 256, 0, s>>>(d_in, n, offset, ntiles, nblocks, exit0);
     LAUNCH_CHECK();
-    const u16* entry = dx_entries(c, exit0, ntiles, RLD_S);
+    const u16* entry = dx_entries(c, exit0, ntiles, RLD_S, c.arena.alloc_top(dx_entries_scratch(ntiles, RLD_S)));
     rld_walk_kernel<false><<<std::min<u32>(nblocks, DEC_MAX_BLOCKS), RLD_WT, 0, s>>>(d_in, n, offset, entry, ntiles, nblocks, tsum, nullptr, nullptr, nullptr, d_err);
     LAUNCH_CHECK();
     exclusive_sum_u64(c, tsum, tsum, ntiles, tsum + ntiles);

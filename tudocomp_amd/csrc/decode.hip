@@ -15,6 +15,7 @@
 #include "stages.hpp"
 #include "prim.hpp"
 #include "decode.hpp"
+#include "tile_chain.hpp"
 
 #include <chrono>
 #include <memory>
@@ -429,20 +430,18 @@ __global__ __launch_bounds__(256) void dec_emit_kernel(const u32* __restrict__ s
 // Lean marking for streams whose longest possible token is short (la <= DL_LA_MAX bits: literal runs of a few codes -- every
 // well-compressible text).  A token chain can only enter a tile of DL_T bit positions within the first la positions behind the
 // tile's start, so next() never leaves the workgroup that computes it: per tile only "where does the chain that enters at offset
-// o leave" is written (la 16-bit words instead of 2048 x (next, exit1, exit2, mark) = 13 bytes per bit position), a second level
-// composes DL_G tiles, one thread walks the groups, and the tokens are then decoded tile by tile from their entries -- counted,
-// scanned per tile, and emitted (literals and factor list) by a second walk.  Same results as the general path below
-// (dec_next_kernel + mark_orbit_u32 + token list + count / emit per token), which keeps the streams with longer tokens.
+// o leave" is written (la 16-bit words instead of 2048 x (next, exit1, exit2, mark) = 13 bytes per bit position), the tile entries
+// follow from the exits (tile_chain.hpp, shared with the byte stages), and the tokens are then decoded tile by tile from their
+// entries -- counted, scanned per tile, and emitted (literals and factor list) by a second walk.  Same results as the general path
+// below (dec_next_kernel + mark_orbit_u32 + token list + count / emit per token), which keeps the streams with longer tokens.
 // ------------------------------------------------------------------------------------------------------------
 constexpr u32 DL_T = 2048;                  // bit positions per tile
-constexpr u32 DL_G = 512;                   // tiles per group (2^20 bit positions)
 constexpr u32 DL_CH = 16384;                // bit positions per workgroup of the exit pass
 constexpr u32 DL_LA_MAX = 1024;             // longest token (bits) the lean path takes
-constexpr u16 DL_NONE = 0xFFFFu;
 
 template <typename Tab>
 __global__ __launch_bounds__(256) void dec_lean_exit_kernel(const u32* __restrict__ s32, u64 x_in, u32 m, ParseParams P, const Tab* __restrict__ gT,
-                                                             u32 nwords, u32 LA, u16* __restrict__ exit1) {
+                                                             u32 nwords, u32 LA, u32 ntiles, u16* __restrict__ exit0) {
     extern __shared__ __attribute__((aligned(16))) u32 dyn[];
     Tab* T = (Tab*)dyn;
     u32* sw = dyn + sizeof(Tab) / 4;
@@ -468,49 +467,7 @@ __global__ __launch_bounds__(256) void dec_lean_exit_kernel(const u32* __restric
         nxl[i] = (u16)d;
     }
     __syncthreads();
-    constexpr u32 TPW = DL_CH / DL_T;
-    for (u32 w = threadIdx.x; w < TPW * LA; w += 256) {
-        const u32 tt = w / LA, o = w - tt * LA;
-        const u32 tile = blockIdx.x * TPW + tt;
-        if ((u64)tile * DL_T >= m) continue;
-        const u32 tend = (tt + 1) * DL_T;
-        u32 e = tt * DL_T + o, res = DL_NONE;
-        for (u32 guard = 0; guard <= DL_T; ++guard) {
-            if (e >= tend) { res = e - tend; break; }
-            const u32 d = nxl[e];
-            if (!d) break;
-            e += d;
-        }
-        exit1[(size_t)tile * LA + o] = (u16)res;
-    }
-}
-__global__ void dec_lean_exit2_kernel(const u16* __restrict__ exit1, u32 ntiles, u32 ngroups, u32 LA, u16* __restrict__ exit2) {
-    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= ngroups * LA) return;
-    const u32 g = w / LA, o = w - g * LA;
-    const u32 t1 = min((g + 1) * DL_G, ntiles);
-    u32 e = o;
-    for (u32 t = g * DL_G; t < t1 && e != DL_NONE; ++t) e = exit1[(size_t)t * LA + e];
-    exit2[w] = (u16)e;
-}
-__global__ void dec_lean_groups_kernel(const u16* __restrict__ exit2, u32 ngroups, u32 LA, u16* __restrict__ group_entry) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    u32 e = 0;                                                  // the segment's first token starts at its first bit position
-    for (u32 g = 0; g < ngroups; ++g) {
-        group_entry[g] = (u16)e;
-        if (e != DL_NONE) e = exit2[(size_t)g * LA + e];
-    }
-}
-__global__ void dec_lean_tiles_kernel(const u16* __restrict__ exit1, const u16* __restrict__ group_entry, u32 ntiles, u32 ngroups, u32 LA,
-                                      u16* __restrict__ tile_entry) {
-    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ngroups) return;
-    const u32 t1 = min((g + 1) * DL_G, ntiles);
-    u32 e = group_entry[g];
-    for (u32 t = g * DL_G; t < t1; ++t) {
-        tile_entry[t] = (u16)e;
-        if (e != DL_NONE) e = exit1[(size_t)t * LA + e];
-    }
+    tile_exits<DL_T, DL_CH / DL_T>(nxl, LA, blockIdx.x * (DL_CH / DL_T), ntiles, exit0);
 }
 // the tokens of every tile, walked from the tile's entry: EMIT = false counts them (tokens, text positions they produce), EMIT = true
 // writes the literal bytes and the factor list (tok0 / out0: what the earlier segments hold; tbase_*: exclusive sums over the tiles)
@@ -529,7 +486,7 @@ __global__ __launch_bounds__(256) void dec_lean_walk_kernel(const u32* __restric
         const u32 e = tile_entry[t];
         u32 cnt = 0;
         u64 out = 0;
-        if (e != DL_NONE) {
+        if (e != DX_NONE) {
             u64 x = x_in + (u64)t * DL_T + e;
             const u64 tile_end = min(x_in + (u64)(t + 1) * DL_T, seg_end);
             u64 j = EMIT ? tok0 + tcount[t] : 0;
@@ -822,14 +779,7 @@ void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d
                                  u32* d_changed, Sink& out, DecodeStats* st) {
     hipStream_t s = c.stream;
     const bool dlog = c.dec_log != 0;
-    auto t_last = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
-        if (!dlog) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "decode:   %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    const DecTick tick = dec_ticker(c, "decode");
     fill_u32(c, d_ref, n, NONE32);
     const int G = (z * 64 > n) ? 8 : 64;
     ref_scatter_kernel<<<dec_grid(z * G), 256, 0, s>>>(d_pos, d_src, d_len, z, G, d_ref);
@@ -895,8 +845,9 @@ void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, 
     HIP_TRY(hipStreamSynchronize(c.stream));
 }
 
-DecTick dec_ticker(Ctx& c, const char* who) {
-    if (!c.dec_log) return [](const char*) {};
+DecTick dec_ticker(Ctx& c, const char* who) { return dec_ticker(c, who, c.dec_log != 0); }
+DecTick dec_ticker(Ctx& c, const char* who, bool on) {
+    if (!on) return [](const char*) {};
     auto t_last = std::make_shared<std::chrono::steady_clock::time_point>(std::chrono::steady_clock::now());
     hipStream_t s = c.stream;
     return [=](const char* what) {                                                       // stage times on stderr (synchronises)
@@ -1016,18 +967,11 @@ static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssF
     const u64 seg_bits = c.dec_seg ? (u64)c.dec_seg : (u64)DEC_SEG;                    // (tests shrink the segments)
     const size_t seg = (size_t)std::min<u64>(seg_bits, total - x0 + 1);
     hipStream_t s = c.stream;
-    const bool dlog = c.dec_log != 0;                                                    // stage times on stderr (synchronises)
-    auto t_last = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
-        if (!dlog) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "decode: %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    const DecTick tick = dec_ticker(c, "decode");
     if (out.into && n > out.cap) throw HipError{hipErrorOutOfMemory, "decode: the caller's buffer is too small for the text", (int)__LINE__};   // (known from the header: before any device work)
     // (the device parse needs ~17 bytes of arena per stream bit of a segment on top of 5 n + 28 zmax; the host parse needs 5 n + 12 z: if
-    //  the device cannot provide the former, the host parse takes the stream instead of the call failing)
+    //  the device cannot provide the former, the host parse takes the stream instead of the call failing.  Of the 17, the general path
+    //  takes 13; the lean path one for its tile exits, LA <= 1024 states per 2048 bits, and under 1/500 of that for dx_entries' levels)
     try { c.ensure_arena(len + 64 + n * 5 + n / 8 + zmax * 28 + seg * 17 + sizeof(Tab) + ((size_t)16 << 20)); }
     catch (const HipError& e) { if (e.e != hipErrorOutOfMemory) throw; (void)hipGetLastError(); return false; }
     const size_t mark0 = c.arena.mark();
@@ -1064,7 +1008,7 @@ static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssF
     HIP_TRY(hipStreamSynchronize(s));
     const ParseParams P{ total, H.n, H.flen_min, H.W, H.lbits, H.dbits, (u32)H.fdist_max };
     if (la_bits <= DL_LA_MAX && c.dec_lean) {
-        // ---- lean marking (short tokens): per segment exits per tile entry -> groups -> tile entries -> count walk -> scans -> emit walk
+        // ---- lean marking (short tokens): per segment exits per tile entry -> tile entries -> count walk -> scans -> emit walk
         const u32 LA = (u32)la_bits;
         u32* d_pos = c.arena.get<u32>(zmax), *d_src = c.arena.get<u32>(zmax), *d_len = c.arena.get<u32>(zmax);
         DecScalars* d_sc = (DecScalars*)c.arena.alloc(sizeof(DecScalars));
@@ -1080,24 +1024,17 @@ static bool decode_lzss_device(Ctx& c, const u8* stream, size_t len, const LzssF
         u32 last_status = 0;
         while (x_in < total) {
             const u32 m = (u32)std::min<u64>(seg_bits, total - x_in);
-            const u32 ntiles = cdiv(m, DL_T), ngroups = cdiv(ntiles, DL_G);
+            const u32 ntiles = cdiv(m, DL_T);
             const size_t mk = c.arena.mark();
-            u16* exit1 = c.arena.get<u16>((size_t)ntiles * LA);
-            u16* exit2 = c.arena.get<u16>((size_t)ngroups * LA);
-            u16* gentry = c.arena.get<u16>(ngroups);
-            u16* tentry = c.arena.get<u16>(ntiles);
+            u16* exit0 = c.arena.get<u16>((size_t)ntiles * LA);
+            void* levels = c.arena.alloc(dx_entries_scratch(ntiles, LA));
             u32* tcount = c.arena.get<u32>(ntiles), *tout = c.arena.get<u32>(ntiles);
             up.need((size_t)((x_in + m + la_bits) / 8 + 64), len, s);
             tick("upload + tables");
-            dec_lean_exit_kernel<Tab><<<cdiv(m, DL_CH), 256, lds_l, s>>>(s32, x_in, m, P, d_tab, nw_l, LA, exit1);
+            dec_lean_exit_kernel<Tab><<<cdiv(m, DL_CH), 256, lds_l, s>>>(s32, x_in, m, P, d_tab, nw_l, LA, ntiles, exit0);
             LAUNCH_CHECK();
             tick("next() + tile exits");
-            dec_lean_exit2_kernel<<<cdiv((size_t)ngroups * LA, 256), 256, 0, s>>>(exit1, ntiles, ngroups, LA, exit2);
-            LAUNCH_CHECK();
-            dec_lean_groups_kernel<<<1, 64, 0, s>>>(exit2, ngroups, LA, gentry);
-            LAUNCH_CHECK();
-            dec_lean_tiles_kernel<<<cdiv(ngroups, 64), 64, 0, s>>>(exit1, gentry, ntiles, ngroups, LA, tentry);
-            LAUNCH_CHECK();
+            const u16* tentry = dx_entries(c, exit0, ntiles, LA, levels);      // (the segment's first token starts at its first bit position: state 0)
             tick("group + tile entries");
             const unsigned gw = std::min<u32>(cdiv(ntiles, 256), 4096u);
             dec_lean_walk_kernel<Tab, false><<<gw, 256, 0, s>>>(s32, x_in, m, P, d_tab, tentry, ntiles, tcount, tout, 0, 0, nullptr, nullptr, nullptr, nullptr, d_sc);

@@ -105,9 +105,11 @@ u8* decode_dest(Sink& o, size_t n);
 void resolve_and_download(Ctx& c, size_t n, u8* d_text, u32* d_ref, const u32* d_pos, const u32* d_src, const u32* d_len, size_t z,
                           u32* d_changed, Sink& out, DecodeStats* st);
 
-// option dec_log: the time since the previous call, on stderr under `who` (synchronises the stream); nothing without the option
+// option dec_log: the time since the previous call, on stderr under `who` (synchronises the stream); nothing without the option.
+// The second form has the caller's own option decide (bwt_log).
 using DecTick = std::function<void(const char*)>;
 DecTick dec_ticker(Ctx& c, const char* who);
+DecTick dec_ticker(Ctx& c, const char* who, bool on);
 // The arena is too small for what follows: the live arrays (pointer, bytes) travel to the host and back into an arena of `bytes`;
 // the pointers are updated, everything else in the arena is gone.
 void regrow_arena(Ctx& c, size_t bytes, std::initializer_list<std::pair<void**, size_t>> live);
