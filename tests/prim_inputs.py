@@ -180,6 +180,13 @@ def orbit_reference(nxt):
 TILE_EXIT_NTILES = (1, DX_G - 1, DX_G, DX_G + 1, DX_G * DX_G - 1, DX_G * DX_G, DX_G * DX_G + 1)     # the group borders of every level
 TILE_EXIT_STATES = (1, 13, 22)                                                                       # sle's fewest, sle's most, rle
 TILE_EXIT_KINDS = ("random", "no_none", "all_none", "ends_in_first_group")
+TILE_EXIT_WIDE_STATES = (64, 255)                                                                    # encode(huff): its longest code, up to 255
+# (ntiles, states, kinds): the widths of sle and rle at every group border; the huff decoder's at the borders of the first level with
+# every kind and once at three levels (a table of 134 MB at 255 states)
+TILE_EXIT_CASES = tuple((n, s, TILE_EXIT_KINDS) for s in TILE_EXIT_STATES for n in TILE_EXIT_NTILES) + \
+    tuple((n, s, TILE_EXIT_KINDS) for s in TILE_EXIT_WIDE_STATES for n in TILE_EXIT_NTILES[:4]) + \
+    tuple((DX_G * DX_G + 1, s, ("random",)) for s in TILE_EXIT_WIDE_STATES)
+TILE_EXIT_IDS = ["%d-%d" % c[:2] for c in TILE_EXIT_CASES]
 TILE_EXIT_END = 100          # "ends_in_first_group": the tile whose exits are all NONE
 
 
@@ -191,7 +198,10 @@ def tile_exits(ntiles, states, kind, rng):
         return np.full((ntiles, states), DX_NONE, dtype=np.uint16)
     ex = rng.integers(0, states, size=(ntiles, states), dtype=np.uint16)
     if kind == "random":
-        ex[rng.random((ntiles, states)) < 1.0 / 4096] = DX_NONE
+        if ntiles * states <= 1 << 24:
+            ex[rng.random((ntiles, states)) < 1.0 / 4096] = DX_NONE
+        else:                                                                 # the same density without a float per entry
+            ex.reshape(-1)[rng.integers(0, ntiles * states, size=ntiles * states // 4096)] = DX_NONE
         e = 0
         for t in range(min(ntiles, 3 * DX_G)):
             if ex[t, e] == DX_NONE:
@@ -212,6 +222,18 @@ def tile_entries_reference(exits):
         if e != DX_NONE:
             e = row[e]
     return np.array(entry, dtype=np.uint16)
+
+
+def tile_entries_reference_array(exits):
+    """the same walk on the array itself: no list of the whole table (134 MB at 2^18 tiles of 255 states)"""
+    entry = np.full(len(exits), DX_NONE, dtype=np.uint16)
+    e = 0
+    for t in range(len(exits)):
+        entry[t] = e
+        e = int(exits[t, e])
+        if e == DX_NONE:
+            break
+    return entry
 
 
 # ---- classes of the selection ----------------------------------------------------------------------------------------------------

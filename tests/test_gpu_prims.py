@@ -283,12 +283,12 @@ def test_mark_orbit_vs_serial_walk(gpu_ctx, kind, n):
 
 
 # ---- tile entries ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("states", P.TILE_EXIT_STATES)
-@pytest.mark.parametrize("ntiles", P.TILE_EXIT_NTILES)
-def test_tile_entries_vs_sequential_walk(gpu_ctx, ntiles, states):
-    for kind in P.TILE_EXIT_KINDS:
+@pytest.mark.parametrize("ntiles,states,kinds", P.TILE_EXIT_CASES, ids=P.TILE_EXIT_IDS)
+def test_tile_entries_vs_sequential_walk(gpu_ctx, ntiles, states, kinds):
+    for kind in kinds:
         ex = P.tile_exits(ntiles, states, kind, np.random.default_rng(ntiles + states))
-        assert np.array_equal(gpu_ctx.prim_tile_entries(ex), P.tile_entries_reference(ex)), (kind, ntiles, states)
+        want = P.tile_entries_reference(ex) if ex.size <= 1 << 24 else P.tile_entries_reference_array(ex)
+        assert np.array_equal(gpu_ctx.prim_tile_entries(ex), want), (kind, ntiles, states)
 
 
 def test_tile_entries_refuses_exits_outside_the_table(gpu_ctx):
@@ -296,6 +296,11 @@ def test_tile_entries_refuses_exits_outside_the_table(gpu_ctx):
     _refused(lambda: gpu_ctx.prim_tile_entries(u16([[0, 1], [2, 0]])))                    # an exit == states
     _refused(lambda: gpu_ctx.prim_tile_entries(u16([[0, 1], [0, 0xFFFE]])))               # ... and one just below NONE
     _refused(lambda: gpu_ctx.prim_tile_entries(np.zeros((3, 0), dtype=np.uint16)))        # no states
+    wide = np.zeros((3, 255), dtype=np.uint16)
+    wide[1, 254] = 255
+    _refused(lambda: gpu_ctx.prim_tile_entries(wide))                                      # an exit == states at the huff decoder's widest
+    wide[1, 254] = 254
+    assert gpu_ctx.prim_tile_entries(wide).tolist() == [0, 0, 0]
     assert gpu_ctx.prim_tile_entries(u16([[1, 0], [0xFFFF, 0xFFFF], [0, 0]])).tolist() == [0, 1, 0xFFFF]      # the context survives
 
 

@@ -149,15 +149,34 @@ def test_tile_entries_reference_is_the_sequential_walk():
     assert P.tile_entries_reference(np.array([[N]], dtype=np.uint16)).tolist() == [0]      # the first tile is always entered in state 0
 
 
-@pytest.mark.parametrize("states", P.TILE_EXIT_STATES)
-@pytest.mark.parametrize("ntiles", P.TILE_EXIT_NTILES)
-def test_tile_exits(ntiles, states):
+def test_tile_entries_array_walk_agrees_with_the_list_walk():
+    for ntiles, states in ((1, 1), (7, 2), (P.DX_G + 1, 13), (3 * P.DX_G, 64), (5000, 255)):
+        for kind in P.TILE_EXIT_KINDS:
+            ex = P.tile_exits(ntiles, states, kind, np.random.default_rng(ntiles))
+            a, b = P.tile_entries_reference_array(ex), P.tile_entries_reference(ex)
+            assert a.dtype == b.dtype and np.array_equal(a, b), (ntiles, states, kind)
+    N = P.DX_NONE
+    assert P.tile_entries_reference_array(np.array([[1, 0], [N, 1], [0, 0], [1, N], [0, N], [0, 0]], dtype=np.uint16)).tolist() == [0, 1, 1, 0, 1, N]
+
+
+def test_tile_exit_cases_cover_the_decoders_widths():
+    cases = {(n, s): k for n, s, k in P.TILE_EXIT_CASES}
+    assert len(cases) == len(P.TILE_EXIT_CASES) == len(set(P.TILE_EXIT_IDS))
     G = P.DX_G
-    for kind in P.TILE_EXIT_KINDS:
+    for s in (1, 13, 22):
+        assert all(cases[(n, s)] == P.TILE_EXIT_KINDS for n in P.TILE_EXIT_NTILES)
+    for s in (64, 255):
+        assert all(cases[(n, s)] == P.TILE_EXIT_KINDS for n in (1, G - 1, G, G + 1)) and cases[(G * G + 1, s)] == ("random",)
+
+
+@pytest.mark.parametrize("ntiles,states,kinds", P.TILE_EXIT_CASES, ids=P.TILE_EXIT_IDS)
+def test_tile_exits(ntiles, states, kinds):
+    G = P.DX_G
+    for kind in kinds:
         ex = P.tile_exits(ntiles, states, kind, np.random.default_rng(ntiles + states))
         assert ex.dtype == np.uint16 and ex.shape == (ntiles, states)
         assert ((ex < states) | (ex == P.DX_NONE)).all(), kind                # the precondition of the entry point
-        entry = P.tile_entries_reference(ex)
+        entry = P.tile_entries_reference(ex) if ex.size <= 1 << 24 else P.tile_entries_reference_array(ex)
         assert len(entry) == ntiles and entry[0] == 0
         ended = np.flatnonzero(entry == P.DX_NONE)
         assert (entry[:ended[0] if len(ended) else ntiles] < states).all()
@@ -165,7 +184,8 @@ def test_tile_exits(ntiles, states):
         if kind == "no_none":
             assert len(ended) == 0 and (ex != P.DX_NONE).all()
             if states > 1 and ntiles >= G:
-                assert len(np.unique(entry)) == states                        # the chain really moves through the states
+                # the chain really moves through the states (about G draws: all of a few states, most of the huff decoder's many)
+                assert len(np.unique(entry)) == states if states <= 22 else len(np.unique(entry)) > states // 2
         elif kind == "all_none":
             assert len(ended) == ntiles - 1
         elif kind == "ends_in_first_group":

@@ -304,8 +304,8 @@ void pipeline_decompress_loops(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, in
 
 // The stages backwards on the device: one upload, every intermediate in the arena, one download.  False: the device cannot hold the
 // arena (nothing has been written, the host loops take the call).  An arena that turns out too small for a stage's output -- the
-// lengths are only known once the stage in front has been decoded -- is reserved again with what is known by then and the call starts
-// over: at most once per stage.
+// lengths are only known once the stage in front has been decoded -- is reserved again with what is known by then, the output's length
+// and the scratch the stage held beside it, and the call starts over: at most once per stage, and never with the same figures twice.
 bool pipeline_decompress_device(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, size_t len, Sink& s, PipeReport& rep) {
     Ctx& c = ctx->c;
     const bool plog = c.pipe_log != 0;
@@ -313,12 +313,13 @@ bool pipeline_decompress_device(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, i
     const int first = lead_bwt ? 1 : 0;
     u64 known[TDC_GPU_PIPELINE_MAX_STAGES] = {0};              // decoded length of stage i, once an attempt has seen it
     bool have[TDC_GPU_PIPELINE_MAX_STAGES] = {false};
+    u64 held[TDC_GPU_PIPELINE_MAX_STAGES] = {0};               // scratch stage i held when its output did not fit
     u64 extra = 0;
     for (int attempt = 0; attempt < 2 * TDC_GPU_PIPELINE_MAX_STAGES + 4; ++attempt) {
         u64 need = len + 4096 + extra, L = len;
         for (int i = k - 1; i >= first; --i) {
             const u64 out = have[i] ? known[i] : stages[i].kind == TDC_GPU_STAGE_MTF ? L : std::min<u64>(3 * L + 4096, STAGE_MAX_BYTES);
-            need += out + 4096 + stage_decode_scratch_bound(L, out);
+            need += out + 4096 + std::max<u64>(stage_decode_scratch_bound(L, out), held[i] + 4096);
             L = out;
         }
         if (lead_bwt) need += bwt_inverse_arena((size_t)std::min<u64>(L, 0x7FFFFFFFull)) + 4096;
@@ -359,14 +360,18 @@ bool pipeline_decompress_device(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, i
                     if (cur.len) HIP_TRY(hipMemcpy(a.data(), cur.d, (size_t)cur.len, hipMemcpyDeviceToHost));
                     host_stage_decode(stages[i], a, b);
                     const size_t off = align_up(c.arena.top, 256);
-                    if (off + b.size() + 64 > c.arena.size) throw StageArenaShort{b.size()};
+                    if (off + b.size() + 64 > c.arena.size) throw StageArenaShort{b.size(), 0};
                     StageOut o;
                     o.d = c.arena.get<u8>(b.size() + 64); o.len = b.size();
                     if (o.len) HIP_TRY(hipMemcpy(o.d, b.data(), b.size(), hipMemcpyHostToDevice));
                     cur = o;
                 }
             } catch (const StageArenaShort& a) {
-                known[i] = a.out_bytes; have[i] = true; again = true;
+                // The same figures a second time: the reservation already counts them and was still short -- a stage behind
+                // StageHostOnly, whose output is measured against the whole arena, or an arena that could not grow.  Not the
+                // same attempt again: grow as the out-of-memory path below does.
+                if (have[i] && known[i] == a.out_bytes && held[i] >= a.scratch_bytes) extra = extra ? 2 * extra : need;
+                known[i] = a.out_bytes; have[i] = true; held[i] = std::max(held[i], a.scratch_bytes); again = true;
             } catch (const HipError& e) {
                 if (e.e != hipErrorOutOfMemory) throw;             // the stage's scratch did not fit
                 (void)hipGetLastError();

@@ -41,10 +41,14 @@ StageOut sle_literals_device(Ctx& c, const u8* d_in, size_t n, u32 kmer);      /
 // The decoders (bytestages_decode.hip): the host loops of host/tdc_coders.hpp are their specification, including what they refuse.
 // d_in: n bytes in the arena (256-byte aligned, 64 allocated bytes behind them).  The output comes from the bottom of the arena, scratch
 // from its top (Arena::alloc_top: the caller releases it once the output exists).  Malformed input: StreamFormatError; an output of more
-// than 2^32 - 2 bytes: StageTooLarge; an output the arena has no room for: StageArenaShort with its length -- each before anything of
-// the output is written; a Huffman header that does not end inside the first 4 KiB (no encoder writes one): StageHostOnly.
-struct StageArenaShort { u64 out_bytes; };
+// than 2^32 - 2 bytes: StageTooLarge; an output the arena has no room for: StageArenaShort with its length and the scratch the stage
+// holds at that moment -- each before anything of the output is written; a Huffman header that does not end inside the first 4 KiB (no
+// encoder writes one): StageHostOnly.
+struct StageArenaShort { u64 out_bytes, scratch_bytes; };
 struct StageHostOnly {};
+// What the driver reserves for a stage's scratch before it has run: n input bytes, `out` output bytes.  Enough for every stream an
+// encoder writes; a stage that holds more (encode(huff) under a header that claims codes of more than 75 bits) says so in
+// StageArenaShort::scratch_bytes.
 u64 stage_decode_scratch_bound(u64 n, u64 out);
 StageOut rle_decode_device(Ctx& c, const u8* d_in, size_t n, u64 offset);
 StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n);

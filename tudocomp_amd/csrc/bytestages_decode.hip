@@ -30,7 +30,7 @@ namespace {
 // the output of a stage, from the bottom of the arena
 u8* stage_out(Ctx& c, u64 len) {
     const size_t off = align_up(c.arena.top, 256);
-    if (off + len + 64 > c.arena.size - c.arena.top_hi) throw StageArenaShort{len};
+    if (off + len + 64 > c.arena.size - c.arena.top_hi) throw StageArenaShort{len, c.arena.top_hi};
     return c.arena.get<u8>((size_t)len + 64);
 }
 
@@ -463,8 +463,11 @@ __global__ void __launch_bounds__(256) rld_fill_kernel(const u32* __restrict__ h
 
 }  // namespace
 
-// rows of 256 bytes per chunk and their lists, the levels above; tile tables of huff (<= 2 x 255 + 10 bytes per 2048 bits), sle (2 x 13 + 10)
-// and rle
+// mtf: rows of 256 bytes per chunk of 1 KiB and their lists (n / 2), the levels above (n / 8 covers them many times).  The tile tables of
+// huff and sle (2 x longest + 10 bytes per 2048 bits of input, entries and levels above included) fit into the same 5 n / 8 up to a longest
+// code of 75 bits: every table an encoder writes (2^32 symbols reach 46 bits) and sle's 13.  A header may claim up to 255: those tables
+// take 2 n, are NOT covered here, and reach the driver through StageArenaShort::scratch_bytes.  rle: 2 x 22 + 10 bytes per 512 bytes of
+// input and 12 bytes per 256 bytes of output (out / 16).
 u64 stage_decode_scratch_bound(u64 n, u64 out) { return n / 2 + n / 8 + out / 16 + ((u64)4 << 20); }
 
 StageOut mtf_decode_device(Ctx& c, const u8* d_in, size_t n) {
