@@ -402,6 +402,47 @@ int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t l
 int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window,
                                     uint8_t* out, size_t out_cap, size_t* out_len, uint64_t* factors, uint32_t* rounds);
 
+/* ---- lzss over a batch: many independent texts in one call, both directions (lzss_sw_batch.hip, DESIGN.md section 5.7 "Batches").
+ * The texts lie back to back in `in`: text k = in[in_off[k], in_off[k + 1]); in_off has count + 1 entries, does not decrease, and
+ * in_off[0] = 0.  Stream k = out[out_off[k], out_off[k] + out_len[k]) is byte for byte what tdc_gpu_lzss_sw_compress returns for text k
+ * alone with the same window, threshold and coder (TDC_GPU_CODER_ASCII, _BIT, _GAMMA, _DELTA), the empty text included: nothing of one
+ * text reaches another one's stream -- candidates, look-ahead and, under coder=bit, the width of a distance are those of the position
+ * inside its own text.  out_off[k] is a multiple of 8, out_off[count] the number of bytes used; the bytes between two streams are
+ * unspecified.  The device makes ONE pass over the concatenation and the call synchronises a constant number of times, whatever count is.
+ * status[k]: TDC_GPU_OK, or -- coder=bit and a length of text k that bits_for(window) bits do not hold, the single call's refusal --
+ * TDC_GPU_ERR_UNSUPPORTED with out_len[k] = 0; the other texts are coded normally and the call returns TDC_GPU_OK.
+ * The call itself: TDC_GPU_ERR_ARG for a NULL argument, window 0, in_off[0] != 0 or a decreasing in_off; TDC_GPU_ERR_UNSUPPORTED for a
+ * window above 4096 or another coder; TDC_GPU_ERR_TOO_LARGE for more than 2^32 - 2 bytes in all (these are decided from the arguments
+ * alone, before the context is looked at); TDC_GPU_ERR_OOM with the required size in out_off[count] if out_cap is too small -- nothing is
+ * written to `out` then.  count = 0 is valid and writes only out_off[0] = 0.
+ * stats (may be NULL): n (all input bytes), out_len (bytes used), factors (summed over the batch), ms_h2d, ms_factorize, ms_encode,
+ * ms_d2h, ms_total, arena_bytes. */
+int tdc_gpu_lzss_sw_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count,
+                                   uint32_t window, uint32_t threshold, int coder,
+                                   uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
+                                   int32_t* status /* count */, tdc_gpu_stats* stats);
+/* what `out` of tdc_gpu_lzss_sw_compress_batch needs at most: the sum of tdc_gpu_lzss_sw_bound of every text, each rounded up to 8.
+ * 0 where tdc_gpu_lzss_sw_bound returns 0 (coder, window), for offsets the call refuses, or for more than 2^32 - 2 bytes in all. */
+size_t tdc_gpu_lzss_sw_batch_bound(const uint64_t* in_off, size_t count, uint32_t window, int coder);
+/* The decoder of such a batch, or of any collection of lzss streams: stream k = streams[s_off[k], s_off[k] + s_len[k]) (any order, any
+ * alignment; together they must lie within 2^32 - 2 bytes), coder = TDC_GPU_CODER_BIT, _GAMMA or _DELTA (TDC_GPU_CODER_ASCII and every
+ * other coder: TDC_GPU_ERR_UNSUPPORTED -- loop tdc_lzss_sw_decode for ascii).  Always on the device, one wave per stream; option
+ * dec_parse is not consulted.  Text k = out[out_off[k], out_off[k + 1]), the texts back to back.  status[k] is the verdict
+ * tdc_lzss_sw_decode gives on stream k alone -- TDC_GPU_OK, TDC_GPU_ERR_ARG or TDC_GPU_ERR_TOO_LARGE -- and the text is the same bytes
+ * where it is TDC_GPU_OK; a refused stream contributes 0 bytes and disturbs no neighbour.  A distance is checked against the token's
+ * position in its OWN text: the text in front of it in `out` is never reachable.  The device caps of tdc_gpu_lzss_sw_decompress hold
+ * here too: a gamma / delta distance or length field of more than 32 value bits, or a literal code of more than 8, is
+ * TDC_GPU_ERR_ARG although the host loop reads it (no encoder writes one).
+ * out == NULL or out_cap too small: TDC_GPU_ERR_OOM with the required total in out_off[count] and all of out_off / status filled -- the
+ * sizes pass alone, so that a caller can size its buffer; nothing is written to `out`.  More than 2^32 - 2 bytes of text in all:
+ * TDC_GPU_ERR_TOO_LARGE.  TDC_GPU_ERR_ARG: a NULL s_off, s_len, out_off or status, coder=bit with window 0 (only coder=bit reads it).
+ * stats (may be NULL): n (all stream bytes), out_len (all text bytes), factors (factor tokens of the accepted streams), ms_h2d,
+ * ms_factorize (the sizes pass), ms_encode (the write pass), ms_d2h, ms_total, arena_bytes. */
+int tdc_gpu_lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len,
+                                     size_t count, int coder, uint32_t window,
+                                     uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */,
+                                     int32_t* status /* count */, tdc_gpu_stats* stats);
+
 /* ---- repair: RePairCompressor<BitCoder | ASCIICoder | EliasGammaCoder | EliasDeltaCoder> (compressors/RePairCompressor.hpp:96-336;
  * DESIGN.md section 5.8): the Re-Pair grammar, built ON THE DEVICE.  No input restrictions (raw bytes, no sentinel).  Symbols are 32-bit:
  * 0 .. 255 are bytes, 256 + k is rule k; a rule is l << 32 | r.  Per round every adjacent pair of the live sequence is counted

@@ -239,6 +239,21 @@ def lzss_sw_bound(n, window=16, coder=CODER_BIT):
     return _native.load().tdc_gpu_lzss_sw_bound(n, int(window), int(coder))
 
 
+def _offsets(lengths):
+    """in_off of a batch: count + 1 ascending uint64, the first one 0"""
+    off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    if len(lengths):
+        np.cumsum(np.asarray(lengths, dtype=np.uint64), out=off[1:])
+    return off
+
+
+def lzss_sw_batch_bound(lengths, window=16, coder=CODER_BIT):
+    """what the output of lzss_sw_compress_batch needs at most for texts of these lengths: the single bounds, each rounded up to 8,
+    summed (0: a coder or a window lzss does not take, or more than 2^32 - 2 bytes in all)"""
+    off = _offsets(lengths)
+    return _native.load().tdc_gpu_lzss_sw_batch_bound(_ptr(off), len(lengths), int(window), int(coder))
+
+
 def repair_decode(data, coder=CODER_BIT):
     """RePairCompressor::decompress (:287-336) on the host, rules expanded with an explicit stack"""
     return _host_decode("tdc_repair_decode", data, int(coder))
@@ -546,6 +561,83 @@ class Context:
         if rc:
             self._raise_required(rc, n.value)
         return n.value, {"factors": f.value, "rounds": r.value, "device_parse": int(self._L.tdc_gpu_ctx_last_decode_on_device(self._h))}
+
+    def lzss_sw_compress_batch_into(self, data, in_off, out, window=16, threshold=3, coder=CODER_BIT):
+        """tdc_gpu_lzss_sw_compress_batch on caller-owned buffers: text k = data[in_off[k]:in_off[k + 1]] (in_off: count + 1 uint64), the
+        streams into `out` (PinnedBuffer or writable uint8 array; lzss_sw_batch_bound sizes it).  Returns (out_off, out_len, status,
+        stats): stream k = out[out_off[k]:out_off[k] + out_len[k]], status[k] -6 for a text coder=bit would truncate.  A buffer that is
+        too small raises TdcGpuError (status -5) whose `required` is the size."""
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        count = len(off) - 1
+        out_off, out_len = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+        status, st = np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = self._L.tdc_gpu_lzss_sw_compress_batch(self._h, _ptr(ta) if len(ta) else None, _ptr(off), count, int(window), int(threshold),
+                                                    int(coder), _ptr(oa), oa.size, _ptr(out_off), _ptr(out_len), _ptr(status), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, int(out_off[count]))
+        return out_off, out_len[:count], status[:count], st.as_dict()
+
+    def lzss_sw_compress_batch(self, texts, window=16, threshold=3, coder=CODER_BIT):
+        """lzss over many independent texts in one call: returns (list of streams, statuses, stats).  Stream k is what lzss_sw_compress
+        returns for texts[k] alone; where coder=bit would truncate a length of text k, statuses[k] is -6 and the stream is b""."""
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        off = _offsets(lengths)
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        cap = lzss_sw_batch_bound(lengths, window, coder)
+        out = np.empty(max(cap, 8), dtype=np.uint8)
+        out_off, out_len, status, st = self.lzss_sw_compress_batch_into(data, off, out, window, threshold, coder)
+        streams = [out[int(o):int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+        return streams, status.tolist(), st
+
+    def lzss_sw_decompress_batch_into(self, blob, s_off, s_len, out, coder, window=16):
+        """tdc_gpu_lzss_sw_decompress_batch on caller-owned buffers: stream k = blob[s_off[k]:s_off[k] + s_len[k]], coder bit, gamma or
+        delta, always on the device.  out: PinnedBuffer, writable uint8 array, or None for the sizes pass alone.  Returns (out_off,
+        status, stats): text k = out[out_off[k]:out_off[k + 1]], status[k] what lzss_sw_decode says of stream k alone (0, -2, -4).
+        out None or too small raises TdcGpuError (status -5) with `required`, `out_off` and `statuses` filled."""
+        ba = blob.a if isinstance(blob, PinnedBuffer) else _u8(blob)
+        oa = None if out is None else (out.a if isinstance(out, PinnedBuffer) else out)
+        so, sl = np.ascontiguousarray(s_off, dtype=np.uint64), np.ascontiguousarray(s_len, dtype=np.uint64)
+        count = len(so)
+        out_off, status, st = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = self._L.tdc_gpu_lzss_sw_decompress_batch(self._h, _ptr(ba) if len(ba) else None, _ptr(so), _ptr(sl), count, int(coder), int(window),
+                                                      None if oa is None else _ptr(oa), 0 if oa is None else oa.size, _ptr(out_off),
+                                                      _ptr(status), ctypes.byref(st))
+        if rc:
+            err = TdcGpuError(rc, self._L.tdc_gpu_last_error(self._h).decode())
+            err.required = int(out_off[count]) if rc == -5 else None
+            err.out_off, err.statuses = out_off, status[:count]
+            raise err
+        return out_off, status[:count], st.as_dict()
+
+    def lzss_sw_decompress_batch(self, streams, coder, window=16):
+        """the decoder of lzss_sw_compress_batch, or of any list of lzss streams: returns (list of texts, statuses, stats); a refused
+        stream (status -2 or -4, as lzss_sw_decode on it alone) yields b"" and disturbs no neighbour"""
+        parts = [_u8(x) for x in streams]
+        s_len = np.array([len(a) for a in parts], dtype=np.uint64)
+        s_off = np.zeros(len(parts), dtype=np.uint64)
+        pos = 0
+        for k, a in enumerate(parts):                                 # every stream at a multiple of 8, as the compressor leaves them
+            s_off[k] = pos
+            pos += (len(a) + 7) & ~7
+        blob = np.zeros(pos, dtype=np.uint8)
+        for o, a in zip(s_off, parts):
+            blob[int(o):int(o) + len(a)] = a
+        try:
+            self.lzss_sw_decompress_batch_into(blob, s_off, s_len, None, coder, window)
+            need = 0
+        except TdcGpuError as e:
+            if e.status != -5:
+                raise
+            need = e.required
+        out = np.empty(max(need, 1), dtype=np.uint8)
+        out_off, status, st = self.lzss_sw_decompress_batch_into(blob, s_off, s_len, out, coder, window)
+        texts = [out[int(a):int(b)].tobytes() for a, b in zip(out_off[:-1], out_off[1:])]
+        return texts, status.tolist(), st
+
+    lzss_sw_batch_bound = staticmethod(lzss_sw_batch_bound)
 
     def repair_compress(self, data, max_rules=0, coder=CODER_BIT):
         """RePairCompressor<coder>::compress on raw bytes (no escaping), the grammar built on the device; coder: CODER_BIT, _ASCII, _GAMMA
@@ -1198,6 +1290,30 @@ class LZSSSlidingWindowCompressor:
                 raise RuntimeError("lzss: dec=gpu needs a context")
             return self.ctx.lzss_sw_decompress(stream, self.window, self.coder)[0]
         return lzss_sw_decode(stream, self.coder, self.window)
+
+    def compress_batch(self, texts):
+        """every text on its own in one device call: (list of streams, statuses); stream k is compress(texts[k])"""
+        out, status, st = self.ctx.lzss_sw_compress_batch(texts, self.window, self.threshold, self.coder)
+        self.last_stats = st
+        return out, status
+
+    def decompress_batch(self, streams):
+        """(list of texts, statuses) on the device, one wave per stream; coder=ascii loops the host decoder"""
+        if self.coder == CODER_ASCII:
+            out, status = [], []
+            for x in streams:
+                try:
+                    out.append(lzss_sw_decode(x, self.coder, self.window))
+                    status.append(0)
+                except TdcGpuError as e:
+                    out.append(b"")
+                    status.append(e.status)
+            return out, status
+        if self.ctx is None:
+            raise RuntimeError("lzss: decompress_batch needs a context")
+        out, status, st = self.ctx.lzss_sw_decompress_batch(streams, self.coder, self.window)
+        self.last_stats = st
+        return out, status
 
 
 class RePairCompressor:

@@ -37,6 +37,7 @@ SYMBOLS = [
     "tdc_gpu_lzss_lcp_compress_into", "tdc_gpu_lzss_lcp_bound", "tdc_gpu_lzss_lcp_decompress", "tdc_gpu_lzss_lcp_decompress_into", "tdc_lzss_decode",
     "tdc_gpu_lzss_sw_compress", "tdc_gpu_lzss_sw_compress_into", "tdc_gpu_lzss_sw_bound", "tdc_gpu_lzss_sw_factorize", "tdc_lzss_sw_factors",
     "tdc_lzss_sw_decode", "tdc_gpu_lzss_sw_decompress", "tdc_gpu_lzss_sw_decompress_into",
+    "tdc_gpu_lzss_sw_compress_batch", "tdc_gpu_lzss_sw_batch_bound", "tdc_gpu_lzss_sw_decompress_batch",
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
     "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
 ]
@@ -205,6 +206,10 @@ def load():
     L.tdc_repair_decode.argtypes = [vp, sz, i32, vp, sz, psz]
     L.tdc_gpu_lzss_sw_decompress.argtypes = [vp, vp, sz, i32, u32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lzss_sw_decompress_into.argtypes = [vp, vp, sz, i32, u32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    L.tdc_gpu_lzss_sw_compress_batch.argtypes = [vp, vp, vp, sz, u32, u32, i32, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]
+    L.tdc_gpu_lzss_sw_batch_bound.argtypes = [vp, sz, u32, i32]
+    L.tdc_gpu_lzss_sw_batch_bound.restype = sz
+    L.tdc_gpu_lzss_sw_decompress_batch.argtypes = [vp, vp, vp, vp, sz, i32, u32, vp, sz, vp, vp, ctypes.POINTER(Stats)]
     L.tdc_gpu_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     L.tdc_gpu_option_count.argtypes = []
     L.tdc_gpu_option_name.argtypes = [i32]

@@ -1,6 +1,7 @@
 // api_compress.hip -- C ABI (include/tdc_gpu.h): lcpcomp, lzss_lcp, lz78, lzw, lzss and repair compression -- the upload, the text's arrays, the factors,
 // the whole pipeline on host and device buffers.
 #include "api.hpp"
+#include "bitsink.hpp"
 
 #include <vector>
 
@@ -684,6 +685,99 @@ int tdc_gpu_lzss_sw_factorize(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uin
         ev.finish();
         *pos = hp.release<uint32_t>(); *src = hs.release<uint32_t>(); *len = hl.release<uint32_t>(); *z = cnt;
     });
+}
+
+}  // extern "C"
+
+// ---- lzss over a batch of texts (lzss_sw_batch.hip, DESIGN.md section 5.7 "Batches") ----------------------------------------------------
+namespace {
+// what can be said of the arguments without a device; throws ArgError
+void lzss_sw_batch_check(const uint8_t* in, const uint64_t* in_off, size_t count, uint32_t window, int coder, const uint8_t* out,
+                         const uint64_t* out_off, const uint64_t* out_len, const int32_t* status) {
+    if (!in_off || !out_off || (count && (!out || !out_len || !status))) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (lzss_sw_kind(coder) < 0) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss: coder must be ascii, bit, gamma or delta"};
+    if (window == 0) throw ArgError{TDC_GPU_ERR_ARG, "lzss: window must be >= 1"};
+    if (window > LZSS_SW_MAX_WINDOW) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss: windows above 4096 are not built"};
+    if (in_off[0] != 0) throw ArgError{TDC_GPU_ERR_ARG, "lzss batch: in_off[0] must be 0"};
+    for (size_t k = 0; k < count; ++k)
+        if (in_off[k + 1] < in_off[k]) throw ArgError{TDC_GPU_ERR_ARG, "lzss batch: in_off must not decrease"};
+    if (in_off[count] > 0xFFFFFFFEull || count > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzss batch: the texts must be at most 2^32 - 2 bytes in all"};
+    if (!in && in_off[count]) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+}
+// the single bounds, each rounded up to 8, summed; 0 where one of them is 0 (window and kind are valid here)
+size_t lzss_sw_batch_bound_sum(const uint64_t* in_off, size_t count, uint32_t window, int kind) {
+    size_t sum = 0;
+    for (size_t k = 0; k < count; ++k) {
+        const size_t b = in_off[k + 1] >= in_off[k] ? lzss_sw_bound((size_t)(in_off[k + 1] - in_off[k]), window, kind) : 0;
+        if (!b) return 0;
+        sum += align_up(b, 8);
+    }
+    return sum;
+}
+
+void lzss_sw_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, uint32_t window, uint32_t threshold,
+                            int coder, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_len, int32_t* status, tdc_gpu_stats* stats) {
+    const int kind = lzss_sw_kind(coder);
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    out_off[0] = 0;
+    if (count == 0) return;
+    const size_t n = (size_t)in_off[count];
+    std::vector<u32> off32(count + 1);
+    for (size_t k = 0; k <= count; ++k) off32[k] = (u32)in_off[k];
+    // per byte as the single call (the worst case of the output behind the position arrays), 24 bytes per text
+    reserve_arena(c, lzss_sw_arena(n, lzss_sw_batch_bound_sum(in_off, count, window, kind) + 16) + 24 * (count + 1) + 4096);
+    Events ev(c);
+    const int e0 = ev.tick();
+    const u8* d_text = upload_plain(c, in, n);
+    LzssSwBatch B;
+    u32* d_off = c.arena.get<u32>(count + 1);
+    B.off = d_off; B.gfirst = c.arena.get<u64>(count + 1); B.ooff = c.arena.get<u64>(count + 1); B.flag = c.arena.get<u32>(count);
+    HIP_TRY(hipMemcpyAsync(d_off, off32.data(), (count + 1) * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+    const int e1 = ev.tick();
+    lzss_sw_batch_sizes(c, d_text, n, count, window, threshold, kind, B);
+    // the sizes: where every stream goes, its bits, and the texts BitCoder would truncate
+    std::vector<u64> gfirst(count + 1);
+    std::vector<u32> flag(count);
+    c.read_n(B.ooff, (u64*)out_off, count + 1);
+    c.read_n(B.gfirst, gfirst.data(), count + 1);
+    c.read_n(B.flag, flag.data(), count);
+    for (size_t k = 0; k < count; ++k) {
+        status[k] = flag[k] ? TDC_GPU_ERR_UNSUPPORTED : TDC_GPU_OK;
+        out_len[k] = flag[k] ? 0 : bit_stream_len(gfirst[k + 1] - gfirst[k]);
+    }
+    const int e2 = ev.tick();
+    const size_t used = (size_t)out_off[count];
+    if (used > out_cap) throw ArgError{TDC_GPU_ERR_OOM, "lzss batch: output buffer too small (out_off[count] holds the required size)"};
+    u8* d_out = c.arena.get<u8>(used + 8);
+    lzss_sw_batch_pack(c, d_text, count, window, kind, B, d_out, used);
+    const int e3 = ev.tick();
+    if (used) HIP_TRY(hipMemcpyAsync(out, d_out, used, hipMemcpyDeviceToHost, c.stream));
+    const int e4 = ev.tick();
+    if (stats) {
+        stats->n = n; stats->out_len = used; stats->factors = B.factors; stats->arena_bytes = c.arena.high;
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_d2h, e3, e4); ev.span(&stats->ms_total, e0, e4);
+    }
+    ev.finish();
+}
+}  // namespace
+
+extern "C" {
+
+size_t tdc_gpu_lzss_sw_batch_bound(const uint64_t* in_off, size_t count, uint32_t window, int coder) {
+    const int kind = lzss_sw_kind(coder);
+    if (!in_off || in_off[0] != 0 || kind < 0 || window == 0 || window > LZSS_SW_MAX_WINDOW) return 0;
+    const size_t sum = lzss_sw_batch_bound_sum(in_off, count, window, kind);
+    return in_off[count] > 0xFFFFFFFEull ? 0 : sum;
+}
+
+int tdc_gpu_lzss_sw_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, uint32_t window, uint32_t threshold,
+                                   int coder, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_len, int32_t* status,
+                                   tdc_gpu_stats* stats) {
+    try { lzss_sw_batch_check(in, in_off, count, window, coder, out, out_off, out_len, status); }      // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { lzss_sw_compress_batch(ctx, in, in_off, count, window, threshold, coder, out, out_cap, out_off, out_len, status, stats); });
 }
 
 }  // extern "C"

@@ -117,6 +117,84 @@ void lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int
     sink_commit(s, n);
 }
 
+// ---- lzss streams in a batch (lzss_sw_batch.hip): one wave per stream, never the host loop ----------------------------------------
+void lzss_sw_batch_dec_check(const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder, uint32_t window,
+                             const uint64_t* out_off, const int32_t* status) {
+    if (!out_off || (count && (!s_off || !s_len || !status))) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA)
+        throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "lzss batch: coder must be bit, gamma or delta (ascii streams: tdc_lzss_sw_decode)"};
+    if (coder == TDC_GPU_CODER_BIT && window == 0) throw ArgError{TDC_GPU_ERR_ARG, "lzss: coder=bit needs the window (the width of the length field)"};
+    if (count > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzss batch: too many streams"};
+    for (size_t k = 0; k < count; ++k) {
+        if (s_off[k] + s_len[k] < s_off[k]) throw ArgError{TDC_GPU_ERR_ARG, "lzss batch: a stream's end overflows"};
+        if (s_len[k] && !streams) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    }
+}
+
+void lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                              uint32_t window, uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    Ctx& c = ctx->c;
+    ctx->last_decode_device = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    out_off[0] = 0;
+    if (count == 0) return;
+    // the part of `streams` the batch lies in, from the 4-byte border in front of its first byte on
+    u64 lo = ~0ull, hi = 0, bytes_in = 0;
+    for (size_t k = 0; k < count; ++k) {
+        if (!s_len[k]) continue;
+        lo = std::min<u64>(lo, s_off[k]); hi = std::max<u64>(hi, s_off[k] + s_len[k]);
+        bytes_in += s_len[k];
+    }
+    if (hi == 0) lo = 0;
+    const u64 sub = lo & ~3ull;
+    const size_t extent = (size_t)(hi - sub);
+    if (extent > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzss batch: the streams must lie within 2^32 - 2 bytes"};
+    const size_t slack = (size_t)16 << 20;
+    const size_t fixed = extent + 64 + 40 * (count + 1) + 8 * 256 + slack;
+    reserve_arena(c, fixed + 4 * extent);                         // (room for texts of four times the streams; more: the arena moves below)
+    Events ev(c);
+    const int e0 = ev.tick();
+    hipStream_t s = c.stream;
+    u8* d_blob = c.arena.get<u8>(extent + 64);
+    if (extent) HIP_TRY(hipMemcpyAsync(d_blob, streams + sub, extent, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_blob + extent, 0, 64, s));
+    u64* d_soff = c.arena.get<u64>(count), *d_slen = c.arena.get<u64>(count), *d_ooff = c.arena.get<u64>(count + 1);
+    u32* d_tlen = c.arena.get<u32>(count);
+    int* d_status = c.arena.get<int>(count);
+    u64* d_fac = c.arena.get<u64>(1);
+    HIP_TRY(hipMemcpyAsync(d_soff, s_off, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_slen, s_len, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    const int e1 = ev.tick();
+    const int kind = dec_kind(coder);
+    LzssSwBatchDec D;
+    D.blob = d_blob; D.sub = sub; D.s_off = d_soff; D.s_len = d_slen; D.tlen = d_tlen; D.status = d_status; D.ooff = d_ooff; D.factors = d_fac;
+    lzss_sw_batch_decode_sizes(c, kind, window, count, D);
+    c.read_n(d_ooff, (u64*)out_off, count + 1);
+    c.read_n(d_status, (int*)status, count);
+    const u64 factors = c.read(d_fac);
+    const int e2 = ev.tick();
+    const u64 total = out_off[count];
+    if (total > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lzss batch: the streams decode to more than 2^32 - 2 bytes in all"};
+    if (!out || total > out_cap) throw ArgError{TDC_GPU_ERR_OOM, "lzss batch: output buffer too small (out_off[count] holds the required size)"};
+    if (c.arena.size < c.arena.mark() + (size_t)total + 64 + 512 + slack) {
+        void* a = d_blob; void* b = d_soff; void* l = d_slen; void* o = d_ooff; void* t = d_tlen; void* v = d_status;
+        regrow_arena(c, fixed + (size_t)total + 1024, {{&a, extent + 64}, {&b, count * 8}, {&l, count * 8}, {&o, (count + 1) * 8}, {&t, count * 4}, {&v, count * 4}});
+        D.blob = (const u8*)a; D.s_off = (const u64*)b; D.s_len = (const u64*)l; D.ooff = (u64*)o; D.tlen = (u32*)t; D.status = (int*)v;
+    }
+    u8* d_text = c.arena.get<u8>((size_t)total + 64);
+    lzss_sw_batch_decode_write(c, kind, window, count, D, d_text);
+    const int e3 = ev.tick();
+    if (total) HIP_TRY(hipMemcpyAsync(out, d_text, (size_t)total, hipMemcpyDeviceToHost, s));
+    const int e4 = ev.tick();
+    if (stats) {
+        stats->n = bytes_in; stats->out_len = total; stats->factors = factors; stats->arena_bytes = c.arena.high;
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_d2h, e3, e4); ev.span(&stats->ms_total, e0, e4);
+    }
+    ev.finish();
+    ctx->last_decode_device = 1;
+}
+
 // RePairCompressor::decompress.  bit, gamma, delta: the device where decode_repair takes the stream, else -- and for ascii -- the host
 // loop that is its specification (tdc_repair_decode), whose status codes the call returns.
 void repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, tdc_gpu_stats* stats) {
@@ -205,6 +283,13 @@ int tdc_gpu_lzw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t 
 int tdc_gpu_lzss_sw_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t** out, size_t* out_len,
                                uint64_t* factors, uint32_t* rounds) {
     return guarded(ctx, [&] { lzss_sw_decompress(ctx, stream, len, coder, window, sink_malloc(out, out_len, "NULL argument"), factors, rounds); });
+}
+
+int tdc_gpu_lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                                     uint32_t window, uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    try { lzss_sw_batch_dec_check(streams, s_off, s_len, count, coder, window, out_off, status); }      // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { lzss_sw_decompress_batch(ctx, streams, s_off, s_len, count, coder, window, out, out_cap, out_off, status, stats); });
 }
 
 int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap,

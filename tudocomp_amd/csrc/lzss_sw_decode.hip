@@ -25,6 +25,7 @@
 #include "stages.hpp"
 #include "prim.hpp"
 #include "stream_parse.hpp"
+#include "lzss_sw_token.hpp"
 
 #include <stdio.h>
 #include <vector>
@@ -35,44 +36,10 @@ namespace {
 
 constexpr u64 SWD_TEXT_MAX = 0xFFFFFFFEull;
 constexpr u8 SWD_LIT = 0, SWD_FAC = 1, SWD_BAD = 2;               // class byte of a token
-// the device caps: most value bits of a distance or length and of a literal code, and of delta's width code in front of each (bits_for
-// of the former)
-constexpr u32 SWD_FIELD_BITS = 32, SWD_FIELD_WBITS = 6, SWD_LIT_BITS = 8, SWD_LIT_WBITS = 4;
-
-// The token that starts at bit x: 0 and its end, kind, distance, length or byte; < 0: no token (malformed, beyond a cap, or cut off by
-// the end of the stream).  k = bits_for(text position), lb = bits_for(window): the widths of the two fields of a factor under bit.
-template <int KIND, typename Win>
-__device__ __forceinline__ int swd_token(const Win& bw, u64 x, u64 total, u32 k, u32 lb, u64& end, u32& fac, u32& dist, u32& val) {
-    end = x; fac = 0; dist = 0; val = 0;
-    if (x >= total) return -1;
-    const u64 w = bw.peek(x);
-    fac = (u32)(w >> 63);
-    u64 y = x + 1;
-    u32 u;
-    if (KIND == DEC_BIT) {
-        if (!fac) { val = (u32)((w << 1) >> 56); y += 8; }
-        else {
-            dist = (u32)(bw.peek(y) >> (64 - k)); y += k;
-            val = (u32)(bw.peek(y) >> (64 - lb)); y += lb;
-        }
-    } else if (!fac) {
-        if (read_field<KIND>(bw, y, SWD_LIT_BITS, SWD_LIT_WBITS, u, val) != FIELD_READ) return -2;
-        y += u;
-    } else {
-        if (read_field<KIND>(bw, y, SWD_FIELD_BITS, SWD_FIELD_WBITS, u, dist) != FIELD_READ) return -2;
-        y += u;
-        if (read_field<KIND>(bw, y, SWD_FIELD_BITS, SWD_FIELD_WBITS, u, val) != FIELD_READ) return -2;
-        y += u;
-    }
-    if (y > total) return -3;
-    end = y;
-    return 0;
-}
-
 // what stream_next_kernel asks (stream_parse.hpp); a factor is the longer token
 template <int KIND>
 struct SwdTok {
-    static constexpr u32 REACH = 1 + (KIND == DEC_BIT ? 32 + 32 : 2 * field_span(KIND, SWD_FIELD_BITS, SWD_FIELD_WBITS));
+    static constexpr u32 REACH = swd_reach(KIND);
     u32 k, lb;
     template <typename Win>
     __device__ __forceinline__ bool at(const Win& bw, u64 x, u64& end) const {

@@ -282,6 +282,32 @@ bool decode_lzss_sw(Ctx& c, const u8* stream, size_t len, int kind, u32 window, 
 // the host loop behind tdc_lzss_sw_decode (lzss_sw_host.cpp): a status of tdc_gpu.h, the text
 int lzss_sw_decode_host(const u8* in, size_t len, int coder, u32 window, std::vector<u8>& text);
 
+// ---- lzss over a batch of independent texts (lzss_sw_batch.hip, DESIGN.md section 5.7 "Batches") -------------------------------------------
+// The texts lie back to back on the device, off[0 .. count] are their borders.  The caller provides the per-text arrays (24 bytes per
+// text); lzss_sw_batch_sizes fills the rest from the arena, where it stays valid until the caller releases its mark.
+struct LzssSwBatch {
+    const u32* off = nullptr;     // count + 1: text k = [off[k], off[k + 1])
+    u64* gfirst = nullptr;        // count + 1: the bit of text k's first token in the concatenated token stream; [count]: all bits
+    u64* ooff = nullptr;          // count + 1: the byte of stream k in the output, a multiple of 8; [count]: the bytes used
+    u32* flag = nullptr;          // count: 1 = BitCoder would truncate a length of this text; it takes no bytes of the output
+    size_t ntok = 0; u64 factors = 0;
+    const u32* tokpos = nullptr, *fac = nullptr; const u64* gpos = nullptr;
+};
+// match, parse, costs and the two scans: everything the output's size depends on (count >= 1; synchronises: token count, factor count)
+void lzss_sw_batch_sizes(Ctx& c, const u8* d_text, size_t n, size_t count, u32 window, u32 threshold, int kind, LzssSwBatch& B);
+// zeroes d_out[0, used), used = ooff[count], packs every token at its bit of its stream and writes the terminators; enqueued only
+void lzss_sw_batch_pack(Ctx& c, const u8* d_text, size_t count, u32 window, int kind, const LzssSwBatch& B, u8* d_out, size_t used);
+// Streams of kind 0 = BitCoder, 1 = EliasGammaCoder, 2 = EliasDeltaCoder, one wave per stream.  Stream k = blob[s_off[k] - sub, + s_len[k]),
+// the blob 4-byte aligned and padded with 64 zero bytes.  _sizes: tlen[k], status[k] (a status of tdc_gpu.h: what tdc_lzss_sw_decode
+// says of the stream), ooff[0 .. count] (the scan of tlen) and *factors; _write: the accepted texts into d_text + ooff[k].  Enqueued only.
+struct LzssSwBatchDec {
+    const u8* blob = nullptr; u64 sub = 0;
+    const u64* s_off = nullptr, *s_len = nullptr;
+    u32* tlen = nullptr; int* status = nullptr; u64* ooff = nullptr; u64* factors = nullptr;
+};
+void lzss_sw_batch_decode_sizes(Ctx& c, int kind, u32 window, size_t count, LzssSwBatchDec& D);
+void lzss_sw_batch_decode_write(Ctx& c, int kind, u32 window, size_t count, const LzssSwBatchDec& D, u8* d_text);
+
 // ---- repair (compressors/RePairCompressor.hpp; repair.hip, repair_host.cpp) ------------------------------------------
 constexpr size_t REPAIR_MAX_N = (size_t)1 << 30;
 // ms_first / ms_last / ms_tie: the first round, the last one and the sum over the tie rounds, on the host clock from one round's read-back

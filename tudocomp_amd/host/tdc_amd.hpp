@@ -558,6 +558,57 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
+    // Every text on its own, all of them in one device call (tdc_gpu_lzss_sw_compress_batch): streams[k] is what compress() writes for
+    // texts[k]; status[k] is TDC_GPU_ERR_UNSUPPORTED, and the stream empty, where coder=bit would truncate a length of text k.
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const size_t count = texts.size();
+        std::vector<uint64_t> in_off(count + 1, 0), out_off(count + 1, 0), out_len(count ? count : 1, 0);
+        for (size_t k = 0; k < count; ++k) in_off[k + 1] = in_off[k] + texts[k].size();
+        bytes in((size_t)in_off[count] ? (size_t)in_off[count] : 1);
+        for (size_t k = 0; k < count; ++k) std::copy(texts[k].begin(), texts[k].end(), in.begin() + (size_t)in_off[k]);
+        const uint32_t w = (uint32_t)m_window, t = (uint32_t)m_opts.get_int("threshold", 3);
+        bytes out(tdc_gpu_lzss_sw_batch_bound(in_off.data(), count, w, m_coder) + 8);
+        status.assign(count ? count : 1, 0);
+        const int rc = tdc_gpu_lzss_sw_compress_batch(m_ctx->h, in.data(), in_off.data(), count, w, t, m_coder, out.data(), out.size(), out_off.data(),
+                                                      out_len.data(), status.data(), &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        status.resize(count);
+        streams.clear();
+        for (size_t k = 0; k < count; ++k) streams.emplace_back(out.begin() + (size_t)out_off[k], out.begin() + (size_t)(out_off[k] + out_len[k]));
+    }
+    // The decoder of such a batch, on the device, one wave per stream (tdc_gpu_lzss_sw_decompress_batch; bit, gamma, delta -- coder=ascii
+    // loops the host decoder): status[k] is the host loop's verdict on streams[k] alone, a refused stream yields an empty text.
+    void decompress_batch(const std::vector<bytes>& streams, std::vector<bytes>& texts, std::vector<int32_t>& status) {
+        const size_t count = streams.size();
+        texts.assign(count, bytes());
+        status.assign(count, 0);
+        if (m_coder == TDC_GPU_CODER_ASCII) {
+            for (size_t k = 0; k < count; ++k) {
+                size_t n = 0;
+                status[k] = tdc_lzss_sw_decode(streams[k].data(), streams[k].size(), m_coder, (uint32_t)m_window, nullptr, 0, &n);
+                texts[k].resize(status[k] ? 0 : n);
+                if (!status[k] && n) status[k] = tdc_lzss_sw_decode(streams[k].data(), streams[k].size(), m_coder, (uint32_t)m_window, texts[k].data(), n, &n);
+            }
+            return;
+        }
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        std::vector<uint64_t> s_off(count ? count : 1, 0), s_len(count ? count : 1, 0), out_off(count + 1, 0);
+        size_t pos = 0;
+        for (size_t k = 0; k < count; ++k) { s_off[k] = pos; s_len[k] = streams[k].size(); pos += (streams[k].size() + 7) / 8 * 8; }
+        bytes blob(pos ? pos : 1);
+        for (size_t k = 0; k < count; ++k) std::copy(streams[k].begin(), streams[k].end(), blob.begin() + (size_t)s_off[k]);
+        status.assign(count ? count : 1, 0);
+        int rc = tdc_gpu_lzss_sw_decompress_batch(m_ctx->h, blob.data(), s_off.data(), s_len.data(), count, m_coder, (uint32_t)m_window, nullptr, 0,
+                                                  out_off.data(), status.data(), nullptr);                      // the sizes
+        bytes out((size_t)out_off[count] ? (size_t)out_off[count] : 1);
+        if (rc == TDC_GPU_ERR_OOM || rc == TDC_GPU_OK)
+            rc = tdc_gpu_lzss_sw_decompress_batch(m_ctx->h, blob.data(), s_off.data(), s_len.data(), count, m_coder, (uint32_t)m_window, out.data(), out.size(),
+                                                  out_off.data(), status.data(), &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        status.resize(count);
+        for (size_t k = 0; k < count; ++k) texts[k].assign(out.begin() + (size_t)out_off[k], out.begin() + (size_t)out_off[k + 1]);
+    }
     // :120-143 -- tokens until the stream ends: the host loop (tdc_lzss_sw_decode), which needs no device; dec=gpu (an addition, as for
     // lz78 / lzw): the device decoder (tdc_gpu_lzss_sw_decompress).  The stream is the same either way.  The window comes from the
     // algorithm id in the file's header (16 if it names none); only coder=bit needs it.
