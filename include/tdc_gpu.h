@@ -289,6 +289,12 @@ int tdc_gpu_prim_mark_orbit(tdc_gpu_ctx* ctx, const uint32_t* next, size_t n, ui
  * state o enters tile t + 1, 0xFFFF: it ends in t.  entry0[t] = the state in which the chain that enters tile 0 in state 0 enters
  * tile t, 0xFFFF behind its end.  Every exit must be < states or 0xFFFF (anything else is refused); at most 2^27 tiles */
 int tdc_gpu_prim_tile_entries(tdc_gpu_ctx* ctx, const uint16_t* exit0, size_t ntiles, uint32_t states, uint16_t* entry0);
+/* For tests/test_gpu_arena_state.py: what a call finds in the scratch arena.  byte 0..255: fill the whole arena [base, base + size) with
+ * it on the context's stream and synchronise; byte < 0: fill nothing; byte > 255: TDC_GPU_ERR_ARG.  Either way *base / *size report
+ * where the arena is and how large.  An arena that does not exist yet: *size = 0, nothing filled, status OK.  The allocation marks of
+ * the arena are not touched.  Not between tdc_gpu_lcpcomp_compress_keep and tdc_gpu_stream_fetch*: the kept stream lives in the arena
+ * (and, as after every call on the context, it is no longer there to fetch). */
+int tdc_gpu_prim_arena_fill(tdc_gpu_ctx* ctx, int byte, uint64_t* base, uint64_t* size);
 
 /* ---- LCPCompressor::decompress (LCPCompressor.hpp:140-150 -> decode_text_internal :23-76, HuffmanCoder::Decoder
  * coders/HuffmanCoder.hpp:572-612); lzss_lcp(coder=huff) streams have the same format (LZSSLCPCompressor.hpp:125-130).

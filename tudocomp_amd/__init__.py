@@ -840,6 +840,13 @@ class Context:
         self._check(self._L.tdc_gpu_prim_tile_entries(self._h, _ptr(a), ntiles, states, _ptr(entry)))
         return entry
 
+    def prim_arena_fill(self, byte=None):
+        """fill the whole scratch arena with `byte` (0 .. 255; None: fill nothing); returns (base, size), size 0 before the first
+        allocation.  For the tests: what a call finds in its scratch is the leftovers of the calls before it."""
+        base, size = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._L.tdc_gpu_prim_arena_fill(self._h, -1 if byte is None else int(byte), ctypes.byref(base), ctypes.byref(size)))
+        return base.value, size.value
+
     def suffix_array(self, text):
         a = _u8(text)
         sa = np.empty(len(a), dtype=np.uint32)

@@ -19,7 +19,7 @@ SYMBOLS = [
     "tdc_gpu_lz78_compress", "tdc_gpu_lzss_lcp_compress", "tdc_gpu_lzss_lcp_factorize",
     "tdc_gpu_sort_pairs_u64", "tdc_gpu_suffix_array", "tdc_gpu_textds", "tdc_gpu_lcpcomp_factorize", "tdc_gpu_flatten", "tdc_gpu_encode_huff",
     "tdc_gpu_prim_scan", "tdc_gpu_prim_sort_pairs", "tdc_gpu_prim_bucketed_scatter", "tdc_gpu_prim_msd_partition", "tdc_gpu_prim_select", "tdc_gpu_prim_select_counts",
-    "tdc_gpu_prim_mark_orbit", "tdc_gpu_prim_tile_entries",
+    "tdc_gpu_prim_mark_orbit", "tdc_gpu_prim_tile_entries", "tdc_gpu_prim_arena_fill",
     "tdc_gpu_lcpcomp_decompress",
     "tdc_gpu_lcpcomp_compress_comp",
     "tdc_gpu_encode_arith",
@@ -147,6 +147,7 @@ def load():
     L.tdc_gpu_prim_select_counts.argtypes = [vp, vp, ctypes.c_uint8, sz, vp, vp, u32, vp, ctypes.POINTER(u32)]
     L.tdc_gpu_prim_mark_orbit.argtypes = [vp, vp, sz, vp]
     L.tdc_gpu_prim_tile_entries.argtypes = [vp, vp, sz, u32, vp]
+    L.tdc_gpu_prim_arena_fill.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.tdc_gpu_suffix_array.argtypes = [vp, vp, sz, vp, vp]
     L.tdc_gpu_textds.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(u32)]
     L.tdc_gpu_lcpcomp_factorize.argtypes = [vp, vp, sz, u32, i32, pvp, pvp, pvp, psz, ctypes.POINTER(Stats)]

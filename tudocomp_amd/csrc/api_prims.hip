@@ -236,4 +236,19 @@ int tdc_gpu_prim_tile_entries(tdc_gpu_ctx* ctx, const uint16_t* exit0, size_t nt
     });
 }
 
+// Not a primitive: what the arena holds between two calls is chosen by the test (tests/test_gpu_arena_state.py).  top, top_hi and high
+// stay as the call before left them.
+int tdc_gpu_prim_arena_fill(tdc_gpu_ctx* ctx, int byte, uint64_t* base, uint64_t* size) {
+    return guarded(ctx, [&] {
+        if (!base || !size) bad("base/size is NULL");
+        if (byte > 255) bad("byte must be 0 .. 255, or negative to fill nothing");
+        Ctx& c = ctx->c;
+        *base = (uint64_t)(uintptr_t)c.arena.base;
+        *size = c.arena.base ? (uint64_t)c.arena.size : 0;
+        if (byte < 0 || *size == 0) return;
+        HIP_TRY(hipMemsetAsync(c.arena.base, byte, c.arena.size, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+    });
+}
+
 }  // extern "C"
