@@ -449,6 +449,49 @@ int tdc_gpu_lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, c
                                      uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */,
                                      int32_t* status /* count */, tdc_gpu_stats* stats);
 
+/* ---- lzw and lz78 over a batch: many independent texts in one call, PARSED ON THE DEVICE (lz_batch.hip, DESIGN.md section 5.4 "Batches").
+ * The single calls parse on the host, because the parse of one text is sequential; across texts the parses are independent, and here one
+ * wave takes one text.  The texts lie back to back in `in`: text k = in[in_off[k], in_off[k + 1]); in_off has count + 1 entries, does not
+ * decrease, and in_off[0] = 0.  Stream k = out[out_off[k], out_off[k] + out_len[k]) is byte for byte what tdc_gpu_lzw_compress /
+ * tdc_gpu_lz78_compress returns for text k alone with the same coder, the empty text (the terminator alone) included.  out_off[k] is a
+ * multiple of 8, out_off[count] the number of bytes used; the bytes between two streams are unspecified.  The call synchronises a constant
+ * number of times, whatever count is.
+ * coder: what the single calls take -- lzw: TDC_GPU_CODER_BIT or _GAMMA, lz78: TDC_GPU_CODER_GAMMA; anything else:
+ * TDC_GPU_ERR_UNSUPPORTED for the call.
+ * status[k]: TDC_GPU_OK, or the code of the single call on text k alone, with out_len[k] = 0 and no byte of `out` taken; the other texts
+ * are coded normally and the call returns TDC_GPU_OK.  lz78: TDC_GPU_ERR_UNSUPPORTED for a text whose left-over phrase ends in a byte
+ * >= 0x80 (the reference encodes it as a signed char).  Both: TDC_GPU_ERR_TOO_LARGE for a text of more than 2^25 - 256 = 33 554 176
+ * bytes -- the cap of ONE text in a batch (a table word holds the key in 33 bits and the id in 25); the single calls take such a text.
+ * The call itself: TDC_GPU_ERR_ARG for a NULL argument, in_off[0] != 0 or a decreasing in_off; TDC_GPU_ERR_UNSUPPORTED for the coder;
+ * TDC_GPU_ERR_TOO_LARGE for more than 2^32 - 2 bytes in all (these are decided from the arguments alone, before the context is looked
+ * at); TDC_GPU_ERR_OOM with the required size in out_off[count] if out_cap is too small -- decided from the sizes before anything is
+ * packed, nothing is written to `out` then -- or if the device cannot hold the arena: the tables take at most 32 bytes per text byte.
+ * count = 0 is valid and writes only out_off[0] = 0.
+ * Option of the context: lz_batch_hash_bits (tests; 0: the whole hash of a phrase picks its home slot in the table, k = 1 .. 24: only k
+ * bits of it do -- long probe runs, the same streams).
+ * stats (may be NULL): n (all input bytes), out_len (bytes used), factors (items summed over the accepted texts), ms_h2d, ms_factorize
+ * (the parse and the placement), ms_encode (the pack), ms_d2h, ms_total, arena_bytes.
+ * The streams are ordinary streams: tdc_lzw_decode, tdc_gpu_lzw_decompress and tdc_gpu_lz78_decompress read them one by one. */
+int tdc_gpu_lzw_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, int coder,
+                               uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
+                               int32_t* status /* count */, tdc_gpu_stats* stats);
+int tdc_gpu_lz78_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, int coder,
+                                uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
+                                int32_t* status /* count */, tdc_gpu_stats* stats);
+/* what `out` of the batch calls needs at most: per text of n bytes the stream of n items with every field at its widest for such a
+ * text -- lzw + bit: S(n) bits, the offset of code n; lzw + gamma: n (2 bits_for(n + 255) + 1); lz78: n (2 bits_for(n) + 1 + 17) --, its
+ * terminator (bits / 8 + 1 bytes, + 2 where bits mod 8 > 5), rounded up to 8; summed.  0 for a coder the call does not take, for offsets
+ * it refuses, or for more than 2^32 - 2 bytes in all. */
+size_t tdc_gpu_lzw_batch_bound(const uint64_t* in_off, size_t count, int coder);
+size_t tdc_gpu_lz78_batch_bound(const uint64_t* in_off, size_t count, int coder);
+/* The parse of such a batch alone, what tdc_lzw_factors (lzw != 0) / tdc_lz78_factors (lzw = 0) compute for every text on the host: the
+ * items of text k are items[item_off[k] .. item_off[k + 1]) -- lzw: the codes; lz78: the phrase ids, with their bytes in chars (NULL for
+ * lzw).  items and chars hold in_off[count] entries (a text has at most as many items as bytes), item_off count + 1.  status[k]:
+ * TDC_GPU_OK; TDC_GPU_ERR_UNSUPPORTED (lz78: the left-over byte is >= 0x80 -- the items are there all the same);
+ * TDC_GPU_ERR_TOO_LARGE (the text is beyond the cap: no items).  Arguments are refused as by the batch calls. */
+int tdc_gpu_lz_parse_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, int lzw,
+                           uint32_t* items /* n */, uint8_t* chars /* n */, uint64_t* item_off /* count + 1 */, int32_t* status /* count */);
+
 /* ---- repair: RePairCompressor<BitCoder | ASCIICoder | EliasGammaCoder | EliasDeltaCoder> (compressors/RePairCompressor.hpp:96-336;
  * DESIGN.md section 5.8): the Re-Pair grammar, built ON THE DEVICE.  No input restrictions (raw bytes, no sentinel).  Symbols are 32-bit:
  * 0 .. 255 are bytes, 256 + k is rule k; a rule is l << 32 | r.  Per round every adjacent pair of the live sequence is counted

@@ -254,6 +254,20 @@ def lzss_sw_batch_bound(lengths, window=16, coder=CODER_BIT):
     return _native.load().tdc_gpu_lzss_sw_batch_bound(_ptr(off), len(lengths), int(window), int(coder))
 
 
+def lzw_batch_bound(lengths, coder=CODER_BIT):
+    """what the output of lzw_compress_batch needs at most for texts of these lengths (0: a coder lzw does not take, or more than
+    2^32 - 2 bytes in all)"""
+    off = _offsets(lengths)
+    return _native.load().tdc_gpu_lzw_batch_bound(_ptr(off), len(lengths), int(coder))
+
+
+def lz78_batch_bound(lengths, coder=CODER_GAMMA):
+    """what the output of lz78_compress_batch needs at most for texts of these lengths (0: a coder lz78 does not take, or more than
+    2^32 - 2 bytes in all)"""
+    off = _offsets(lengths)
+    return _native.load().tdc_gpu_lz78_batch_bound(_ptr(off), len(lengths), int(coder))
+
+
 def repair_decode(data, coder=CODER_BIT):
     """RePairCompressor::decompress (:287-336) on the host, rules expanded with an explicit stack"""
     return _host_decode("tdc_repair_decode", data, int(coder))
@@ -591,6 +605,66 @@ class Context:
         out_off, out_len, status, st = self.lzss_sw_compress_batch_into(data, off, out, window, threshold, coder)
         streams = [out[int(o):int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
         return streams, status.tolist(), st
+
+    def _lz_compress_batch_into(self, name, data, in_off, out, coder):
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        count = len(off) - 1
+        out_off, out_len = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+        status, st = np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = getattr(self._L, "tdc_gpu_%s_compress_batch" % name)(self._h, _ptr(ta) if len(ta) else None, _ptr(off), count, int(coder), _ptr(oa),
+                                                                  oa.size, _ptr(out_off), _ptr(out_len), _ptr(status), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, int(out_off[count]))
+        return out_off, out_len[:count], status[:count], st.as_dict()
+
+    def _lz_compress_batch(self, name, bound, texts, coder):
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        out = np.empty(max(bound(lengths, coder), 8), dtype=np.uint8)
+        out_off, out_len, status, st = self._lz_compress_batch_into(name, data, _offsets(lengths), out, coder)
+        streams = [out[int(o):int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+        return streams, status.tolist(), st
+
+    def lzw_compress_batch_into(self, data, in_off, out, coder=CODER_BIT):
+        """tdc_gpu_lzw_compress_batch on caller-owned buffers: text k = data[in_off[k]:in_off[k + 1]] (in_off: count + 1 uint64), the
+        streams into `out` (PinnedBuffer or writable uint8 array; lzw_batch_bound sizes it).  The texts are parsed on the device, one wave
+        per text.  Returns (out_off, out_len, status, stats): stream k = out[out_off[k]:out_off[k] + out_len[k]], status[k] -4 for a text
+        beyond the cap of one text (2^25 - 256 bytes).  A buffer that is too small raises TdcGpuError (status -5) whose `required` is the
+        size."""
+        return self._lz_compress_batch_into("lzw", data, in_off, out, coder)
+
+    def lzw_compress_batch(self, texts, coder=CODER_BIT):
+        """lzw over many independent texts in one call: returns (list of streams, statuses, stats).  Stream k is what lzw_compress returns
+        for texts[k] alone; a refused text (statuses[k] != 0) yields b""."""
+        return self._lz_compress_batch("lzw", lzw_batch_bound, texts, coder)
+
+    def lz78_compress_batch_into(self, data, in_off, out, coder=CODER_GAMMA):
+        """tdc_gpu_lz78_compress_batch on caller-owned buffers, as lzw_compress_batch_into; status[k] is also -6 for a text whose
+        left-over phrase ends in a byte >= 0x80, the single call's refusal"""
+        return self._lz_compress_batch_into("lz78", data, in_off, out, coder)
+
+    def lz78_compress_batch(self, texts, coder=CODER_GAMMA):
+        """lz78 over many independent texts in one call: returns (list of streams, statuses, stats).  Stream k is what lz78_compress
+        returns for texts[k] alone; a refused text (statuses[k] -6 or -4) yields b""."""
+        return self._lz_compress_batch("lz78", lz78_batch_bound, texts, coder)
+
+    def lz_parse_batch(self, texts, lzw):
+        """the device parse of a batch alone: returns (items, chars, statuses) -- items[k]: the uint32 codes (lzw) or phrase ids (lz78)
+        of texts[k], what lzw_factors / lz78_factors compute on the host; chars[k]: the bytes of the lz78 pairs (None for lzw)"""
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        off = _offsets(lengths)
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        n, count = len(data), len(parts)
+        items, chars = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint8)
+        item_off, status = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.int32)
+        self._check(self._L.tdc_gpu_lz_parse_batch(self._h, _ptr(data) if n else None, _ptr(off), count, 1 if lzw else 0, _ptr(items),
+                                                   None if lzw else _ptr(chars), _ptr(item_off), _ptr(status)))
+        cut = [(int(a), int(b)) for a, b in zip(item_off[:-1], item_off[1:])]
+        return ([items[a:b].copy() for a, b in cut], None if lzw else [chars[a:b].tobytes() for a, b in cut], status[:count].tolist())
 
     def lzss_sw_decompress_batch_into(self, blob, s_off, s_len, out, coder, window=16):
         """tdc_gpu_lzss_sw_decompress_batch on caller-owned buffers: stream k = blob[s_off[k]:s_off[k] + s_len[k]], coder bit, gamma or
@@ -1239,6 +1313,12 @@ class LZ78Compressor:
         text, _ = self.ctx.lz78_decompress(stream)
         return text
 
+    def compress_batch(self, texts):
+        """every text on its own in one device call, parsed there: (list of streams, statuses); stream k is compress(texts[k])"""
+        out, status, st = self.ctx.lz78_compress_batch(texts, CODER_GAMMA)
+        self.last_stats = st
+        return out, status
+
 
 class LZWCompressor:
     """Mirror of tdc::LZWCompressor<coder, trie> (compressors/LZWCompressor.hpp:19-135); no input restrictions.  coder: bit (the
@@ -1266,6 +1346,12 @@ class LZWCompressor:
         if self.dec == "gpu":
             return self.ctx.lzw_decompress(stream, self.coder)[0]
         return lzw_decode(stream, self.coder)
+
+    def compress_batch(self, texts):
+        """every text on its own in one device call, parsed there: (list of streams, statuses); stream k is compress(texts[k])"""
+        out, status, st = self.ctx.lzw_compress_batch(texts, self.coder)
+        self.last_stats = st
+        return out, status
 
 
 class LZSSSlidingWindowCompressor:

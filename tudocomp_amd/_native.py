@@ -38,6 +38,7 @@ SYMBOLS = [
     "tdc_gpu_lzss_sw_compress", "tdc_gpu_lzss_sw_compress_into", "tdc_gpu_lzss_sw_bound", "tdc_gpu_lzss_sw_factorize", "tdc_lzss_sw_factors",
     "tdc_lzss_sw_decode", "tdc_gpu_lzss_sw_decompress", "tdc_gpu_lzss_sw_decompress_into",
     "tdc_gpu_lzss_sw_compress_batch", "tdc_gpu_lzss_sw_batch_bound", "tdc_gpu_lzss_sw_decompress_batch",
+    "tdc_gpu_lzw_compress_batch", "tdc_gpu_lzw_batch_bound", "tdc_gpu_lz78_compress_batch", "tdc_gpu_lz78_batch_bound", "tdc_gpu_lz_parse_batch",
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
     "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
 ]
@@ -211,6 +212,11 @@ def load():
     L.tdc_gpu_lzss_sw_batch_bound.argtypes = [vp, sz, u32, i32]
     L.tdc_gpu_lzss_sw_batch_bound.restype = sz
     L.tdc_gpu_lzss_sw_decompress_batch.argtypes = [vp, vp, vp, vp, sz, i32, u32, vp, sz, vp, vp, ctypes.POINTER(Stats)]
+    for name in ("lzw", "lz78"):
+        getattr(L, "tdc_gpu_%s_compress_batch" % name).argtypes = [vp, vp, vp, sz, i32, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]
+        getattr(L, "tdc_gpu_%s_batch_bound" % name).argtypes = [vp, sz, i32]
+        getattr(L, "tdc_gpu_%s_batch_bound" % name).restype = sz
+    L.tdc_gpu_lz_parse_batch.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp]
     L.tdc_gpu_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     L.tdc_gpu_option_count.argtypes = []
     L.tdc_gpu_option_name.argtypes = [i32]

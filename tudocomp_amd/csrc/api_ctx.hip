@@ -137,7 +137,8 @@ constexpr size_t NOPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
 // set is the one tests/test_gpu_parity.py::test_every_option_value_is_bit_exact walks; these are walked by tests/test_gpu_fused_candidates.py.
 // flatten_chunks (a schedule, not a fold) sits here for the same reason; tests/test_gpu_flatten_chunks.py walks it.  The repair_* switches
 // (a cross-check mode, a forced table size, a log, the device decoder's depth cap) belong to one compressor; tests/test_gpu_repair.py and
-// tests/test_gpu_repair_decode.py walk them.
+// tests/test_gpu_repair_decode.py walk them.  lz_batch_hash_bits (the batch parse's table under long probe runs) is walked by
+// tests/test_gpu_lz_batch.py.
 const OptionDef FOLD_OPTIONS[] = {
     { "fused_cand",       [](Ctx& c, long v) { c.fused_cand = v != 0; } },
     { "sel_tile_counts",  [](Ctx& c, long v) { c.sel_tile_counts = v != 0; } },
@@ -146,6 +147,7 @@ const OptionDef FOLD_OPTIONS[] = {
     { "repair_table_bits",[](Ctx& c, long v) { c.repair_table_bits = v == 0 ? 0 : clampi(v, 8, 30); } },
     { "repair_log",       [](Ctx& c, long v) { c.repair_log = v != 0; } },
     { "repair_dec_rounds",[](Ctx& c, long v) { c.repair_dec_rounds = clampi(v, 1, 1 << 24); } },
+    { "lz_batch_hash_bits",[](Ctx& c, long v) { c.lz_batch_hash_bits = clampi(v, 0, 24); } },
 };
 constexpr size_t NFOLD = sizeof(FOLD_OPTIONS) / sizeof(FOLD_OPTIONS[0]);
 const OptionDef* find_option(const char* name) {

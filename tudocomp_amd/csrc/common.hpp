@@ -213,6 +213,7 @@ struct Ctx {
     int repair_table_bits = 0;     // repair: 0 = the first capacity of the digram table comes from the text length; 8 .. 30 forces 2^bits slots (small texts reach the rebuild; tests)
     int repair_log = 0;            // repair: one line per round on stderr
     int repair_dec_rounds = 1024;  // repair, device decoder: most rounds of the length and of the first-occurrence pass; a grammar that needs more (a chain of rules) is decoded by the host loop
+    int lz_batch_hash_bits = 0;    // lzw / lz78 batches: 0 = the whole hash of a phrase picks its home slot; k = 1 .. 24: only k bits of it do (every node in 2^k homes, long probe runs; tests)
     int dec_log = 0, bwt_log = 0, pipe_log = 0, level_log = 0, wsort_log = 0, eager_dump = 0, small_prof = 0, arena_log = 0;   // diagnostics on stderr
 
     // overlapped D2H of the compressed stream (end-to-end entry point with a caller buffer): while the pack kernel works on the

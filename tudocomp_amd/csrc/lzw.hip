@@ -19,6 +19,7 @@
 #include "bitsink.hpp"
 #include "prim.hpp"
 #include "decode.hpp"
+#include "lzw_offsets.hpp"
 #include "../host/tdc_coders.hpp"
 
 #include <stdexcept>
@@ -28,21 +29,7 @@ namespace tdc {
 
 namespace {
 
-// bits in front of the first code of width w: sum_{v = 9}^{w - 1} v 2^(v - 1) = (w - 2) 2^(w - 1) - 1792  (256 codes of 9 bits, then
-// 2^(v - 1) codes of v bits: code k has width bits_for(k + 256))
-__host__ __device__ __forceinline__ u64 lzw_width_base(u32 w) { return ((u64)(w - 2) << (w - 1)) - 1792ull; }
-__host__ __device__ __forceinline__ u32 lzw_width(u64 k) { return 64u - (u32)__builtin_clzll(k + 256); }
-// S(k): the bit offset of code k
-__host__ __device__ __forceinline__ u64 lzw_offset(u64 k) {
-    const u32 w = lzw_width(k);
-    return lzw_width_base(w) + (k - ((1ull << (w - 1)) - 256)) * w;
-}
-// the code that holds bit x, and its width (the inverse of S; x < S(2^32))
-__host__ __device__ __forceinline__ u64 lzw_code_at(u64 x, u32& w) {
-    w = 9;
-    while (w < 40 && lzw_width_base(w + 1) <= x) ++w;
-    return ((1ull << (w - 1)) - 256) + (x - lzw_width_base(w)) / w;
-}
+// (S(k), its inverse and the widths: lzw_offsets.hpp)
 
 // output word j = stream bits [64 j, 64 j + 64): the codes that touch it, MSB first; zeros behind code z - 1
 __global__ __launch_bounds__(256) void lzw_bit_pack_kernel(const u32* __restrict__ codes, u64 z, u64* __restrict__ out, u64 words) {

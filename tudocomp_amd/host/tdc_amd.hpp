@@ -424,6 +424,26 @@ public:
     }
 };
 
+// lzw / lz78 over a batch (tdc_gpu_lzw_compress_batch, tdc_gpu_lz78_compress_batch): every text on its own, all of them parsed and coded
+// in one device call.  streams[k] is what compress() writes for texts[k]; where status[k] is not TDC_GPU_OK (the single call's refusal of
+// that text) the stream is empty.
+template <class Call, class Bound>
+inline void lz_compress_batch(tdc_gpu_ctx* h, Call call, Bound bound, int coder, const std::vector<bytes>& texts, std::vector<bytes>& streams,
+                              std::vector<int32_t>& status, tdc_gpu_stats* stats) {
+    const size_t count = texts.size();
+    std::vector<uint64_t> in_off(count + 1, 0), out_off(count + 1, 0), out_len(count ? count : 1, 0);
+    for (size_t k = 0; k < count; ++k) in_off[k + 1] = in_off[k] + texts[k].size();
+    bytes in((size_t)in_off[count] ? (size_t)in_off[count] : 1);
+    for (size_t k = 0; k < count; ++k) std::copy(texts[k].begin(), texts[k].end(), in.begin() + (size_t)in_off[k]);
+    bytes out(bound(in_off.data(), count, coder) + 8);
+    status.assign(count ? count : 1, 0);
+    const int rc = call(h, in.data(), in_off.data(), count, coder, out.data(), out.size(), out_off.data(), out_len.data(), status.data(), stats);
+    if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(h));
+    status.resize(count);
+    streams.clear();
+    for (size_t k = 0; k < count; ++k) streams.emplace_back(out.begin() + (size_t)out_off[k], out.begin() + (size_t)(out_off[k] + out_len[k]));
+}
+
 // tdc::LZ78Compressor<EliasGammaCoder, trie>  (compressors/LZ78Compressor.hpp:45-161): no input restrictions.
 class LZ78Compressor : public Compressor {
     AlgorithmValue m_opts;
@@ -445,6 +465,10 @@ public:
         if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
         output.write(out, out_len);
         tdc_gpu_free(out);
+    }
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        lz_compress_batch(m_ctx->h, tdc_gpu_lz78_compress_batch, tdc_gpu_lz78_batch_bound, TDC_GPU_CODER_GAMMA, texts, streams, status, &last_stats);
     }
     // LZ78Compressor::decompress (:142-160) with EliasGammaCoder::Decoder: pairs until BitIStream eof.
     // dec=gpu (an addition, as for lcpcomp): the stream is parsed and the phrases are expanded on the device (tdc_gpu_lz78_decompress);
@@ -505,6 +529,10 @@ public:
         if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
         output.write(out, out_len);
         tdc_gpu_free(out);
+    }
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        lz_compress_batch(m_ctx->h, tdc_gpu_lzw_compress_batch, tdc_gpu_lzw_batch_bound, m_coder, texts, streams, status, &last_stats);
     }
     // LZWCompressor::decompress (:110-133): the host loop of tdc_coders.hpp (lzw::decode_step restated), which needs no device;
     // dec=gpu (an addition, as for lz78): the device decoder (tdc_gpu_lzw_decompress).  The stream is the same either way.
