@@ -471,7 +471,8 @@ int tdc_gpu_lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, c
  * bits of it do -- long probe runs, the same streams).
  * stats (may be NULL): n (all input bytes), out_len (bytes used), factors (items summed over the accepted texts), ms_h2d, ms_factorize
  * (the parse and the placement), ms_encode (the pack), ms_d2h, ms_total, arena_bytes.
- * The streams are ordinary streams: tdc_lzw_decode, tdc_gpu_lzw_decompress and tdc_gpu_lz78_decompress read them one by one. */
+ * The batch decoders are tdc_gpu_lzw_decompress_batch / tdc_gpu_lz78_decompress_batch below; the streams are also ordinary streams for
+ * tdc_lzw_decode, tdc_gpu_lzw_decompress and tdc_gpu_lz78_decompress. */
 int tdc_gpu_lzw_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, int coder,
                                uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
                                int32_t* status /* count */, tdc_gpu_stats* stats);
@@ -491,6 +492,37 @@ size_t tdc_gpu_lz78_batch_bound(const uint64_t* in_off, size_t count, int coder)
  * TDC_GPU_ERR_TOO_LARGE (the text is beyond the cap: no items).  Arguments are refused as by the batch calls. */
 int tdc_gpu_lz_parse_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, int lzw,
                            uint32_t* items /* n */, uint8_t* chars /* n */, uint64_t* item_off /* count + 1 */, int32_t* status /* count */);
+
+/* The decoders of such batches, or of any collection of lzw / lz78 streams (lz_batch_decode.hip, DESIGN.md section 5.4 "Batch decoder").
+ * The arguments are those of tdc_gpu_lzss_sw_decompress_batch, one by one: stream k = streams[s_off[k], s_off[k] + s_len[k]) (any order,
+ * any alignment; together they must lie within 2^32 - 2 bytes), text k = out[out_off[k], out_off[k + 1]), the texts back to back; a
+ * refused stream contributes 0 bytes and disturbs no neighbour.  coder: lzw TDC_GPU_CODER_BIT or _GAMMA, lz78 _GAMMA; anything else is
+ * TDC_GPU_ERR_UNSUPPORTED for the call.  Always on the device -- option dec_parse is not consulted, no stream is too small -- and in ONE
+ * pass: the items of all streams form one forest of backward links, expanded as tdc_gpu_lzw_decompress expands one stream's; under
+ * coder=bit every code of every stream is read side by side from its closed-form offset.  The call synchronises a constant number of
+ * times (plus the pointer-jumping rounds, which depend on the deepest chain), whatever count is.
+ * status[k], lzw: the verdict of tdc_lzw_decode on stream k alone -- TDC_GPU_OK with the same bytes; TDC_GPU_ERR_ARG for a code j above
+ * 255 + j, a cut-off code, a cut-off terminator or a gamma field wider than 32 bits; TDC_GPU_ERR_TOO_LARGE for a text above 2^32 - 2
+ * bytes.  lz78: what tdc_gpu_lz78_decompress returns on stream k alone (the rules are stated there).  An item is counted from its OWN
+ * stream's first item: a code or id that a global count would allow -- the second stream of a batch opening with lzw code 256, or with
+ * the lz78 pair (1, c) -- is refused, and nothing in front of a stream's own text is reachable from it.  A stream that holds a bad item
+ * AND claims too much text is TDC_GPU_ERR_ARG: the device reads every item before it knows a length, as the single device decoders do
+ * (the host loop reports whichever comes first in the stream).
+ * out == NULL or out_cap too small: TDC_GPU_ERR_OOM with the required total in out_off[count] and all of out_off / status filled -- the
+ * sizes alone, so that a caller can size its buffer; nothing is written to `out`.  More than 2^32 - 2 bytes of text in all, or
+ * 2^32 - 258 items and more in all: TDC_GPU_ERR_TOO_LARGE for the call, before anything text-sized is allocated.  Decided from the
+ * arguments alone, before the context is looked at: TDC_GPU_ERR_ARG for a NULL s_off, s_len, out_off or status, a stream whose end
+ * overflows, streams == NULL with a non-empty stream; the coder.  count = 0 is valid and writes only out_off[0] = 0.
+ * stats (may be NULL): n (all stream bytes), out_len (all text bytes), factors (the items of the accepted streams), ms_h2d, ms_factorize
+ * (parse, lengths, starts and sizes, up to the read-back of out_off and status), ms_encode (literals, the resolver and -- the resolver
+ * hands the text over as it finishes -- its download; ms_d2h stays 0), ms_total, arena_bytes, len_rounds and flatten_rounds (the
+ * pointer-jumping rounds over the items and over the text). */
+int tdc_gpu_lzw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len,
+                                 size_t count, int coder, uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */,
+                                 int32_t* status /* count */, tdc_gpu_stats* stats);
+int tdc_gpu_lz78_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len,
+                                  size_t count, int coder, uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */,
+                                  int32_t* status /* count */, tdc_gpu_stats* stats);
 
 /* ---- repair: RePairCompressor<BitCoder | ASCIICoder | EliasGammaCoder | EliasDeltaCoder> (compressors/RePairCompressor.hpp:96-336;
  * DESIGN.md section 5.8): the Re-Pair grammar, built ON THE DEVICE.  No input restrictions (raw bytes, no sentinel).  Symbols are 32-bit:

@@ -713,6 +713,67 @@ class Context:
 
     lzss_sw_batch_bound = staticmethod(lzss_sw_batch_bound)
 
+    def _lz_decompress_batch_into(self, name, blob, s_off, s_len, out, coder):
+        ba = blob.a if isinstance(blob, PinnedBuffer) else _u8(blob)
+        oa = None if out is None else (out.a if isinstance(out, PinnedBuffer) else out)
+        so, sl = np.ascontiguousarray(s_off, dtype=np.uint64), np.ascontiguousarray(s_len, dtype=np.uint64)
+        count = len(so)
+        out_off, status, st = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = getattr(self._L, "tdc_gpu_%s_decompress_batch" % name)(self._h, _ptr(ba) if len(ba) else None, _ptr(so), _ptr(sl), count, int(coder),
+                                                                    None if oa is None else _ptr(oa), 0 if oa is None else oa.size,
+                                                                    _ptr(out_off), _ptr(status), ctypes.byref(st))
+        if rc:
+            err = TdcGpuError(rc, self._L.tdc_gpu_last_error(self._h).decode())
+            err.required = int(out_off[count]) if rc == -5 else None
+            err.out_off, err.statuses = out_off, status[:count]
+            raise err
+        return out_off, status[:count], st.as_dict()
+
+    def _lz_decompress_batch(self, name, streams, coder):
+        parts = [_u8(x) for x in streams]
+        s_len = np.array([len(a) for a in parts], dtype=np.uint64)
+        s_off = np.zeros(len(parts), dtype=np.uint64)
+        pos = 0
+        for k, a in enumerate(parts):                                 # every stream at a multiple of 8, as the compressor leaves them
+            s_off[k] = pos
+            pos += (len(a) + 7) & ~7
+        blob = np.zeros(pos, dtype=np.uint8)
+        for o, a in zip(s_off, parts):
+            blob[int(o):int(o) + len(a)] = a
+        try:
+            self._lz_decompress_batch_into(name, blob, s_off, s_len, None, coder)
+            need = 0
+        except TdcGpuError as e:
+            if e.status != -5:
+                raise
+            need = e.required
+        out = np.empty(max(need, 1), dtype=np.uint8)
+        out_off, status, st = self._lz_decompress_batch_into(name, blob, s_off, s_len, out, coder)
+        texts = [out[int(a):int(b)].tobytes() for a, b in zip(out_off[:-1], out_off[1:])]
+        return texts, status.tolist(), st
+
+    def lzw_decompress_batch_into(self, blob, s_off, s_len, out, coder=CODER_BIT):
+        """tdc_gpu_lzw_decompress_batch on caller-owned buffers: stream k = blob[s_off[k]:s_off[k] + s_len[k]], coder bit or gamma, always
+        on the device, all streams in one pass.  out: PinnedBuffer, writable uint8 array, or None for the sizes alone.  Returns (out_off,
+        status, stats): text k = out[out_off[k]:out_off[k + 1]], status[k] what lzw_decode says of stream k alone (0, -2, -4).  out None
+        or too small raises TdcGpuError (status -5) with `required`, `out_off` and `statuses` filled."""
+        return self._lz_decompress_batch_into("lzw", blob, s_off, s_len, out, coder)
+
+    def lzw_decompress_batch(self, streams, coder=CODER_BIT):
+        """the decoder of lzw_compress_batch, or of any list of lzw streams: returns (list of texts, statuses, stats); a refused stream
+        (status -2 or -4, as lzw_decode on it alone) yields b"" and disturbs no neighbour"""
+        return self._lz_decompress_batch("lzw", streams, coder)
+
+    def lz78_decompress_batch_into(self, blob, s_off, s_len, out, coder=CODER_GAMMA):
+        """tdc_gpu_lz78_decompress_batch on caller-owned buffers, as lzw_decompress_batch_into; status[k] is what lz78_decompress returns
+        for stream k alone"""
+        return self._lz_decompress_batch_into("lz78", blob, s_off, s_len, out, coder)
+
+    def lz78_decompress_batch(self, streams):
+        """the decoder of lz78_compress_batch, or of any list of lz78 streams: returns (list of texts, statuses, stats); a refused stream
+        yields b"" and disturbs no neighbour"""
+        return self._lz_decompress_batch("lz78", streams, CODER_GAMMA)
+
     def repair_compress(self, data, max_rules=0, coder=CODER_BIT):
         """RePairCompressor<coder>::compress on raw bytes (no escaping), the grammar built on the device; coder: CODER_BIT, _ASCII, _GAMMA
         or _DELTA.  Returns (stream, stats)."""
@@ -1319,6 +1380,12 @@ class LZ78Compressor:
         self.last_stats = st
         return out, status
 
+    def decompress_batch(self, streams):
+        """(list of texts, statuses) on the device, all streams in one pass; text k is decompress(streams[k]), b"" where it is refused"""
+        out, status, st = self.ctx.lz78_decompress_batch(streams)
+        self.last_stats = st
+        return out, status
+
 
 class LZWCompressor:
     """Mirror of tdc::LZWCompressor<coder, trie> (compressors/LZWCompressor.hpp:19-135); no input restrictions.  coder: bit (the
@@ -1350,6 +1417,13 @@ class LZWCompressor:
     def compress_batch(self, texts):
         """every text on its own in one device call, parsed there: (list of streams, statuses); stream k is compress(texts[k])"""
         out, status, st = self.ctx.lzw_compress_batch(texts, self.coder)
+        self.last_stats = st
+        return out, status
+
+    def decompress_batch(self, streams):
+        """(list of texts, statuses) on the device, all streams in one pass, whatever dec says; text k is decompress(streams[k]), b""
+        where it is refused"""
+        out, status, st = self.ctx.lzw_decompress_batch(streams, self.coder)
         self.last_stats = st
         return out, status
 

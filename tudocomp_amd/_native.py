@@ -39,6 +39,7 @@ SYMBOLS = [
     "tdc_lzss_sw_decode", "tdc_gpu_lzss_sw_decompress", "tdc_gpu_lzss_sw_decompress_into",
     "tdc_gpu_lzss_sw_compress_batch", "tdc_gpu_lzss_sw_batch_bound", "tdc_gpu_lzss_sw_decompress_batch",
     "tdc_gpu_lzw_compress_batch", "tdc_gpu_lzw_batch_bound", "tdc_gpu_lz78_compress_batch", "tdc_gpu_lz78_batch_bound", "tdc_gpu_lz_parse_batch",
+    "tdc_gpu_lzw_decompress_batch", "tdc_gpu_lz78_decompress_batch",
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
     "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
 ]
@@ -216,6 +217,7 @@ def load():
         getattr(L, "tdc_gpu_%s_compress_batch" % name).argtypes = [vp, vp, vp, sz, i32, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]
         getattr(L, "tdc_gpu_%s_batch_bound" % name).argtypes = [vp, sz, i32]
         getattr(L, "tdc_gpu_%s_batch_bound" % name).restype = sz
+        getattr(L, "tdc_gpu_%s_decompress_batch" % name).argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, vp, vp, ctypes.POINTER(Stats)]
     L.tdc_gpu_lz_parse_batch.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp]
     L.tdc_gpu_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     L.tdc_gpu_option_count.argtypes = []

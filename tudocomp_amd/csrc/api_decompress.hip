@@ -195,6 +195,123 @@ void lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const ui
     ctx->last_decode_device = 1;
 }
 
+// ---- lzw / lz78 streams in a batch (lz_batch_decode.hip): one forest of items, one pass, never the host loop -------------------------
+void lz_batch_dec_check(bool lzw, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                        const uint64_t* out_off, const int32_t* status) {
+    if (!out_off || (count && (!s_off || !s_len || !status))) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (lzw ? (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA) : coder != TDC_GPU_CODER_GAMMA)
+        throw ArgError{TDC_GPU_ERR_UNSUPPORTED, lzw ? "lzw batch: only coder=bit and coder=gamma are built" : "lz78 batch: only coder=gamma is built"};
+    if (count > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lz batch: too many streams"};
+    for (size_t k = 0; k < count; ++k) {
+        if (s_off[k] + s_len[k] < s_off[k]) throw ArgError{TDC_GPU_ERR_ARG, "lz batch: a stream's end overflows"};
+        if (s_len[k] && !streams) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    }
+}
+
+void lz_decompress_batch(tdc_gpu_ctx* ctx, bool lzw, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                         uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    Ctx& c = ctx->c;
+    ctx->last_decode_device = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    out_off[0] = 0;
+    if (count == 0) return;
+    const bool bit = coder == TDC_GPU_CODER_BIT;
+    // the part of `streams` the batch lies in, from the 4-byte border in front of its first byte on
+    u64 lo = ~0ull, hi = 0, bytes_in = 0;
+    for (size_t k = 0; k < count; ++k) {
+        if (!s_len[k]) continue;
+        lo = std::min<u64>(lo, s_off[k]); hi = std::max<u64>(hi, s_off[k] + s_len[k]);
+        bytes_in += s_len[k];
+    }
+    if (hi == 0) lo = 0;
+    const u64 sub = lo & ~3ull;
+    const size_t extent = (size_t)(hi - sub);
+    if (extent > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lz batch: the streams must lie within 2^32 - 2 bytes"};
+    const size_t slack = (size_t)16 << 20;
+    const size_t fixed = extent + 64 + 48 * (count + 1) + 12 * 256 + slack;
+    const size_t per_item = 38, per_byte = 5;                     // ids, chars, owner, J, S, the factor list, lit | text, d_ref, the done bits
+    reserve_arena(c, fixed + 40 * extent);                        // (room for the items and the texts of most batches; more: the arena moves below)
+    Events ev(c);
+    const int e0 = ev.tick();
+    hipStream_t s = c.stream;
+    u8* d_blob = c.arena.get<u8>(extent + 64);
+    if (extent) HIP_TRY(hipMemcpyAsync(d_blob, streams + sub, extent, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_blob + extent, 0, 64, s));
+    u64* d_soff = c.arena.get<u64>(count), *d_slen = c.arena.get<u64>(count), *d_bits = c.arena.get<u64>(count);
+    u64* d_ioff = c.arena.get<u64>(count + 1), *d_ooff = c.arena.get<u64>(count + 1);
+    int* d_status = c.arena.get<int>(count);
+    u64* d_fac = c.arena.get<u64>(1);
+    HIP_TRY(hipMemcpyAsync(d_soff, s_off, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_slen, s_len, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    const int e1 = ev.tick();
+    LzBatchDec D;
+    D.blob = d_blob; D.sub = sub; D.s_off = d_soff; D.s_len = d_slen; D.bits = d_bits; D.status = d_status; D.item_off = d_ioff; D.ooff = d_ooff;
+    D.factors = d_fac;
+    lz_batch_decode_count(c, lzw, bit, count, D);
+    // the one number the arena's size depends on (gamma: no array may hold an entry per stream bit, so the items are counted first)
+    const u64 z = c.read(d_ioff + count);
+    if (z >= 0xFFFFFFFEull - 256) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lz batch: the streams hold 2^32 - 258 items or more in all"};
+    u64 factors = 0;
+    u32 len_rounds = 0, ref_rounds = 0;
+    LzBatchItems I;
+    I.z = (size_t)z;
+    size_t mk_items = 0;
+    if (z == 0) {                                                 // no item anywhere: every text is empty, the verdicts are the bits kernel's
+        HIP_TRY(hipMemsetAsync(d_ooff, 0, (count + 1) * sizeof(u64), s));
+    } else {
+        if (c.arena.size < c.arena.mark() + per_item * (size_t)z + per_byte * extent + slack) {
+            void* a = d_blob; void* b = d_soff; void* l = d_slen; void* t = d_bits; void* i = d_ioff; void* o = d_ooff; void* v = d_status; void* f = d_fac;
+            regrow_arena(c, fixed + per_item * (size_t)z + 4 * per_byte * extent + 4096,
+                         {{&a, extent + 64}, {&b, count * 8}, {&l, count * 8}, {&t, count * 8}, {&i, (count + 1) * 8}, {&o, (count + 1) * 8}, {&v, count * 4}, {&f, 8}});
+            D.blob = (const u8*)a; D.s_off = (const u64*)b; D.s_len = (const u64*)l; D.bits = (u64*)t; D.item_off = (u64*)i; D.ooff = (u64*)o;
+            D.status = (int*)v; D.factors = (u64*)f;
+        }
+        I.fpos = c.arena.get<u32>(I.z); I.fsrc = c.arena.get<u32>(I.z); I.flen = c.arena.get<u32>(I.z); I.lit = c.arena.get<u8>(I.z + 64);
+        mk_items = c.arena.mark();                                // (what lies above lives until the factor list is made)
+        I.ids = c.arena.get<u32>(I.z); I.owner = c.arena.get<u32>(I.z); I.J = c.arena.get<u64>(I.z); I.S = c.arena.get<u64>(I.z + 1);
+        I.chars = lzw ? nullptr : c.arena.get<u8>(I.z + 64);
+        u32* d_cnt = c.arena.get<u32>(2);
+        len_rounds = lz_batch_decode_sizes(c, lzw, bit, count, D, I, d_cnt);
+    }
+    // the one round of read-backs every decision below rests on
+    c.read_n(D.ooff, (u64*)out_off, count + 1);
+    c.read_n(D.status, (int*)status, count);
+    if (z) factors = c.read(D.factors);
+    const int e2 = ev.tick();
+    const u64 total = out_off[count];
+    if (total > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "lz batch: the streams decode to more than 2^32 - 2 bytes in all"};
+    if (!out || total > out_cap) throw ArgError{TDC_GPU_ERR_OOM, "lz batch: output buffer too small (out_off[count] holds the required size)"};
+    int e3 = e2;
+    if (total) {
+        c.arena.release(mk_items);
+        const size_t text_need = (size_t)total * per_byte + (size_t)total / 8 + 4096 + slack;
+        if (c.arena.size < c.arena.mark() + text_need) {
+            void* p = I.fpos; void* q = I.fsrc; void* l = I.flen; void* t = I.lit;
+            regrow_arena(c, fixed + 13 * I.z + text_need, {{&p, I.z * 4}, {&q, I.z * 4}, {&l, I.z * 4}, {&t, I.z}});
+            I.fpos = (u32*)p; I.fsrc = (u32*)q; I.flen = (u32*)l; I.lit = (u8*)t;
+        }
+        u32* d_cnt = c.arena.get<u32>(2);
+        u8* d_text = c.arena.get<u8>((size_t)total + 64);
+        u32* d_ref = c.arena.get<u32>((size_t)total);
+        lz_batch_decode_literals(c, lzw, I, d_text);
+        Sink sink;
+        size_t written = 0;
+        sink.into = out; sink.cap = out_cap; sink.out_len = &written;
+        DecodeStats ds;
+        resolve_and_download(c, (size_t)total, d_text, d_ref, I.fpos, I.fsrc, I.flen, I.z, d_cnt, sink, &ds);
+        ref_rounds = ds.rounds;
+        e3 = ev.tick();
+    }
+    if (stats) {
+        stats->n = bytes_in; stats->out_len = total; stats->factors = factors; stats->arena_bytes = c.arena.high;
+        stats->len_rounds = len_rounds; stats->flatten_rounds = ref_rounds;
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_total, e0, e3);
+    }
+    ev.finish();
+    ctx->last_decode_device = 1;
+}
+
 // RePairCompressor::decompress.  bit, gamma, delta: the device where decode_repair takes the stream, else -- and for ascii -- the host
 // loop that is its specification (tdc_repair_decode), whose status codes the call returns.
 void repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, Sink s, tdc_gpu_stats* stats) {
@@ -290,6 +407,20 @@ int tdc_gpu_lzss_sw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, c
     try { lzss_sw_batch_dec_check(streams, s_off, s_len, count, coder, window, out_off, status); }      // (before the context: no device needed)
     catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
     return guarded(ctx, [&] { lzss_sw_decompress_batch(ctx, streams, s_off, s_len, count, coder, window, out, out_cap, out_off, status, stats); });
+}
+
+int tdc_gpu_lzw_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                                 uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    try { lz_batch_dec_check(true, streams, s_off, s_len, count, coder, out_off, status); }             // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { lz_decompress_batch(ctx, true, streams, s_off, s_len, count, coder, out, out_cap, out_off, status, stats); });
+}
+
+int tdc_gpu_lz78_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                                  uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    try { lz_batch_dec_check(false, streams, s_off, s_len, count, coder, out_off, status); }
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { lz_decompress_batch(ctx, false, streams, s_off, s_len, count, coder, out, out_cap, out_off, status, stats); });
 }
 
 int tdc_gpu_lzss_sw_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint32_t window, uint8_t* out, size_t out_cap,

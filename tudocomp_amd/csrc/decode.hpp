@@ -128,5 +128,10 @@ size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, s
 // out.into is too small.  ids / chars lie in the arena, nothing above them is live.
 size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
                       const DecTick& tick);
+// The first stage of expand_phrases alone, for any forest of links that point backwards (the batch of lz_batch_decode.hip: the items of
+// many streams with their links rebased): J[k] = NONE32 << 32 | len_k for z >= 1 items, where ids[k] >= base links item k to item
+// ids[k] - base (base: 1 for LZ78 ids, 256 for LZW codes) and a smaller value links nowhere.  d_changed: one word.  Returns the number
+// of pointer-jumping rounds; it synchronises once per round.
+u32 phrase_lengths(Ctx& c, const u32* ids, size_t z, u32 base, u64* J, u32* d_changed);
 
 }  // namespace tdc

@@ -25,40 +25,22 @@
 #include "stages.hpp"
 #include "prim.hpp"
 #include "stream_parse.hpp"
+#include "lz_pair.hpp"
 
 namespace tdc {
 
 namespace {
 
-constexpr u32 LZD_ID_BITS = 32, LZD_CHAR_BITS = 64;               // most value bits of the id field (a factorid_t) and of the char field
 #ifndef TDC_LZD_HOPS
 #define TDC_LZD_HOPS 16
 #endif
 
-// The pair that starts at bit x (read_elias_gamma<u32>, read_elias_gamma<u8>): 0 and its end, id and char; < 0: no pair there.
-// NV == 1: the item is the first code alone.
-template <int NV, typename Win>
-__device__ __forceinline__ int lz_pair(const Win& bw, u64 x, u64 total, u64& end, u32& id, u32& ch) {
-    end = x; ch = 0;
-    u32 used;
-    if (read_field<DEC_GAMMA>(bw, x, LZD_ID_BITS, 0u, used, id) != FIELD_READ) return -1;     // (zeros up to the end, or wider than a factorid_t)
-    const u64 y = x + used;
-    if (NV == 1) { end = y; return end > total ? -3 : 0; }
-    const u64 v = bw.peek(y);
-    u32 b2;
-    if (v) b2 = (u32)__builtin_clzll(v);
-    else if (bw.peek(y + 64) >> 63) b2 = 64;                      // a sign-extended 64-bit char (the reference's left-over phrase)
-    else return -2;
-    end = y + 2 * (u64)b2 + 1;
-    if (end > total) return -3;                                   // cut off by the end of the stream
-    if (b2) { const u32 k = b2 < 8 ? b2 : 8; ch = (u32)(bw.peek(end - k) >> (64 - k)); }     // the low 8 bits of the value
-    return 0;
-}
+// (the item reader lz_pair<NV>: lz_pair.hpp)
 
 // what stream_next_kernel asks (stream_parse.hpp)
 template <int NV>
 struct LzTok {
-    static constexpr u32 REACH = field_span(DEC_GAMMA, LZD_ID_BITS, 0) + (NV == 2 ? 2 * LZD_CHAR_BITS + 1 : 0);
+    static constexpr u32 REACH = lz_pair_reach<NV>();
     template <typename Win>
     __device__ __forceinline__ bool at(const Win& bw, u64 x, u64& end) const {
         u32 id, ch;
@@ -192,6 +174,23 @@ size_t parse_gamma_items(Ctx& c, const u32* s32, u64 total, int nv, u32 slack, s
     return nv == 2 ? parse_items<2>(c, s32, total, slack, zcap, ids, chars, tick) : parse_items<1>(c, s32, total, slack, zcap, ids, chars, tick);
 }
 
+u32 phrase_lengths(Ctx& c, const u32* ids, size_t z, u32 base, u64* J, u32* d_changed) {
+    hipStream_t s = c.stream;
+    lz_link_kernel<<<dec_grid(z), 256, 0, s>>>(ids, z, base, J);
+    LAUNCH_CHECK();
+    unsigned g = cdiv(z, 256 * 8); if (g > 16384) g = 16384;
+    u32 len_rounds = 0;
+    for (u32 round = 0;; ++round) {
+        if (round > 40) throw HipError{hipErrorUnknown, "phrase lengths did not converge", (int)__LINE__};   // depth < 2^32
+        HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(u32), s));
+        lz_len_jump_kernel<<<g, 256, 0, s>>>(J, z, d_changed);
+        LAUNCH_CHECK();
+        len_rounds = round + 1;
+        if (c.read(d_changed) == 0) break;
+    }
+    return len_rounds;
+}
+
 size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const char* who, Sink& out, size_t* need, DecodeStats* st,
                       const DecTick& tick) {
     hipStream_t s = c.stream;
@@ -213,18 +212,7 @@ size_t expand_phrases(Ctx& c, u32* ids, u8* chars, size_t z, bool lzw, const cha
     u64* J = c.arena.get<u64>(z);
     u64* S = c.arena.get<u64>(z);
     u64* d_total = c.arena.get<u64>(1);
-    lz_link_kernel<<<dec_grid(z), 256, 0, s>>>(ids, z, lzw ? 256u : 1u, J);
-    LAUNCH_CHECK();
-    unsigned g = cdiv(z, 256 * 8); if (g > 16384) g = 16384;
-    u32 len_rounds = 0;
-    for (u32 round = 0;; ++round) {
-        if (round > 40) throw HipError{hipErrorUnknown, "phrase lengths did not converge", (int)__LINE__};   // depth < 2^32
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(u32), s));
-        lz_len_jump_kernel<<<g, 256, 0, s>>>(J, z, d_cnt);
-        LAUNCH_CHECK();
-        len_rounds = round + 1;
-        if (c.read(d_cnt) == 0) break;
-    }
+    const u32 len_rounds = phrase_lengths(c, ids, z, lzw ? 256u : 1u, J, d_cnt);
     lz_len_kernel<<<dec_grid(z), 256, 0, s>>>(J, z, S);
     LAUNCH_CHECK();
     exclusive_sum_u64(c, S, S, z, d_total);

@@ -1,6 +1,6 @@
 // lzw_offsets.hpp -- lzw(coder=bit): code k is written with bits_for(k + 256) bits (Coder.hpp:61-63), a width that depends on k alone, so
 // the bit offset S(k) of every code is a closed form and so is its inverse.  Shared by the single call (lzw.hip) and the batch
-// (lz_batch.hip).
+// (lz_batch.hip) and its decoder (lz_batch_decode.hip).
 #pragma once
 
 #include "common.hpp"

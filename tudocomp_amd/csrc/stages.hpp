@@ -308,6 +308,35 @@ struct LzssSwBatchDec {
 void lzss_sw_batch_decode_sizes(Ctx& c, int kind, u32 window, size_t count, LzssSwBatchDec& D);
 void lzss_sw_batch_decode_write(Ctx& c, int kind, u32 window, size_t count, const LzssSwBatchDec& D, u8* d_text);
 
+// ---- lzw / lz78 streams in a batch (lz_batch_decode.hip, DESIGN.md section 5.4 "Batch decoder") ----------------------------------------------
+// Stream k = blob[s_off[k] - sub, + s_len[k]), the blob 4-byte aligned and padded with 64 zero bytes.  The items of all streams lie back
+// to back (stream k: item_off[k] .. item_off[k + 1]) with their links rebased to global item indices: one forest, whose text is the
+// texts back to back.  The caller provides every array; all three functions only enqueue, but for the pointer-jumping rounds of _sizes.
+struct LzBatchDec {
+    const u8* blob = nullptr; u64 sub = 0;
+    const u64* s_off = nullptr, *s_len = nullptr;
+    u64* bits = nullptr;          // count: the payload bits of stream k
+    int* status = nullptr;        // count: a status of tdc_gpu.h
+    u64* item_off = nullptr;      // count + 1: the item counts, then their scan; [count]: all items
+    u64* ooff = nullptr;          // count + 1: the scan of the accepted text lengths
+    u64* factors = nullptr;       // 1: the items of the accepted streams
+};
+// The items of one batch (z = item_off[count] of them).  ids / chars / owner / J / S (z + 1) are scratch of the length stages; fpos, fsrc,
+// flen and lit are what the text is made of: the factor list for resolve_and_download and the literal of every item.
+struct LzBatchItems {
+    size_t z = 0;
+    u32* ids = nullptr; u8* chars = nullptr; u32* owner = nullptr; u64* J = nullptr, *S = nullptr;
+    u32* fpos = nullptr, *fsrc = nullptr, *flen = nullptr; u8* lit = nullptr;
+};
+// bits, the verdicts that need no item (a cut-off terminator; bit: a cut-off code), the item count of every stream -- bit: from the closed
+// form, gamma: by the first walk, one wave per stream -- and item_off
+void lz_batch_decode_count(Ctx& c, bool lzw, bool bit, size_t count, LzBatchDec& D);
+// the items at item_off[k] + j, links rebased (bit: one thread per code of the batch; gamma: the second walk); lengths, starts, the
+// per-stream sums and verdicts, ooff, *factors, and the factor list.  z >= 1.  Returns the pointer-jumping rounds.
+u32 lz_batch_decode_sizes(Ctx& c, bool lzw, bool bit, size_t count, LzBatchDec& D, LzBatchItems& I, u32* d_changed);
+// the literals of the accepted streams at their text positions
+void lz_batch_decode_literals(Ctx& c, bool lzw, const LzBatchItems& I, u8* d_text);
+
 // ---- repair (compressors/RePairCompressor.hpp; repair.hip, repair_host.cpp) ------------------------------------------
 constexpr size_t REPAIR_MAX_N = (size_t)1 << 30;
 // ms_first / ms_last / ms_tie: the first round, the last one and the sum over the tie rounds, on the host clock from one round's read-back

@@ -444,6 +444,28 @@ inline void lz_compress_batch(tdc_gpu_ctx* h, Call call, Bound bound, int coder,
     for (size_t k = 0; k < count; ++k) streams.emplace_back(out.begin() + (size_t)out_off[k], out.begin() + (size_t)(out_off[k] + out_len[k]));
 }
 
+// The decoders of such batches (tdc_gpu_lzw_decompress_batch, tdc_gpu_lz78_decompress_batch): all streams in one pass on the device, the
+// sizes first, then the call.  status[k] is the single decoder's verdict on streams[k] alone, a refused stream yields an empty text.
+template <class Call>
+inline void lz_decompress_batch(tdc_gpu_ctx* h, Call call, int coder, const std::vector<bytes>& streams, std::vector<bytes>& texts,
+                                std::vector<int32_t>& status, tdc_gpu_stats* stats) {
+    const size_t count = streams.size();
+    texts.assign(count, bytes());
+    std::vector<uint64_t> s_off(count ? count : 1, 0), s_len(count ? count : 1, 0), out_off(count + 1, 0);
+    size_t pos = 0;
+    for (size_t k = 0; k < count; ++k) { s_off[k] = pos; s_len[k] = streams[k].size(); pos += (streams[k].size() + 7) / 8 * 8; }
+    bytes blob(pos ? pos : 1);
+    for (size_t k = 0; k < count; ++k) std::copy(streams[k].begin(), streams[k].end(), blob.begin() + (size_t)s_off[k]);
+    status.assign(count ? count : 1, 0);
+    int rc = call(h, blob.data(), s_off.data(), s_len.data(), count, coder, nullptr, 0, out_off.data(), status.data(), nullptr);      // the sizes
+    bytes out((size_t)out_off[count] ? (size_t)out_off[count] : 1);
+    if (rc == TDC_GPU_ERR_OOM || rc == TDC_GPU_OK)
+        rc = call(h, blob.data(), s_off.data(), s_len.data(), count, coder, out.data(), out.size(), out_off.data(), status.data(), stats);
+    if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(h));
+    status.resize(count);
+    for (size_t k = 0; k < count; ++k) texts[k].assign(out.begin() + (size_t)out_off[k], out.begin() + (size_t)out_off[k + 1]);
+}
+
 // tdc::LZ78Compressor<EliasGammaCoder, trie>  (compressors/LZ78Compressor.hpp:45-161): no input restrictions.
 class LZ78Compressor : public Compressor {
     AlgorithmValue m_opts;
@@ -469,6 +491,10 @@ public:
     void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
         if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
         lz_compress_batch(m_ctx->h, tdc_gpu_lz78_compress_batch, tdc_gpu_lz78_batch_bound, TDC_GPU_CODER_GAMMA, texts, streams, status, &last_stats);
+    }
+    void decompress_batch(const std::vector<bytes>& streams, std::vector<bytes>& texts, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        lz_decompress_batch(m_ctx->h, tdc_gpu_lz78_decompress_batch, TDC_GPU_CODER_GAMMA, streams, texts, status, &last_stats);
     }
     // LZ78Compressor::decompress (:142-160) with EliasGammaCoder::Decoder: pairs until BitIStream eof.
     // dec=gpu (an addition, as for lcpcomp): the stream is parsed and the phrases are expanded on the device (tdc_gpu_lz78_decompress);
@@ -533,6 +559,10 @@ public:
     void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
         if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
         lz_compress_batch(m_ctx->h, tdc_gpu_lzw_compress_batch, tdc_gpu_lzw_batch_bound, m_coder, texts, streams, status, &last_stats);
+    }
+    void decompress_batch(const std::vector<bytes>& streams, std::vector<bytes>& texts, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        lz_decompress_batch(m_ctx->h, tdc_gpu_lzw_decompress_batch, m_coder, streams, texts, status, &last_stats);
     }
     // LZWCompressor::decompress (:110-133): the host loop of tdc_coders.hpp (lzw::decode_step restated), which needs no device;
     // dec=gpu (an addition, as for lz78): the device decoder (tdc_gpu_lzw_decompress).  The stream is the same either way.
