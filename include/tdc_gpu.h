@@ -552,6 +552,46 @@ size_t tdc_gpu_repair_bound(size_t n, int coder);
  * tdc_repair_grammar computes on the host.  stats (may be NULL): the repair fields and ms_factorize. */
 int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64_t max_rules, uint64_t** rules, size_t* nrules,
                            uint32_t** start, size_t* nstart, tdc_gpu_stats* stats);
+/* ---- repair over a batch: many independent texts in one call, ONE WORKGROUP PER GRAMMAR (repair_batch.hip, DESIGN.md section 5.8
+ * "Batches").  The single call is a host-driven loop with a read-back per rule; across texts the grammars are independent, and here one
+ * workgroup runs the whole round loop of one text on the device.  The texts lie back to back in `in`: text k = in[in_off[k], in_off[k + 1]);
+ * in_off has count + 1 entries, does not decrease, and in_off[0] = 0.  Stream k = out[out_off[k], out_off[k] + out_len[k]) is byte for byte
+ * what tdc_gpu_repair_compress returns for text k alone with the same max_rules and coder, the empty text included; no pair spans a
+ * border.  out_off[k] is a multiple of 8, out_off[count] the number of bytes used; the bytes between two streams are unspecified.
+ * coder: TDC_GPU_CODER_BIT, _ASCII, _GAMMA or _DELTA; anything else: TDC_GPU_ERR_UNSUPPORTED for the call.
+ * status[k]: TDC_GPU_OK, or TDC_GPU_ERR_TOO_LARGE for a text of more than 2^24 = 16 777 216 bytes -- the cap of ONE text in a batch (one
+ * workgroup walks the text once per rule; tdc_gpu_repair_compress is the tool for such a text) --, with out_len[k] = 0 and no byte of
+ * `out` taken; the other texts are coded normally and the call returns TDC_GPU_OK.
+ * status[k] can also be TDC_GPU_ERR_INTERNAL: the text's round loop met a broken invariant (a full table, a tie without a winner, a round
+ * that took no pair).  That is a bug of the library, not a property of the text; the text is then treated like a refused one, and callers
+ * should check for it as for TOO_LARGE.
+ * The call itself, decided from the arguments alone before the context is looked at, in this order: TDC_GPU_ERR_UNSUPPORTED for the
+ * coder; TDC_GPU_ERR_ARG for a NULL argument, in_off[0] != 0 or a decreasing in_off; TDC_GPU_ERR_TOO_LARGE for more than 2^32 - 2 bytes
+ * in all; TDC_GPU_ERR_ARG for a NULL context.  TDC_GPU_ERR_OOM with the required size in out_off[count] if out_cap is too small --
+ * decided from the sizes before anything is packed, nothing is written to `out` then -- or if the device cannot hold the arena (DESIGN.md
+ * section 5.8 states the formula: at most 142 bytes per text byte).  count = 0 is valid and writes only out_off[0] = 0.
+ * Options of the context (not enumerated by tdc_gpu_option_name): repair_batch_rounds (rounds per text and launch, divided by n_k / 64 KiB for a text above 128 KiB; the host relaunches
+ * while a text is unfinished, one read-back per launch), repair_batch_table (0: a text's digram table has 4 slots per text byte; 1: 2
+ * slots, so that small texts reach the in-kernel rebuild -- tests; the same streams).
+ * stats (may be NULL): n (all input bytes), out_len (bytes used), rules, replaced, tie_rounds and rebuilds (summed over the accepted
+ * texts), len_rounds (the LAUNCHES of the round kernel), ms_h2d, ms_factorize (the grammars and the placement), ms_encode (the pack),
+ * ms_d2h, ms_total, arena_bytes.
+ * There is no batch decoder yet: the streams are ordinary streams for tdc_repair_decode and tdc_gpu_repair_decompress. */
+int tdc_gpu_repair_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, uint64_t max_rules, int coder,
+                                  uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
+                                  int32_t* status /* count */, tdc_gpu_stats* stats);
+/* what `out` of tdc_gpu_repair_compress_batch needs at most: the sum of tdc_gpu_repair_bound of every text, each rounded up to 8.  0 for
+ * a coder the call does not take, for offsets it refuses, or for more than 2^32 - 2 bytes in all. */
+size_t tdc_gpu_repair_batch_bound(const uint64_t* in_off, size_t count, int coder);
+/* The grammars of such a batch alone, what tdc_repair_grammar computes for every text on the host: the rules of text k are
+ * rules[rule_off[k] .. rule_off[k + 1]) (l << 32 | r), its start sequence start[start_off[k] .. start_off[k + 1]).  rules and start hold
+ * in_off[count] entries, rule_off and start_off count + 1.  status[k]: TDC_GPU_OK, or TDC_GPU_ERR_TOO_LARGE / TDC_GPU_ERR_INTERNAL as in the
+ * batch call (no rules, no symbols).
+ * Arguments are refused as by the batch call (there is no coder). */
+int tdc_gpu_repair_grammar_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, uint64_t max_rules,
+                                 uint64_t* rules /* in_off[count] */, uint64_t* rule_off /* count + 1 */,
+                                 uint32_t* start /* in_off[count] */, uint64_t* start_off /* count + 1 */, int32_t* status /* count */);
+
 /* RePairCompressor::decompress.  bit, gamma and delta streams are decoded ON THE DEVICE ("Device decoder"): the
  * tokens are parsed side by side, the grammar becomes a factor list (lengths bottom-up, first occurrences top-down) and the reference
  * resolver of the other decoders writes the text.  Option dec_parse picks the path: 1 (default) = streams of 1 MiB and more, 2 = every

@@ -278,6 +278,13 @@ def repair_bound(n, coder=CODER_BIT):
     return _native.load().tdc_gpu_repair_bound(n, int(coder))
 
 
+def repair_batch_bound(lengths, coder=CODER_BIT):
+    """what the output of repair_compress_batch needs at most for texts of these lengths: the single bounds, each rounded up to 8,
+    summed (0: a coder repair does not take, or more than 2^32 - 2 bytes in all)"""
+    off = _offsets(lengths)
+    return _native.load().tdc_gpu_repair_batch_bound(_ptr(off), len(lengths), int(coder))
+
+
 def lzss_lcp_bound(n, coder=CODER_HUFF):
     """worst-case length of an lzss_lcp stream for a text of n bytes (0: a coder lzss_lcp does not take)"""
     return _native.load().tdc_gpu_lzss_lcp_bound(n, int(coder))
@@ -796,6 +803,53 @@ class Context:
         return ol.value, st.as_dict()
 
     repair_bound = staticmethod(repair_bound)
+
+    def repair_compress_batch_into(self, data, in_off, out, max_rules=0, coder=CODER_BIT):
+        """tdc_gpu_repair_compress_batch on caller-owned buffers: text k = data[in_off[k]:in_off[k + 1]] (in_off: count + 1 uint64), the
+        streams into `out` (PinnedBuffer or writable uint8 array; repair_batch_bound sizes it).  The grammars are built on the device, one
+        workgroup per text.  Returns (out_off, out_len, status, stats): stream k = out[out_off[k]:out_off[k] + out_len[k]], status[k] -4
+        for a text beyond the cap of one text (2^24 bytes); stats["len_rounds"] counts the launches.  A buffer that is too small raises
+        TdcGpuError (status -5) whose `required` is the size."""
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        count = len(off) - 1
+        out_off, out_len = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+        status, st = np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = self._L.tdc_gpu_repair_compress_batch(self._h, _ptr(ta) if len(ta) else None, _ptr(off), count, int(max_rules), int(coder),
+                                                   _ptr(oa), oa.size, _ptr(out_off), _ptr(out_len), _ptr(status), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, int(out_off[count]))
+        return out_off, out_len[:count], status[:count], st.as_dict()
+
+    def repair_compress_batch(self, texts, max_rules=0, coder=CODER_BIT):
+        """repair over many independent texts in one call: returns (list of streams, statuses, stats).  Stream k is what repair_compress
+        returns for texts[k] alone; a refused text (statuses[k] -4) yields b""."""
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        out = np.empty(max(repair_batch_bound(lengths, coder), 8), dtype=np.uint8)
+        out_off, out_len, status, st = self.repair_compress_batch_into(data, _offsets(lengths), out, max_rules, coder)
+        streams = [out[int(o):int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+        return streams, status.tolist(), st
+
+    repair_batch_bound = staticmethod(repair_batch_bound)
+
+    def repair_grammar_batch(self, texts, max_rules=0):
+        """the grammars of a batch alone: returns (rules, start, statuses) -- rules[k] (uint64, l << 32 | r) and start[k] (uint32) are
+        what repair_grammar computes for texts[k] on the host"""
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        off = _offsets(lengths)
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        n, count = len(data), len(parts)
+        rules, start = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+        rule_off, start_off = np.zeros(count + 1, dtype=np.uint64), np.zeros(count + 1, dtype=np.uint64)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        self._check(self._L.tdc_gpu_repair_grammar_batch(self._h, _ptr(data) if n else None, _ptr(off), count, int(max_rules), _ptr(rules),
+                                                         _ptr(rule_off), _ptr(start), _ptr(start_off), _ptr(status)))
+        return ([rules[int(a):int(b)].copy() for a, b in zip(rule_off[:-1], rule_off[1:])],
+                [start[int(a):int(b)].copy() for a, b in zip(start_off[:-1], start_off[1:])], status[:count].tolist())
 
     def repair_grammar(self, data, max_rules=0):
         """the grammar from the device: (rules, start, stats) -- rules[k] = l << 32 | r (uint64), start the sequence that is left (uint32)"""
@@ -1505,6 +1559,13 @@ class RePairCompressor:
         out, st = self.ctx.repair_compress(data, self.max_rules, self.coder)
         self.last_stats = st
         return out
+
+    def compress_batch(self, texts):
+        """every text on its own in one device call, one workgroup per grammar: (list of streams, statuses); stream k is
+        compress(texts[k])"""
+        out, status, st = self.ctx.repair_compress_batch(texts, self.max_rules, self.coder)
+        self.last_stats = st
+        return out, status
 
     def decompress(self, stream):
         if self.dec == "gpu":

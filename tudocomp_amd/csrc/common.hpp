@@ -214,6 +214,8 @@ struct Ctx {
     int repair_log = 0;            // repair: one line per round on stderr
     int repair_dec_rounds = 1024;  // repair, device decoder: most rounds of the length and of the first-occurrence pass; a grammar that needs more (a chain of rules) is decoded by the host loop
     int lz_batch_hash_bits = 0;    // lzw / lz78 batches: 0 = the whole hash of a phrase picks its home slot; k = 1 .. 24: only k bits of it do (every node in 2^k homes, long probe runs; tests)
+    int repair_batch_rounds = 1024; // repair batches: most rounds per text and launch; the host relaunches while a text is unfinished (one read-back per launch)
+    int repair_batch_table = 0;    // repair batches: 0 = the digram table of a text has 4 slots per text byte, 1 = 2 (small texts reach the in-kernel rebuild; tests)
     int dec_log = 0, bwt_log = 0, pipe_log = 0, level_log = 0, wsort_log = 0, eager_dump = 0, small_prof = 0, arena_log = 0;   // diagnostics on stderr
 
     // overlapped D2H of the compressed stream (end-to-end entry point with a caller buffer): while the pack kernel works on the

@@ -721,6 +721,18 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
+    // every text on its own in one device call, one workgroup per grammar (tdc_gpu_repair_compress_batch): streams[k] is what compress()
+    // writes for texts[k]; where status[k] is not TDC_GPU_OK (a text beyond the cap of one text in a batch) the stream is empty
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const uint64_t max_rules = (uint64_t)m_max_rules;
+        lz_compress_batch(m_ctx->h,
+                          [max_rules](tdc_gpu_ctx* h, const uint8_t* in, const uint64_t* in_off, size_t count, int coder, uint8_t* out, size_t out_cap,
+                                      uint64_t* out_off, uint64_t* out_len, int32_t* st, tdc_gpu_stats* stats) {
+                              return tdc_gpu_repair_compress_batch(h, in, in_off, count, max_rules, coder, out, out_cap, out_off, out_len, st, stats);
+                          },
+                          tdc_gpu_repair_batch_bound, m_coder, texts, streams, status, &last_stats);
+    }
     // :287-336 -- the host loop (tdc_repair_decode: the rules expanded with an explicit stack), which needs no device; dec=gpu (an
     // addition, as for lzss): the device decoder (tdc_gpu_repair_decompress, which keeps the host loop for coder=ascii).  The stream is
     // the same either way.
