@@ -576,7 +576,8 @@ int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64
  * stats (may be NULL): n (all input bytes), out_len (bytes used), rules, replaced, tie_rounds and rebuilds (summed over the accepted
  * texts), len_rounds (the LAUNCHES of the round kernel), ms_h2d, ms_factorize (the grammars and the placement), ms_encode (the pack),
  * ms_d2h, ms_total, arena_bytes.
- * There is no batch decoder yet: the streams are ordinary streams for tdc_repair_decode and tdc_gpu_repair_decompress. */
+ * The batch decoder is tdc_gpu_repair_decompress_batch below; the streams are also ordinary streams for tdc_repair_decode and
+ * tdc_gpu_repair_decompress. */
 int tdc_gpu_repair_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t count, uint64_t max_rules, int coder,
                                   uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
                                   int32_t* status /* count */, tdc_gpu_stats* stats);
@@ -608,6 +609,44 @@ int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size
  * download), ms_total -- host clock around synchronisations; all zero but n, out_len and ms_total where the host loop decoded. */
 int tdc_gpu_repair_decompress_stats(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len,
                                     tdc_gpu_stats* stats);
+/* The decoder of repair batches, or of any collection of repair streams (repair_batch_decode.hip, DESIGN.md section 5.8 "Batch decoder").
+ * The arguments are those of tdc_gpu_lzw_decompress_batch, one by one: stream k = streams[s_off[k], s_off[k] + s_len[k]) (any order, any
+ * alignment; together they must lie within 2^32 - 2 bytes), text k = out[out_off[k], out_off[k + 1]), the texts back to back; a refused
+ * stream contributes 0 bytes and disturbs no neighbour.  coder: TDC_GPU_CODER_BIT, _GAMMA or _DELTA; _ASCII and anything else is
+ * TDC_GPU_ERR_UNSUPPORTED for the call (ascii streams: loop tdc_repair_decode).  Always on the device -- option dec_parse is not
+ * consulted, no stream is too small, nothing is handed to the host loop -- and in ONE pass: one wave per stream finds the token borders,
+ * the rules of all streams with their references rebased form one forest, and the grammar passes of tdc_gpu_repair_decompress run over
+ * it once.  The call synchronises a constant number of times (plus the rounds of the length pass, of the first-occurrence pass and of
+ * the resolver, which depend on the deepest accepted grammar), whatever count is.  tdc_gpu_ctx_last_decode_on_device is 1 after a
+ * successful call.
+ * status[k]: the verdict of tdc_repair_decode on stream k alone -- TDC_GPU_OK with the same bytes; TDC_GPU_ERR_ARG for a cut-off field, a
+ * stream that ends inside its rules, more rules than twice the stream's bytes, a rule index out of range, a cut-off terminator, the
+ * stream of no bytes; TDC_GPU_ERR_TOO_LARGE for a text above 2^32 - 2 bytes.  An index is checked against its OWN stream: a side of
+ * rule i names a rule below i of that stream, a start symbol a rule below its R; nothing in front of a stream's own rules or text is
+ * reachable.  A stream that holds a bad token AND claims too much text is TDC_GPU_ERR_ARG, as on the host (both parse the whole stream
+ * before they look at a length).  Two deviations from the host's verdict, and no other:
+ *   1. the device caps of the single decoder: a gamma / delta index field (the count field among them) of more than 32 value bits is
+ *      TDC_GPU_ERR_ARG -- the host refuses it too --, and so is a literal code of more than 8 value bits, although the host loop keeps
+ *      its low byte (no encoder writes one);
+ *   2. depth: a stream whose grammar is higher than option repair_dec_rounds (default 1024) is TDC_GPU_ERR_UNSUPPORTED and contributes 0
+ *      bytes; tdc_gpu_repair_decompress decodes it through the host loop.  A byte has height 0, a rule 1 + the larger height of its sides,
+ *      and the height counts over ALL rules of the stream: a deep rule that nothing names refuses an otherwise shallow stream too.  The
+ *      verdict is a function of the stream and the option alone.
+ * out == NULL or out_cap too small: TDC_GPU_ERR_OOM with the required total in out_off[count] and all of out_off / status filled -- the
+ * sizes alone, so that a caller can size its buffer; nothing is written to `out`.  More than 2^32 - 2 bytes of text in all, or
+ * 2^32 - 258 tokens (sides of rules and start symbols) and more in all: TDC_GPU_ERR_TOO_LARGE for the call, before anything text-sized
+ * is allocated.  Decided from the arguments alone, before the context is looked at, in this order: TDC_GPU_ERR_UNSUPPORTED for the
+ * coder; TDC_GPU_ERR_ARG for a NULL s_off, s_len, out_off or status, for a stream whose end overflows, for streams == NULL with a
+ * non-empty stream; TDC_GPU_ERR_ARG for a NULL context.  count = 0 is valid and writes only out_off[0] = 0.  TDC_GPU_ERR_INTERNAL: the
+ * first-occurrence pass did not come to rest within its bound -- a bug of the library, not a property of a stream.
+ * stats (may be NULL): n (all stream bytes), out_len (all text bytes), rules (summed over the accepted streams), factors (the factor
+ * list of the accepted streams), len_rounds (rounds of the length pass), levels (rounds of the first-occurrence pass), flatten_rounds
+ * (pointer-jumping rounds of the resolver), ms_h2d, ms_factorize (walks, lengths and sizes, up to the read-back of out_off and status),
+ * ms_encode (first occurrences, items, the resolver and -- the resolver hands the text over as it finishes -- its download; ms_d2h stays
+ * 0), ms_total, arena_bytes. */
+int tdc_gpu_repair_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len,
+                                    size_t count, int coder, uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */,
+                                    int32_t* status /* count */, tdc_gpu_stats* stats);
 
 /* ---- bwt: BWTCompressor::compress / ::decompress (compressors/BWTCompressor.hpp:29-60, ds/bwt.hpp:20-98), the Burrows-Wheeler transform
  * of the text.  Text contract and error codes of tdc_gpu_lcpcomp_compress (escaped, ONE terminating 0; TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG

@@ -835,6 +835,17 @@ class Context:
 
     repair_batch_bound = staticmethod(repair_batch_bound)
 
+    def repair_decompress_batch_into(self, blob, s_off, s_len, out, coder=CODER_BIT):
+        """tdc_gpu_repair_decompress_batch on caller-owned buffers, as lzw_decompress_batch_into: coder bit, gamma or delta, always on the
+        device, the grammars of all streams as one forest.  status[k] is what repair_decode says of stream k alone (0, -2, -4), -2 for a
+        gamma / delta field beyond the device's caps, or -6 for a grammar higher than option repair_dec_rounds."""
+        return self._lz_decompress_batch_into("repair", blob, s_off, s_len, out, coder)
+
+    def repair_decompress_batch(self, streams, coder=CODER_BIT):
+        """the decoder of repair_compress_batch, or of any list of repair streams: returns (list of texts, statuses, stats); a refused
+        stream yields b"" and disturbs no neighbour"""
+        return self._lz_decompress_batch("repair", streams, coder)
+
     def repair_grammar_batch(self, texts, max_rules=0):
         """the grammars of a batch alone: returns (rules, start, statuses) -- rules[k] (uint64, l << 32 | r) and start[k] (uint32) are
         what repair_grammar computes for texts[k] on the host"""
@@ -1573,6 +1584,13 @@ class RePairCompressor:
                 raise RuntimeError("repair: dec=gpu needs a context")
             return self.ctx.repair_decompress(stream, self.coder)
         return repair_decode(stream, self.coder)
+
+    def decompress_batch(self, streams):
+        """(list of texts, statuses) on the device, all streams in one pass, whatever dec says; text k is decompress(streams[k]), b""
+        where it is refused.  coder=ascii is refused as the C call refuses it (status -6): loop decompress() over such streams."""
+        out, status, st = self.ctx.repair_decompress_batch(streams, self.coder)
+        self.last_stats = st
+        return out, status
 
 
 class LZSSLCPCompressor:

@@ -42,7 +42,7 @@ SYMBOLS = [
     "tdc_gpu_lzw_decompress_batch", "tdc_gpu_lz78_decompress_batch",
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
     "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
-    "tdc_gpu_repair_compress_batch", "tdc_gpu_repair_batch_bound", "tdc_gpu_repair_grammar_batch",
+    "tdc_gpu_repair_compress_batch", "tdc_gpu_repair_batch_bound", "tdc_gpu_repair_grammar_batch", "tdc_gpu_repair_decompress_batch",
 ]
 
 
@@ -212,6 +212,7 @@ def load():
     L.tdc_gpu_repair_batch_bound.argtypes = [vp, sz, i32]
     L.tdc_gpu_repair_batch_bound.restype = sz
     L.tdc_gpu_repair_grammar_batch.argtypes = [vp, vp, vp, sz, u64, vp, vp, vp, vp, vp]
+    L.tdc_gpu_repair_decompress_batch.argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, vp, vp, ctypes.POINTER(Stats)]
     L.tdc_gpu_lzss_sw_decompress.argtypes = [vp, vp, sz, i32, u32, pvp, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lzss_sw_decompress_into.argtypes = [vp, vp, sz, i32, u32, vp, sz, psz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     L.tdc_gpu_lzss_sw_compress_batch.argtypes = [vp, vp, vp, sz, u32, u32, i32, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]

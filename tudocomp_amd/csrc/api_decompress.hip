@@ -346,6 +346,143 @@ void repair_decompress(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int 
     ctx->last_decode_device = (int)rs.dec.device_parse;
     sink_commit(s, n);
 }
+
+// ---- repair streams in a batch (repair_batch_decode.hip): one forest of rules, one pass, never the host loop ----------------------------
+// the refusals decided from the arguments alone, in the order of tdc_gpu_repair_compress_batch: the coder first
+void repair_batch_dec_check(const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder, const uint64_t* out_off,
+                            const int32_t* status) {
+    if (coder != TDC_GPU_CODER_BIT && coder != TDC_GPU_CODER_GAMMA && coder != TDC_GPU_CODER_DELTA)
+        throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "repair batch: coder must be bit, gamma or delta (ascii streams: tdc_repair_decode)"};
+    if (!out_off || (count && (!s_off || !s_len || !status))) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    for (size_t k = 0; k < count; ++k)
+        if (s_off[k] + s_len[k] < s_off[k]) throw ArgError{TDC_GPU_ERR_ARG, "repair batch: a stream's end overflows"};
+    for (size_t k = 0; k < count; ++k)
+        if (s_len[k] && !streams) throw ArgError{TDC_GPU_ERR_ARG, "NULL argument"};
+    if (count > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "repair batch: too many streams"};
+}
+
+void repair_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                             uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    Ctx& c = ctx->c;
+    ctx->last_decode_device = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    out_off[0] = 0;
+    if (count == 0) return;
+    const int kind = dec_kind(coder);
+    // the part of `streams` the batch lies in, from the 4-byte border in front of its first byte on
+    u64 lo = ~0ull, hi = 0, bytes_in = 0;
+    for (size_t k = 0; k < count; ++k) {
+        if (!s_len[k]) continue;
+        lo = std::min<u64>(lo, s_off[k]); hi = std::max<u64>(hi, s_off[k] + s_len[k]);
+        bytes_in += s_len[k];
+    }
+    if (hi == 0) lo = 0;
+    const u64 sub = lo & ~3ull;
+    const size_t extent = (size_t)(hi - sub);
+    if (extent > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "repair batch: the streams must lie within 2^32 - 2 bytes"};
+    const size_t slack = (size_t)16 << 20;
+    // (with the slack of the grammar and the two of the text pass: the batches a compressor writes do not move the arena)
+    const size_t fixed = extent + 64 + 56 * (count + 1) + 16 * 256 + 16384 + 3 * slack;
+    // per token: its symbol, and what a rule (two tokens: two lengths, a first occurrence) or a start symbol (a position) adds at most |
+    // per token: class byte, index and 12 bytes per factor | per text byte: text, d_ref, the done bits
+    const size_t per_token = 12, per_item = 17, per_byte = 5;
+    reserve_arena(c, fixed + 40 * extent);                        // (room for the grammars and the texts of most batches; more: the arena moves below)
+    Events ev(c);
+    const int e0 = ev.tick();
+    hipStream_t s = c.stream;
+    u8* d_blob = c.arena.get<u8>(extent + 64);
+    if (extent) HIP_TRY(hipMemcpyAsync(d_blob, streams + sub, extent, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_blob + extent, 0, 64, s));
+    u64* d_soff = c.arena.get<u64>(count), *d_slen = c.arena.get<u64>(count), *d_bits = c.arena.get<u64>(count);
+    u64* d_roff = c.arena.get<u64>(count + 1), *d_toff = c.arena.get<u64>(count + 1), *d_ooff = c.arena.get<u64>(count + 1);
+    int* d_status = c.arena.get<int>(count);
+    u64* d_rules = c.arena.get<u64>(1);
+    HIP_TRY(hipMemcpyAsync(d_soff, s_off, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_slen, s_len, count * sizeof(u64), hipMemcpyHostToDevice, s));
+    const int e1 = ev.tick();
+    RepairBatchDec D;
+    D.blob = d_blob; D.sub = sub; D.s_off = d_soff; D.s_len = d_slen; D.bits = d_bits; D.status = d_status; D.rule_off = d_roff; D.start_off = d_toff;
+    D.ooff = d_ooff; D.rules = d_rules;
+    repair_batch_decode_count(c, kind, count, D);
+    // the two numbers the arena's size depends on (no array may hold an entry per stream bit, so the tokens are counted first)
+    RepairBatchGrammar G;
+    G.R = (size_t)c.read(d_roff + count); G.M = (size_t)c.read(d_toff + count);
+    const u64 items = 2 * (u64)G.R + G.M;
+    if (items >= 0xFFFFFFFEull - 256) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "repair batch: the streams hold 2^32 - 258 tokens or more in all"};
+    const u32 cap = (u32)std::min<long>(std::max<long>(c.repair_dec_rounds, 1), 1l << 24);
+    u64 rules = 0;
+    u32 len_rounds = 0, first_rounds = 0, ref_rounds = 0;
+    size_t zf = 0, mk_len2 = 0;
+    if (items == 0) {                                             // no token anywhere: every text is empty, the verdicts are the first walk's
+        HIP_TRY(hipMemsetAsync(d_ooff, 0, (count + 1) * sizeof(u64), s));
+    } else {
+        if (c.arena.size < c.arena.mark() + per_token * (size_t)items + 8192 + 3 * slack) {              // (the text pass keeps its slack)
+            void* a = d_blob; void* b = d_soff; void* l = d_slen; void* t = d_bits; void* r = d_roff; void* m = d_toff; void* o = d_ooff; void* v = d_status;
+            void* f = d_rules;
+            regrow_arena(c, fixed + (per_token + per_item) * (size_t)items + 4 * per_byte * extent + 8192 + slack,
+                         {{&a, extent + 64}, {&b, count * 8}, {&l, count * 8}, {&t, count * 8}, {&r, (count + 1) * 8}, {&m, (count + 1) * 8},
+                          {&o, (count + 1) * 8}, {&v, count * 4}, {&f, 8}});
+            D.blob = (const u8*)a; D.s_off = (const u64*)b; D.s_len = (const u64*)l; D.bits = (u64*)t; D.rule_off = (u64*)r; D.start_off = (u64*)m;
+            D.ooff = (u64*)o; D.status = (int*)v; D.rules = (u64*)f;
+        }
+        G.sym = c.arena.get<u32>((size_t)items); G.len = c.arena.get<u32>(G.R + 1); G.first = c.arena.get<u32>(G.R + 1); G.pos = c.arena.get<u64>(G.M + 1);
+        mk_len2 = c.arena.mark();                                 // (what lies above is dead behind the sizes)
+        G.len2 = c.arena.get<u32>(G.R + 1);
+        u32* d_flags = c.arena.get<u32>(8);
+        len_rounds = repair_batch_decode_sizes(c, kind, count, D, G, cap, d_flags);
+    }
+    // the one round of read-backs every decision below rests on
+    c.read_n(D.ooff, (u64*)out_off, count + 1);
+    c.read_n(D.status, (int*)status, count);
+    if (items) rules = c.read(D.rules);
+    const int e2 = ev.tick();
+    const u64 total = out_off[count];
+    if (total > 0xFFFFFFFEull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "repair batch: the streams decode to more than 2^32 - 2 bytes in all"};
+    if (!out || total > out_cap) throw ArgError{TDC_GPU_ERR_OOM, "repair batch: output buffer too small (out_off[count] holds the required size)"};
+    int e3 = e2;
+    if (total) {
+        const size_t n = (size_t)total, nit = (size_t)items;
+        c.arena.release(mk_len2);
+        u32* d_flags = c.arena.get<u32>(8);
+        // every accepted grammar is at most `cap` high: its first occurrences rest after cap rounds and are seen to in the one behind
+        first_rounds = repair_batch_decode_first(c, G, cap + 1, d_flags);
+        if (!first_rounds) throw HipError{hipErrorUnknown, "repair batch decode: the first occurrences did not come to rest", (int)__LINE__};
+        const size_t text_need = per_item * nit + per_byte * n + n / 8 + 8192 + 2 * slack;
+        if (c.arena.size < c.arena.mark() + text_need) {
+            void* a = G.sym; void* b = G.len; void* f = G.first; void* p = G.pos;
+            const size_t live = nit * 4 + (G.R + 1) * 8 + (G.M + 1) * 8 + 4 * 320;
+            regrow_arena(c, live + text_need, {{&a, nit * 4}, {&b, (G.R + 1) * 4}, {&f, (G.R + 1) * 4}, {&p, (G.M + 1) * 8}});
+            G.sym = (u32*)a; G.len = (u32*)b; G.first = (u32*)f; G.pos = (u64*)p;
+        }
+        u32* d_cnt = c.arena.get<u32>(2);
+        u8* cls = c.arena.get<u8>(nit);
+        u32* fidx = c.arena.get<u32>(nit);
+        u8* d_text = c.arena.get<u8>(n + 64);
+        zf = repair_batch_decode_items(c, G, n, d_text, cls, fidx, d_cnt);
+        u32* fpos = c.arena.get<u32>(zf + 1), *fsrc = c.arena.get<u32>(zf + 1), *flen = c.arena.get<u32>(zf + 1);
+        repair_batch_decode_factors(c, G, fidx, zf, fpos, fsrc, flen);
+        u32* d_ref = c.arena.get<u32>(n);
+        if (zf == 0) {                                            // literals only: the text is complete
+            HIP_TRY(hipMemcpyAsync(out, d_text, n, hipMemcpyDeviceToHost, s));
+        } else {
+            Sink sink;
+            size_t written = 0;
+            sink.into = out; sink.cap = out_cap; sink.out_len = &written;
+            DecodeStats ds;
+            resolve_and_download(c, n, d_text, d_ref, fpos, fsrc, flen, zf, d_cnt, sink, &ds);
+            ref_rounds = ds.rounds;
+        }
+        e3 = ev.tick();
+    }
+    if (stats) {
+        stats->n = bytes_in; stats->out_len = total; stats->rules = rules; stats->factors = zf; stats->arena_bytes = c.arena.high;
+        stats->len_rounds = len_rounds; stats->levels = first_rounds; stats->flatten_rounds = ref_rounds;
+        ev.span(&stats->ms_h2d, e0, e1); ev.span(&stats->ms_factorize, e1, e2); ev.span(&stats->ms_encode, e2, e3);
+        ev.span(&stats->ms_total, e0, e3);
+    }
+    ev.finish();
+    ctx->last_decode_device = 1;
+}
 }  // namespace
 
 extern "C" {
@@ -439,6 +576,13 @@ int tdc_gpu_repair_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* stream, size
 int tdc_gpu_repair_decompress_stats(tdc_gpu_ctx* ctx, const uint8_t* stream, size_t len, int coder, uint8_t* out, size_t out_cap, size_t* out_len,
                                     tdc_gpu_stats* stats) {
     return guarded(ctx, [&] { repair_decompress(ctx, stream, len, coder, sink_into(out, out_cap, out_len), stats); });
+}
+
+int tdc_gpu_repair_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, const uint64_t* s_off, const uint64_t* s_len, size_t count, int coder,
+                                    uint8_t* out, size_t out_cap, uint64_t* out_off, int32_t* status, tdc_gpu_stats* stats) {
+    try { repair_batch_dec_check(streams, s_off, s_len, count, coder, out_off, status); }                 // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { repair_decompress_batch(ctx, streams, s_off, s_len, count, coder, out, out_cap, out_off, status, stats); });
 }
 
 }  // extern "C"

@@ -358,6 +358,39 @@ size_t repair_bound(size_t n, int kind);
 // clock around synchronisations).
 struct RepairDecodeStats { DecodeStats dec; u64 rules = 0, nstart = 0; u32 segments = 0, len_rounds = 0, first_rounds = 0; float ms_h2d = 0, ms_grammar = 0, ms_text = 0; };
 bool decode_repair(Ctx& c, const u8* stream, size_t len, int kind, Sink& out, size_t* need, RepairDecodeStats* st, size_t* n_out);
+// ---- repair streams in a batch (repair_batch_decode.hip, DESIGN.md section 5.8 "Batch decoder") ------------------------------------------
+// Stream k = blob[s_off[k] - sub, + s_len[k]), the blob 4-byte aligned and padded with 64 zero bytes; kind as decode_repair.  The rules of
+// all streams lie back to back (stream k: rule_off[k] .. rule_off[k + 1]) with their references rebased to global rule indices, the start
+// sequences likewise behind them: one forest, whose text is the texts back to back.  The caller provides every array.
+struct RepairBatchDec {
+    const u8* blob = nullptr; u64 sub = 0;
+    const u64* s_off = nullptr, *s_len = nullptr;
+    u64* bits = nullptr;          // count: the payload bits of stream k; behind _sizes: the scan of all start symbols at its first one
+    int* status = nullptr;        // count: a status of tdc_gpu.h
+    u64* rule_off = nullptr;      // count + 1: the rule counts, then their scan; [count]: all rules
+    u64* start_off = nullptr;     // count + 1: the same for the start symbols
+    u64* ooff = nullptr;          // count + 1: the scan of the accepted text lengths
+    u64* rules = nullptr;         // 1: the rules of the accepted streams
+};
+// The forest: R = rule_off[count] rules, M = start_off[count] start symbols.  sym (2 R + M): the sides of rule k at 2 k and 2 k + 1, start
+// symbol j at 2 R + j; len, len2, first: R + 1 entries each (entry R is the rule `nothing`, of length 0; len2 is the second buffer of the
+// length rounds and dead behind _sizes); pos: M + 1, the text position of every start symbol, [M] the scan's total.
+struct RepairBatchGrammar {
+    size_t R = 0, M = 0;
+    u32* sym = nullptr, *len = nullptr, *len2 = nullptr, *first = nullptr; u64* pos = nullptr;
+};
+// bits, the first walk (one wave per stream: R_k, m_k and the verdict), rule_off and start_off; enqueued only
+void repair_batch_decode_count(Ctx& c, int kind, size_t count, RepairBatchDec& D);
+// The second walk (the symbols, rebased), the lengths in at most `cap` strict rounds -- a stream that owns a rule higher than cap is
+// TDC_GPU_ERR_UNSUPPORTED --, positions, the per-stream sizes and verdicts, ooff and *rules; the start symbols of refused streams become
+// `nothing`.  2 R + M >= 1.  d_flags: 8 words.  Returns the length rounds that ran up to the quiet one; it synchronises once per 8 rounds.
+u32 repair_batch_decode_sizes(Ctx& c, int kind, size_t count, RepairBatchDec& D, RepairBatchGrammar& G, u32 cap, u32* d_flags);
+// first occurrences at the global positions, seeded from the start symbols; the rounds that ran, 0: `cap` rounds did not come to rest
+u32 repair_batch_decode_first(Ctx& c, const RepairBatchGrammar& G, u32 cap, u32* d_flags);
+// the literals to d_text (n + 64 bytes), cls / fidx (2 R + M entries each): the items that are factors; returns their number (synchronises)
+size_t repair_batch_decode_items(Ctx& c, const RepairBatchGrammar& G, size_t n, u8* d_text, u8* cls, u32* fidx, u32* d_cnt);
+// the factor list for resolve_and_download (zf + 1 entries each)
+void repair_batch_decode_factors(Ctx& c, const RepairBatchGrammar& G, const u32* fidx, size_t zf, u32* fpos, u32* fsrc, u32* flen);
 
 // ---- bwt (compressors/BWTCompressor.hpp, ds/bwt.hpp; bwt.hip) ---------------------------------------------
 // forward: d_out[i] = T[SA[i] - 1] (T[n - 1] where SA[i] = 0), i < n; d_out holds n + 64 bytes.  host_dst (nullable): where the transform

@@ -733,6 +733,13 @@ public:
                           },
                           tdc_gpu_repair_batch_bound, m_coder, texts, streams, status, &last_stats);
     }
+    // The decoder of such a batch, or of any collection of repair streams, on the device: the grammars of all streams as one forest, one
+    // pass, whatever dec says (tdc_gpu_repair_decompress_batch; bit, gamma, delta -- coder=ascii is refused as the call refuses it).
+    // texts[k] is what decompress() writes for streams[k], empty where status[k] is not TDC_GPU_OK.
+    void decompress_batch(const std::vector<bytes>& streams, std::vector<bytes>& texts, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        lz_decompress_batch(m_ctx->h, tdc_gpu_repair_decompress_batch, m_coder, streams, texts, status, &last_stats);
+    }
     // :287-336 -- the host loop (tdc_repair_decode: the rules expanded with an explicit stack), which needs no device; dec=gpu (an
     // addition, as for lzss): the device decoder (tdc_gpu_repair_decompress, which keeps the host loop for coder=ascii).  The stream is
     // the same either way.
