@@ -671,6 +671,44 @@ int tdc_gpu_bwt_decompress_into(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len
 int tdc_gpu_bwt_inverse_stage(tdc_gpu_ctx* ctx, const uint8_t* bwt, size_t len, uint32_t sample, uint32_t max_steps, uint8_t* out,
                               uint32_t* lf, uint64_t* heads, uint32_t* launches);
 
+/* bwt over a batch of independent texts, both directions (bwt_batch.hip; DESIGN.md section 5.2 "Batches" and "Batch decoder").  Text k
+ * is in[off[k], off[k + 1]) (off: count + 1 entries, off[0] = 0, the texts back to back); a transform has exactly its text's length, so
+ * result k is written to the same range of `out`, out[off[k], off[k + 1]): `out` needs off[count] bytes, there is no out_off and no bound
+ * function.  The range of a refused text is left untouched, a refused text costs its neighbours nothing, and the call returns TDC_GPU_OK.
+ * Result k is byte for byte what the single call returns for text k alone.
+ * tdc_gpu_bwt_compress_batch: text k has the contract of tdc_gpu_bwt_compress (escaped, ONE terminating 0) and status[k] is that call's
+ * code for it -- TDC_GPU_OK, TDC_GPU_ERR_NO_SENTINEL (also for the text of no bytes), TDC_GPU_ERR_ARG for an inner 0 -- with one
+ * exception: a text of more than BWT_BATCH_TEXT_CAP = 2^20 = 1 048 576 bytes is TDC_GPU_ERR_TOO_LARGE, refused before any work (the batch
+ * is built for many small texts; tdc_gpu_bwt_compress is the tool for a long one).  status[k] can also be TDC_GPU_ERR_INTERNAL: the text's
+ * doubling rounds did not come to rest within the call's bound, bits_for(the longest accepted text) + 1 -- a bug of the library, not a
+ * property of the text.  The suffix sort is
+ * a prefix doubling over the unresolved positions of all texts at once, ranks never compared across texts.
+ * tdc_gpu_bwt_decompress_batch: status[k] is the verdict of tdc_gpu_bwt_decompress on buffer k alone -- TDC_GPU_OK with the same bytes (a
+ * buffer of 0 or 1 bytes is TDC_GPU_OK and writes nothing), TDC_GPU_ERR_ARG for a buffer of two or more bytes that has not exactly one 0
+ * byte or whose LF mapping is not one cycle.  There is no cap per buffer; the LF cycles of all buffers are ranked as one forest of lists.
+ * The call synchronises a constant number of times plus the launches of the first walk and the pointer-jumping rounds, whatever count is.
+ * The call itself, decided from the arguments alone before the context is looked at, in this order: TDC_GPU_ERR_ARG for a NULL off or
+ * status, off[0] != 0, a decreasing off or in == NULL with off[count] > 0; TDC_GPU_ERR_TOO_LARGE for off[count] > 2^32 - 2 (forward),
+ * off[count] >= 2^31 - 1 (inverse: the top bit of an LF word marks a cut) or 2^31 texts and more; TDC_GPU_ERR_ARG for `out` overlapping
+ * `in` and for a NULL context.  out == NULL or out_cap < off[count]: TDC_GPU_ERR_OOM, nothing written to `out`, status filled with
+ * what needs no device (forward: the terminator and the lengths; inverse: TDC_GPU_OK).  TDC_GPU_ERR_OOM also if the device cannot hold the
+ * arena: 64 bytes per text byte forward, 40 inverse, plus 64 MiB (DESIGN.md states the formulas).  count = 0 is valid.
+ * Options of the context (tests; not enumerated by tdc_gpu_option_name): bwt_batch_sample (expected rows per list of the inverse) and
+ * bwt_batch_steps (most steps of a walk per launch), 0 = the library's choice; the same bytes whatever they are.
+ * stats (may be NULL): n, out_len, ms_h2d, ms_sa (forward: the sort; inverse: LF), ms_encode (forward: the gather; inverse: the walks and
+ * the ranking), ms_d2h, ms_total, arena_bytes; len_rounds = the doubling rounds behind the initial sort (forward: the most any text
+ * took) or the pointer-jumping rounds (inverse); forward: sa_sorted_elems = records sorted over all rounds; inverse: levels = launches
+ * of the first walk, entries = list heads in the end, flen_max = the longest list. */
+#define BWT_BATCH_TEXT_CAP ((size_t)1 << 20)
+int tdc_gpu_bwt_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off /* count + 1 */, size_t count, uint8_t* out,
+                               size_t out_cap, int32_t* status /* count */, tdc_gpu_stats* stats);
+int tdc_gpu_bwt_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off /* count + 1 */, size_t count, uint8_t* out,
+                                 size_t out_cap, int32_t* status /* count */, tdc_gpu_stats* stats);
+/* tests and later batches: the suffix arrays alone, sa[off[k] + i] = the i-th smallest suffix of text k, counted from the text's start
+ * (off[count] entries; the range of a refused text is left untouched).  Arguments and status as for tdc_gpu_bwt_compress_batch. */
+int tdc_gpu_suffix_array_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off /* count + 1 */, size_t count,
+                               uint32_t* sa /* off[count] */, int32_t* status /* count */);
+
 /* ---- rle, mtf, encode(huff), encode(sle) and chains of them behind bwt: the reference's `bwtzip = bwt:rle:mtf:encode(huff)`
  * (etc/compare-suites/default.suite).  A pipeline is a sequence of 1 .. 8 stages; every stage's whole output is the
  * next stage's input (tudocomp_driver/ChainCompressor.hpp: `a:b:c` = chain(chain(a, b), c)) and stays in device memory, only the last

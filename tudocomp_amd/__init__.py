@@ -1187,6 +1187,71 @@ class Context:
                                                       _ptr(lf) if want_lf else None, ctypes.byref(h), ctypes.byref(ln)))
         return (out.tobytes() if len(a) > 1 else b""), {"lf": lf, "heads": h.value, "launches": ln.value}
 
+    def _bwt_batch_into(self, fn, data, off, out):
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        if oa is not None and not (isinstance(oa, np.ndarray) and oa.dtype == np.uint8 and oa.flags.c_contiguous and oa.flags.writeable):
+            raise TypeError("out must be a PinnedBuffer or a writable, contiguous uint8 array")      # (the call writes oa.size bytes from its first one)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        count = len(off) - 1
+        status, st = np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = fn(self._h, _ptr(ta) if len(ta) else None, _ptr(off), count, _ptr(oa) if oa is not None and oa.size else None,
+                oa.size if oa is not None else 0, _ptr(status), ctypes.byref(st))
+        if rc:
+            self._raise_required(rc, int(off[count]))
+        return status[:count], st.as_dict()
+
+    def bwt_compress_batch_into(self, data, off, out):
+        """tdc_gpu_bwt_compress_batch on caller-owned buffers: text k = data[off[k]:off[k + 1]] (off: count + 1 uint64, the escaped,
+        0-terminated views back to back), its transform into the same range of `out` (PinnedBuffer or writable uint8 array of off[count]
+        bytes).  Returns (status, stats): status[k] is what bwt_compress says of text k alone (0, -3, -2), or -4 for a text beyond the
+        cap of one text (BWT_BATCH_TEXT_CAP = 2^20 bytes); the range of a refused text is left untouched.  A buffer that is too small
+        raises TdcGpuError (status -5) whose `required` is off[count]."""
+        return self._bwt_batch_into(self._L.tdc_gpu_bwt_compress_batch, data, off, out)
+
+    def bwt_decompress_batch_into(self, data, off, out):
+        """tdc_gpu_bwt_decompress_batch on caller-owned buffers, laid out as for bwt_compress_batch_into: returns (status, stats);
+        status[k] is the verdict of bwt_decompress on buffer k alone (0, or -2 for what is no transform).  A buffer of 0 or 1 bytes is
+        accepted and writes nothing."""
+        return self._bwt_batch_into(self._L.tdc_gpu_bwt_decompress_batch, data, off, out)
+
+    def _bwt_batch(self, into, items, short):
+        parts = [_u8(t) for t in items]
+        lengths = [len(a) for a in parts]
+        off = _offsets(lengths)
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        out = np.zeros(max(len(data), 1), dtype=np.uint8)
+        status, st = into(data, off, out)
+        res = [out[int(a):int(b)].tobytes() if s == 0 and int(b) - int(a) > short else b"" for a, b, s in zip(off[:-1], off[1:], status)]
+        return res, status.tolist(), st
+
+    def bwt_compress_batch(self, texts):
+        """bwt over many independent texts in one call: returns (list of transforms, statuses, stats).  Transform k is what bwt_compress
+        returns for texts[k] alone; a refused text yields b\"\"."""
+        return self._bwt_batch(self.bwt_compress_batch_into, texts, 0)
+
+    def bwt_decompress_batch(self, bwts):
+        """the inverse of bwt_compress_batch, or of any list of transforms: returns (list of texts, statuses, stats); a refused buffer
+        and a buffer of at most one byte yield b\"\", and none disturbs a neighbour"""
+        return self._bwt_batch(self.bwt_decompress_batch_into, bwts, 1)
+
+    def suffix_array_batch(self, texts):
+        """the suffix arrays of many independent texts in one call: returns (list of uint32 arrays, statuses, stats); array k holds
+        positions counted from the start of texts[k], a refused text yields an empty array.  The C call keeps no statistics: stats
+        holds n, the bytes of all texts, and zeros."""
+        parts = [_u8(t) for t in texts]
+        lengths = [len(a) for a in parts]
+        off = _offsets(lengths)
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        sa = np.zeros(max(len(data), 1), dtype=np.uint32)
+        status = np.zeros(max(len(parts), 1), dtype=np.int32)
+        self._check(self._L.tdc_gpu_suffix_array_batch(self._h, _ptr(data) if len(data) else None, _ptr(off), len(parts), _ptr(sa), _ptr(status)))
+        status = status[:len(parts)]
+        res = [sa[int(a):int(b)].copy() if s == 0 else np.zeros(0, dtype=np.uint32) for a, b, s in zip(off[:-1], off[1:], status)]
+        st = Stats()
+        st.n = len(data)
+        return res, status.tolist(), st.as_dict()
+
     # ---- rle, mtf, encode(huff) and chains ------------------------------------------------------------------
     def pipeline_compress(self, stages, data):
         """stages: [STAGE_* | (STAGE_RLE, offset), ...], intermediates stay on the device.  A leading STAGE_BWT takes the escaped +
@@ -1339,6 +1404,20 @@ class BWTCompressor:
     def decompress(self, stream):
         text, _ = self.ctx.bwt_decompress(stream)
         return unescape(text) if text else b""
+
+    def compress_batch(self, datas):
+        """every input on its own in one device call: (list of transforms, statuses); transform k is compress(datas[k]), b"" where
+        the text is refused (status -4: its escaped view is longer than BWT_BATCH_TEXT_CAP)"""
+        out, status, st = self.ctx.bwt_compress_batch([escape(d) for d in datas])
+        self.last_stats = st
+        return out, status
+
+    def decompress_batch(self, streams):
+        """(list of inputs, statuses), all transforms inverted in one pass: entry k is decompress(streams[k]), None where the buffer
+        is refused (status -2: no transform)"""
+        texts, status, st = self.ctx.bwt_decompress_batch(streams)
+        self.last_stats = st
+        return [None if s else (unescape(t) if t else b"") for t, s in zip(texts, status)], status
 
 
 def parse_chain(spec):

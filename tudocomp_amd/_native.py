@@ -43,6 +43,7 @@ SYMBOLS = [
     "tdc_gpu_repair_compress", "tdc_gpu_repair_compress_into", "tdc_gpu_repair_bound", "tdc_gpu_repair_grammar", "tdc_gpu_repair_decompress",
     "tdc_gpu_repair_decompress_into", "tdc_gpu_repair_decompress_stats", "tdc_repair_grammar", "tdc_repair_decode",
     "tdc_gpu_repair_compress_batch", "tdc_gpu_repair_batch_bound", "tdc_gpu_repair_grammar_batch", "tdc_gpu_repair_decompress_batch",
+    "tdc_gpu_bwt_compress_batch", "tdc_gpu_bwt_decompress_batch", "tdc_gpu_suffix_array_batch",
 ]
 
 
@@ -209,6 +210,9 @@ def load():
     L.tdc_repair_grammar.argtypes =[vp, sz, u64, pvp, psz, pvp, psz]
     L.tdc_repair_decode.argtypes = [vp, sz, i32, vp, sz, psz]
     L.tdc_gpu_repair_compress_batch.argtypes = [vp, vp, vp, sz, u64, i32, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]
+    L.tdc_gpu_bwt_compress_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, ctypes.POINTER(Stats)]
+    L.tdc_gpu_bwt_decompress_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, ctypes.POINTER(Stats)]
+    L.tdc_gpu_suffix_array_batch.argtypes = [vp, vp, vp, sz, vp, vp]
     L.tdc_gpu_repair_batch_bound.argtypes = [vp, sz, i32]
     L.tdc_gpu_repair_batch_bound.restype = sz
     L.tdc_gpu_repair_grammar_batch.argtypes = [vp, vp, vp, sz, u64, vp, vp, vp, vp, vp]

@@ -190,6 +190,15 @@ void run_factorize(Ctx& c, size_t n, DevArrays& A, u32 threshold, int flatten, t
 // the factor list of fs, sorted by pos, in three malloc'd arrays for the caller (tdc_gpu_free); ends the call's event frame (ev.finish())
 void download_factors(Ctx& c, size_t n, const FactorSpace& fs, Events& ev, uint32_t** pos, uint32_t** src, uint32_t** len, size_t* z);
 
+// ---- bwt over a batch of texts (bwt_batch.hip, DESIGN.md section 5.2 "Batches" and "Batch decoder") ----------------------------------------
+// the refusals decided from the arguments alone, before the context is looked at (throws ArgError); `out` holds out_cap elements of elem bytes
+void bwtb_check(const uint8_t* in, const uint64_t* off, size_t count, const void* out, size_t out_cap, size_t elem, const int32_t* status, u64 total_max);
+// the transforms into `out` (want_out) or the suffix arrays into sa_out; the inverse
+void bwtb_forward(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap, bool want_out, uint32_t* sa_out,
+                  int32_t* status, tdc_gpu_stats* stats);
+void bwtb_inverse(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap, int32_t* status,
+                  tdc_gpu_stats* stats);
+
 // ---- the output sink (stages.hpp Sink) ----------------------------------------------------------------------------------------------
 // One of these three builds the sink of an entry point from its arguments.
 // A malloc'd buffer handed to *out.  null_msg: the decompressing entry points refuse a NULL `out` before they look at anything else;

@@ -881,3 +881,21 @@ int tdc_gpu_repair_grammar(tdc_gpu_ctx* ctx, const uint8_t* in, size_t n, uint64
 }
 
 }  // extern "C"
+
+// ---- bwt over a batch of texts (bwt_batch.hip, DESIGN.md section 5.2 "Batches") ----------------------------------------------------------
+extern "C" {
+
+int tdc_gpu_bwt_compress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap,
+                               int32_t* status, tdc_gpu_stats* stats) {
+    try { bwtb_check(in, off, count, out, out_cap, 1, status, 0xFFFFFFFEull); }                       // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { bwtb_forward(ctx, in, off, count, out, out_cap, true, nullptr, status, stats); });
+}
+
+int tdc_gpu_suffix_array_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint32_t* sa, int32_t* status) {
+    try { bwtb_check(in, off, count, sa, SIZE_MAX, 4, status, 0xFFFFFFFEull); }
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { bwtb_forward(ctx, in, off, count, nullptr, 0, false, sa, status, nullptr); });
+}
+
+}  // extern "C"

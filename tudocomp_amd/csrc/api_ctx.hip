@@ -139,7 +139,8 @@ constexpr size_t NOPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
 // (a cross-check mode, a forced table size, a log, the device decoder's depth cap) belong to one compressor; tests/test_gpu_repair.py and
 // tests/test_gpu_repair_decode.py walk them.  lz_batch_hash_bits (the batch parse's table under long probe runs) is walked by
 // tests/test_gpu_lz_batch.py; repair_batch_rounds and repair_batch_table (the batch grammar's launches and its table) by
-// tests/test_gpu_repair_batch.py.
+// tests/test_gpu_repair_batch.py; bwt_batch_sample and bwt_batch_steps (the batch inverse's list heads and walk launches) by
+// tests/test_gpu_bwt_batch.py.
 const OptionDef FOLD_OPTIONS[] = {
     { "fused_cand",       [](Ctx& c, long v) { c.fused_cand = v != 0; } },
     { "sel_tile_counts",  [](Ctx& c, long v) { c.sel_tile_counts = v != 0; } },
@@ -151,6 +152,8 @@ const OptionDef FOLD_OPTIONS[] = {
     { "lz_batch_hash_bits",[](Ctx& c, long v) { c.lz_batch_hash_bits = clampi(v, 0, 24); } },
     { "repair_batch_rounds",[](Ctx& c, long v) { c.repair_batch_rounds = clampi(v, 1, 1 << 24); } },
     { "repair_batch_table",[](Ctx& c, long v) { c.repair_batch_table = v != 0; } },
+    { "bwt_batch_sample", [](Ctx& c, long v) { c.bwt_batch_sample = clampi(v, 0, 1 << 24); } },
+    { "bwt_batch_steps",  [](Ctx& c, long v) { c.bwt_batch_steps = clampi(v, 0, 1 << 30); } },
 };
 constexpr size_t NFOLD = sizeof(FOLD_OPTIONS) / sizeof(FOLD_OPTIONS[0]);
 const OptionDef* find_option(const char* name) {

@@ -586,3 +586,15 @@ int tdc_gpu_repair_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* streams, co
 }
 
 }  // extern "C"
+
+// ---- bwt buffers in a batch (bwt_batch.hip, DESIGN.md section 5.2 "Batch decoder"): the LF cycles of all buffers as one forest --------------
+extern "C" {
+
+int tdc_gpu_bwt_decompress_batch(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap,
+                                 int32_t* status, tdc_gpu_stats* stats) {
+    try { bwtb_check(in, off, count, out, out_cap, 1, status, 0x7FFFFFFEull); }                       // (the top bit of an LF word stays free)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { bwtb_inverse(ctx, in, off, count, out, out_cap, status, stats); });
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include "stages.hpp"
 #include "prim.hpp"
 #include "decode.hpp"
+#include "bwt_passes.hpp"
 
 namespace tdc {
 namespace {
@@ -101,29 +102,6 @@ __global__ void __launch_bounds__(256) bwt_lf_kernel(const u8* __restrict__ b, s
 }
 
 // ---- inverse: list ranking ------------------------------------------------------------------------------------------------------------
-// Row i is a list head iff mix(i) < T, and mix(i) is then its slot in the head table: a bijection of [0, 2^m) (2^m >= n) with mix(0) = 0,
-// so row 0 always is one, nothing is enumerated and a walk that meets a head knows its slot.  Multiples of S would be periodic in row space.
-struct Mix { u32 mask, h, T, inv_a, inv_b; };
-constexpr u32 MIX_A = 0x9E3779B1u, MIX_B = 0x85EBCA6Bu;
-__device__ __forceinline__ u32 mix(u32 i, const Mix& m) {
-    u32 x = (i * MIX_A) & m.mask;
-    x ^= x >> m.h;
-    x = (x * MIX_B) & m.mask;
-    return x ^ (x >> m.h);
-}
-__device__ __forceinline__ u32 unmix(u32 k, const Mix& m) {       // (2 h >= m: the fold is its own inverse)
-    u32 x = k ^ (k >> m.h);
-    x = (x * m.inv_b) & m.mask;
-    x ^= x >> m.h;
-    return (x * m.inv_a) & m.mask;
-}
-u32 inv_odd(u32 a) { u32 x = a; for (int i = 0; i < 6; ++i) x *= 2u - a * x; return x; }
-
-// head table: hrow[k] = first row of the list of slot k (NONE32: the slot's row lies behind the text), hlen[k] = rows in it,
-// w[k] = link << 32 | length: the slot the list runs into (NONE32: it ends the cycle) and the rows up to there
-constexpr u64 W_END = (u64)NONE32 << 32;
-struct Heads { u32* hrow; u32* hlen; unsigned long long* w; u32* cnt; /* [0] slots in use, [1] longest list, [2] overflow, [3] changed */ u32 cap; };
-
 __global__ void __launch_bounds__(256) bwt_heads_init_kernel(Heads H, Mix m, u32 n) {
     for (u64 kk = (u64)blockIdx.x * 256 + threadIdx.x; kk < m.T; kk += (u64)gridDim.x * 256) {
         const u32 k = (u32)kk;
@@ -163,27 +141,6 @@ __global__ void __launch_bounds__(256) bwt_walk1_kernel(const u32* __restrict__ 
     }
     longest = wave_reduce_max(longest);
     if (lane_id() == 0 && longest) atomicMax(&H.cnt[1], longest);
-}
-
-// Pointer jumping over the heads, in place: w[k] = (l, d) says "d rows from the head of k up to the head of l"; whatever state w[l] is
-// read in, (l', d + d') says the same of l'.  The words are read and written whole.
-__global__ void __launch_bounds__(256) bwt_jump_kernel(Heads H, u32 slots) {
-    bool changed = false;
-    for (u64 kk = (u64)blockIdx.x * 256 + threadIdx.x; kk < slots; kk += (u64)gridDim.x * 256) {
-        const u32 k = (u32)kk;
-        const u64 a = __hip_atomic_load(&H.w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const u32 l = (u32)(a >> 32);
-        if (l == NONE32) continue;
-        const u64 b = __hip_atomic_load(&H.w[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&H.w[k], (unsigned long long)((b & W_END) | (u32)((u32)a + (u32)b)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        changed = true;
-    }
-    if (__any(changed) && lane_id() == 0) H.cnt[3] = 1u;
-}
-
-__device__ __forceinline__ void put_bytes(u8* out, size_t word, u32 acc, u32 lo, u32 hi) {      // byte lanes lo .. hi of the word at `word`
-    if (lo == 0 && hi == 3) { *(u32*)(out + word) = acc; return; }
-    for (u32 l = lo; l <= hi; ++l) out[word + l] = (u8)(acc >> (8 * l));
 }
 
 // Second walk: the head of slot k starts `n - w[k]` rows behind row 0; the row t behind row 0 puts its byte at n - 2 - t (the last row
@@ -271,11 +228,7 @@ size_t bwt_inverse(Ctx& c, const u8* bwt, size_t len, u32 sample, u32 max_steps,
     const bool dlog = c.bwt_log != 0;                       // stage times on stderr (synchronises)
     const DecTick tick = dec_ticker(c, "bwt", dlog);
 
-    Mix mx;
-    const u32 mbits = (u32)bits_for(n - 1);                  // 1 .. 31
-    mx.mask = (u32)((1ull << mbits) - 1); mx.h = (mbits + 1) / 2;
-    mx.T = (u32)((((u64)1 << mbits) + S - 1) / S);
-    mx.inv_a = inv_odd(MIX_A); mx.inv_b = inv_odd(MIX_B);
+    const Mix mx = make_mix(n, S);
     const u32 ntiles = cdiv(n, LF_TILE);
     const size_t cap = (size_t)mx.T + n / M + 2;             // hashed slots + one per max_steps rows walked
     // (on_device: the transform lies in the arena already, what is needed comes from the room above it)

@@ -783,6 +783,50 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
+    // every text on its own in one device call (tdc_gpu_bwt_compress_batch): streams[k] is what compress() writes for texts[k] -- each
+    // escaped and terminated like a view; where status[k] is not TDC_GPU_OK (a view beyond the cap of one text in a batch) it is empty
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        bytes in, piece;
+        std::vector<uint64_t> off(texts.size() + 1, 0);
+        for (size_t k = 0; k < texts.size(); ++k) {
+            piece.resize(2 * texts[k].size() + 1);
+            piece.resize(tdc_escape(texts[k].data(), texts[k].size(), piece.data()));
+            in.insert(in.end(), piece.begin(), piece.end());
+            off[k + 1] = in.size();
+        }
+        batch_call(tdc_gpu_bwt_compress_batch, in, off, streams, status, 0);
+    }
+    // The inverse of such a batch, or of any collection of transforms, on the device in one pass whatever dec says
+    // (tdc_gpu_bwt_decompress_batch): texts[k] is what decompress() writes for streams[k], empty where status[k] is not TDC_GPU_OK.
+    void decompress_batch(const std::vector<bytes>& streams, std::vector<bytes>& texts, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        bytes in;
+        std::vector<uint64_t> off(streams.size() + 1, 0);
+        for (size_t k = 0; k < streams.size(); ++k) { in.insert(in.end(), streams[k].begin(), streams[k].end()); off[k + 1] = in.size(); }
+        batch_call(tdc_gpu_bwt_decompress_batch, in, off, texts, status, 1);
+        for (bytes& t : texts) {
+            if (t.empty()) continue;
+            bytes raw(t.size());
+            raw.resize(tdc_unescape(t.data(), t.size(), raw.data()));
+            t.swap(raw);
+        }
+    }
+private:
+    // results longer than `shortest` bytes are handed out (a buffer of at most one byte inverts to nothing)
+    template <typename Call>
+    void batch_call(Call call, const bytes& in, const std::vector<uint64_t>& off, std::vector<bytes>& res, std::vector<int32_t>& status, size_t shortest) {
+        const size_t count = off.size() - 1;
+        bytes out(in.size() ? in.size() : 1);
+        status.assign(count ? count : 1, 0);
+        const int rc = call(m_ctx->h, in.data(), off.data(), count, out.data(), out.size(), status.data(), &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        status.resize(count);
+        res.assign(count, bytes());
+        for (size_t k = 0; k < count; ++k)
+            if (!status[k] && off[k + 1] - off[k] > shortest) res[k].assign(out.begin() + off[k], out.begin() + off[k + 1]);
+    }
+public:
     // decode_bwt (ds/bwt.hpp:77-98): LF[i] = C[b[i]] + rank of b[i] among the equal bytes in front; n - 1 steps from row 0, then the 0.
     // C is accumulated over ALL byte values here (the reference's loop stops in front of 255, which breaks texts that hold 0xFF --
     // every escaped 0x00 or 0xFF byte).  Like the reference the host loop does not look at what it is given beyond staying inside the
