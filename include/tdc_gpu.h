@@ -744,6 +744,45 @@ int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
  * on the copy stream (page-locked memory -- tdc_gpu_host_alloc -- receives it at the host link's rate). */
 int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
                                    size_t out_cap, size_t* out_len, tdc_gpu_stats* stats);
+/* ---- a chain over a batch: many independent texts in one call (bytestages_batch.hip, bwt_batch.hip; DESIGN.md section 5.3 "Batches").
+ * Any chain of bwt (first only), rle, mtf and encode(huff).  The texts lie back to back in `in`: text k = in[in_off[k], in_off[k + 1]);
+ * in_off has count + 1 entries, does not decrease, and in_off[0] = 0.  Stream k = out[out_off[k], out_off[k] + out_len[k]) is byte for byte
+ * what tdc_gpu_pipeline_compress returns for text k alone with the same stages, the empty text included wherever that call accepts it:
+ * nothing of one text reaches another one's stream -- no run spans a border, every text starts from the list 0 .. 255 and has its own
+ * histogram, table, header and terminator.  out_off[k] is a multiple of 8, out_off[count] the number of bytes used; the bytes between two
+ * streams are unspecified.  The intermediates of all texts stay in device memory; the call makes a constant number of launches and
+ * synchronisations whatever count is (but for the doubling rounds of a leading bwt: tdc_gpu_bwt_compress_batch).
+ * status[k] is the single call's code for text k alone -- under a leading bwt TDC_GPU_ERR_NO_SENTINEL, TDC_GPU_ERR_ARG for an inner 0 and
+ * TDC_GPU_ERR_INTERNAL as documented for tdc_gpu_bwt_compress_batch -- with one exception that holds for every chain: a text of more than
+ * BWT_BATCH_TEXT_CAP = 2^20 bytes is TDC_GPU_ERR_TOO_LARGE, refused before any work (the single call is the tool for a long text).  A
+ * refused text has out_len[k] = 0 and costs its neighbours nothing; the call returns TDC_GPU_OK.
+ * The call itself, decided from the arguments alone before the context is looked at, in this order: TDC_GPU_ERR_ARG for a NULL in_off,
+ * out_off, out_len or status, in_off[0] != 0, a decreasing in_off, in == NULL with bytes to read; for the stage list what
+ * tdc_gpu_pipeline_compress says (TDC_GPU_ERR_NO_SENTINEL for a bwt behind the first stage, TDC_GPU_ERR_ARG for an invalid list);
+ * TDC_GPU_ERR_UNSUPPORTED for a list that holds TDC_GPU_STAGE_SLE; TDC_GPU_ERR_TOO_LARGE for more than 2^32 - 2 input bytes in all or
+ * 2^31 texts and more; TDC_GPU_ERR_ARG for a NULL context.
+ * The exact sizes are known before the last stage writes: out == NULL or an out_cap that is too small gives TDC_GPU_ERR_OOM with out_off,
+ * out_len and status completely filled and the required total in out_off[count] -- nothing is written to `out`, the sizes pass alone.  A
+ * stage whose output over the whole batch would pass 2^32 - 2 bytes: TDC_GPU_ERR_TOO_LARGE for the call, before anything is written to
+ * `out`.  count = 0 is valid and writes only out_off[0] = 0.
+ * Arena, reserved before any work (TDC_GPU_ERR_OOM if the device cannot hold it): n + 80 count bytes for the input, then the larger of
+ * what tdc_gpu_bwt_compress_batch takes (64 n + 64 count + 64 MiB) and, summed over the byte stages with L = the stage's worst-case input,
+ * 0.5625 L + 4624 count + 1 MiB of scratch plus the stage's worst-case output (tdc_gpu_pipeline_bound's terms; encode(huff) 1024 count more).
+ * stats (may be NULL): n (all input bytes), out_len (bytes used), pipe_stages, pipe_len[i] = the bytes behind stage i summed over the
+ * accepted texts, pipe_ms[i] (option pipe_log: one synchronisation per stage; the stage of encode(huff) includes the host's table build,
+ * which the log prints on a line of its own), arena_bytes, ms_h2d, ms_d2h, ms_total, and for a leading bwt the fields
+ * tdc_gpu_bwt_compress_batch fills.  Option pipe_batch_threads (not enumerated by tdc_gpu_option_name): host threads of that table build,
+ * 0 = min(16, hardware threads); the same bytes on any number.
+ * The streams are ordinary pipeline streams: tdc_gpu_pipeline_decompress, the host decoders below and tdc_gpu_bwt_decompress_batch decode
+ * them.  A batch decoder of the chain and encode(sle) over a batch are not built. */
+int tdc_gpu_pipeline_compress_batch(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages,
+                                    const uint8_t* in, const uint64_t* in_off /* count + 1 */, size_t count,
+                                    uint8_t* out, size_t out_cap, uint64_t* out_off /* count + 1 */, uint64_t* out_len /* count */,
+                                    int32_t* status /* count */, tdc_gpu_stats* stats);
+/* what `out` of tdc_gpu_pipeline_compress_batch needs at most: the sum of tdc_gpu_pipeline_bound of every text, each rounded up to 8; a
+ * text above the cap contributes 0.  0 for what the call refuses from its arguments (an encode(sle) stage and more than 2^32 - 2 bytes in
+ * all among them). */
+size_t tdc_gpu_pipeline_batch_bound(const tdc_gpu_stage* stages, int nstages, const uint64_t* in_off, size_t count);
 /* Inverse, stage by stage from the last one, on the device: one upload of the stream, the decoders of rle, mtf, encode(huff) and encode(sle)
  * (csrc/bytestages_decode.hip) and the inverse of a leading bwt work from buffer to buffer in the arena, one download (*out then holds the
  * escaped, 0-terminated text if the pipeline starts with bwt).  Option dec_parse picks the path once per call from the stream's length:

@@ -254,6 +254,14 @@ def lzss_sw_batch_bound(lengths, window=16, coder=CODER_BIT):
     return _native.load().tdc_gpu_lzss_sw_batch_bound(_ptr(off), len(lengths), int(window), int(coder))
 
 
+def pipeline_batch_bound(stages, lengths):
+    """what the output of pipeline_compress_batch needs at most for texts of these lengths: pipeline_bound of every text, each rounded
+    up to 8, summed; a text above 2^20 bytes contributes 0 (0: an invalid pipeline, an encode(sle) stage, more than 2^32 - 2 bytes in all)"""
+    arr, k = _stages(stages)
+    off = _offsets(lengths)
+    return _native.load().tdc_gpu_pipeline_batch_bound(arr, k, _ptr(off), len(lengths))
+
+
 def lzw_batch_bound(lengths, coder=CODER_BIT):
     """what the output of lzw_compress_batch needs at most for texts of these lengths (0: a coder lzw does not take, or more than
     2^32 - 2 bytes in all)"""
@@ -1274,6 +1282,52 @@ class Context:
             self._raise_required(rc, ol.value)
         return ol.value, st.as_dict()
 
+    def pipeline_compress_batch_into(self, stages, data, in_off, out):
+        """tdc_gpu_pipeline_compress_batch on caller-owned buffers: text k = data[in_off[k]:in_off[k + 1]] (in_off: count + 1 uint64), any
+        chain of bwt (first only), rle, mtf and encode(huff); the streams into `out` (PinnedBuffer, writable uint8 array, or None for
+        the sizes alone).  Returns (out_off, out_len, status, stats): stream k = out[out_off[k]:out_off[k] + out_len[k]] is what
+        pipeline_compress returns for text k alone, status[k] that call's code (-4 for a text above 2^20 bytes).  A buffer that is
+        missing or too small raises TdcGpuError (status -5) whose `required` is the size and whose `sizes` is (out_off, out_len,
+        status), complete."""
+        arr, k = _stages(stages)
+        ta = data.a if isinstance(data, PinnedBuffer) else _u8(data)
+        oa = out.a if isinstance(out, PinnedBuffer) else out
+        off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        count = len(off) - 1
+        out_off, out_len = np.zeros(count + 1, dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+        status, st = np.zeros(max(count, 1), dtype=np.int32), Stats()
+        rc = self._L.tdc_gpu_pipeline_compress_batch(self._h, arr, k, _ptr(ta) if len(ta) else None, _ptr(off), count,
+                                                     _ptr(oa) if oa is not None else None, oa.size if oa is not None else 0,
+                                                     _ptr(out_off), _ptr(out_len), _ptr(status), ctypes.byref(st))
+        if rc:
+            try:
+                self._raise_required(rc, int(out_off[count]))
+            except TdcGpuError as e:
+                e.sizes = (out_off, out_len[:count], status[:count])
+                raise
+        return out_off, out_len[:count], status[:count], st.as_dict()
+
+    def pipeline_compress_batch(self, stages, texts):
+        """a chain over many independent texts in one call: returns (list of streams, statuses, stats).  Stream k is what
+        pipeline_compress returns for texts[k] alone, b"" where statuses[k] is not 0.  The buffer is sized by the call's sizes pass,
+        not by pipeline_batch_bound (encode(huff) is bounded by 8 n + 1024 per text)."""
+        parts = [_u8(t) for t in texts]
+        off = _offsets([len(a) for a in parts])
+        data = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        required = 0
+        try:
+            self.pipeline_compress_batch_into(stages, data, off, None)
+        except TdcGpuError as e:
+            if e.status != -5 or getattr(e, "required", None) is None:
+                raise
+            required = int(e.required)
+        out = np.empty(max(required, 8), dtype=np.uint8)
+        out_off, out_len, status, st = self.pipeline_compress_batch_into(stages, data, off, out)
+        streams = [out[int(o):int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+        return streams, status.tolist(), st
+
+    pipeline_batch_bound = staticmethod(pipeline_batch_bound)
+
     def pipeline_decompress(self, stages, stream):
         """inverse of pipeline_compress, stage by stage on the device (option dec_parse: 1 = streams of 1 MiB and more, 2 = every stream,
         0 = the host loops for rle, mtf and encode(huff))"""
@@ -1466,6 +1520,15 @@ class ChainCompressor:
         if self.stages[0][0] == STAGE_BWT:
             return unescape(text) if text else b""
         return text
+
+    def compress_batch(self, datas):
+        """every input on its own in one device call: (list of streams, statuses); stream k is compress(datas[k]), b"" where the text
+        is refused (status -4: it -- under a leading bwt its escaped view -- is longer than 2^20 bytes).  A chain with encode(sle)
+        raises TdcGpuError with status -6: it has no batch form.  The streams are decompress()'s; a batch decoder is not built."""
+        lead = self.stages[0][0] == STAGE_BWT
+        out, status, st = self.ctx.pipeline_compress_batch(self.stages, [escape(d) for d in datas] if lead else datas)
+        self.last_stats = st
+        return out, status
 
 
 class RunLengthEncoder(ChainCompressor):

@@ -31,7 +31,7 @@ SYMBOLS = [
     "tdc_gpu_lcpcomp_compress_keep", "tdc_gpu_stream_fetch", "tdc_gpu_stream_fetch_dev", "tdc_gpu_host_register", "tdc_gpu_host_unregister",
     "tdc_gpu_lz78_decompress", "tdc_gpu_lz78_decompress_into",
     "tdc_gpu_bwt_compress", "tdc_gpu_bwt_compress_into", "tdc_gpu_bwt_decompress", "tdc_gpu_bwt_decompress_into", "tdc_gpu_bwt_inverse_stage",
-    "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_decompress",
+    "tdc_gpu_pipeline_bound", "tdc_gpu_pipeline_compress", "tdc_gpu_pipeline_compress_into", "tdc_gpu_pipeline_compress_batch", "tdc_gpu_pipeline_batch_bound", "tdc_gpu_pipeline_decompress",
     "tdc_gpu_pipeline_decompress_into", "tdc_gpu_pipeline_decompress_stats", "tdc_rle_decode", "tdc_mtf_decode", "tdc_huff_decode_literals", "tdc_sle_decode",
     "tdc_gpu_lzw_compress", "tdc_gpu_lzw_decompress", "tdc_gpu_lzw_decompress_into", "tdc_lzw_factors", "tdc_lzw_decode",
     "tdc_gpu_lzss_lcp_compress_into", "tdc_gpu_lzss_lcp_bound", "tdc_gpu_lzss_lcp_decompress", "tdc_gpu_lzss_lcp_decompress_into", "tdc_lzss_decode",
@@ -170,6 +170,9 @@ def load():
     L.tdc_gpu_pipeline_bound.restype = sz
     L.tdc_gpu_pipeline_compress.argtypes = [vp, pst, i32, vp, sz, pvp, psz, ctypes.POINTER(Stats)]
     L.tdc_gpu_pipeline_compress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]
+    L.tdc_gpu_pipeline_compress_batch.argtypes = [vp, pst, i32, vp, vp, sz, vp, sz, vp, vp, vp, ctypes.POINTER(Stats)]
+    L.tdc_gpu_pipeline_batch_bound.argtypes = [pst, i32, vp, sz]
+    L.tdc_gpu_pipeline_batch_bound.restype = sz
     L.tdc_gpu_pipeline_decompress.argtypes = [vp, pst, i32, vp, sz, pvp, psz]
     L.tdc_gpu_pipeline_decompress_into.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz]
     L.tdc_gpu_pipeline_decompress_stats.argtypes = [vp, pst, i32, vp, sz, vp, sz, psz, ctypes.POINTER(Stats)]

@@ -193,9 +193,13 @@ void download_factors(Ctx& c, size_t n, const FactorSpace& fs, Events& ev, uint3
 // ---- bwt over a batch of texts (bwt_batch.hip, DESIGN.md section 5.2 "Batches" and "Batch decoder") ----------------------------------------
 // the refusals decided from the arguments alone, before the context is looked at (throws ArgError); `out` holds out_cap elements of elem bytes
 void bwtb_check(const uint8_t* in, const uint64_t* off, size_t count, const void* out, size_t out_cap, size_t elem, const int32_t* status, u64 total_max);
-// the transforms into `out` (want_out) or the suffix arrays into sa_out; the inverse
+// the transforms into `out` (want_out) or the suffix arrays into sa_out; the inverse.
+// keep != NULL (the batch pipeline, api_chain.hip): nothing is downloaded -- transform k stays in the arena at d_out + off[k] (the range
+// of a refused text holds nothing), status[] is filled as ever, and the CALLER has reserved the arena (bwtb_forward_arena and its own)
+struct BwtbKeep { u8* d_out = nullptr; };
+size_t bwtb_forward_arena(size_t n, size_t count);
 void bwtb_forward(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap, bool want_out, uint32_t* sa_out,
-                  int32_t* status, tdc_gpu_stats* stats);
+                  int32_t* status, tdc_gpu_stats* stats, BwtbKeep* keep = nullptr);
 void bwtb_inverse(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap, int32_t* status,
                   tdc_gpu_stats* stats);
 

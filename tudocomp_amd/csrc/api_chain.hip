@@ -3,6 +3,7 @@
 // decoders of the byte stages.
 #include "api.hpp"
 #include "bytestages.hpp"
+#include "bytestages_batch.hpp"
 #include "../host/tdc_coders.hpp"
 
 #include <vector>
@@ -229,6 +230,155 @@ void pipeline_compress_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k
         fprintf(stderr, "pipe:     total incl. download %9.2f ms\n", st->ms_total);
     }
     sink_commit(s, out_len);
+}
+
+
+// ---- chains over a batch of texts (bytestages_batch.hip, bwt_batch.hip; DESIGN.md section 5.3 "Batches") ---------------------------------
+// the refusals decided from the arguments alone, in the order include/tdc_gpu.h documents
+void pipeline_batch_check(const tdc_gpu_stage* stages, int k, const uint8_t* in, const uint64_t* in_off, size_t count, const uint64_t* out_off,
+                          const uint64_t* out_len, const int32_t* status) {
+    if (!in_off || !out_off || !out_len || !status) throw ArgError{TDC_GPU_ERR_ARG, "pipeline batch: NULL argument"};
+    if (in_off[0] != 0) throw ArgError{TDC_GPU_ERR_ARG, "pipeline batch: in_off[0] must be 0"};
+    for (size_t t = 0; t < count; ++t)
+        if (in_off[t + 1] < in_off[t]) throw ArgError{TDC_GPU_ERR_ARG, "pipeline batch: in_off must not decrease"};
+    if (!in && in_off[count]) throw ArgError{TDC_GPU_ERR_ARG, "pipeline batch: NULL argument"};
+    if (stages && k >= 1 && k <= TDC_GPU_PIPELINE_MAX_STAGES)
+        for (int i = 1; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_BWT) throw ArgError{TDC_GPU_ERR_NO_SENTINEL, "pipeline: bwt must be the first stage (its input is the escaped, 0-terminated view)"};
+    if (!pipeline_valid(stages, k)) throw ArgError{TDC_GPU_ERR_ARG, "pipeline: 1 .. 8 stages of kind bwt (first only), rle (offset <= 2^62), mtf, encode(huff) or encode(sle) (kmer 1 .. 7)"};
+    for (int i = 0; i < k; ++i) if (stages[i].kind == TDC_GPU_STAGE_SLE) throw ArgError{TDC_GPU_ERR_UNSUPPORTED, "pipeline batch: encode(sle) has no batch form"};
+    if (in_off[count] > STAGE_MAX_BYTES || count > 0x7FFFFFFFull) throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline batch: too many bytes or texts in one call"};
+}
+
+void pipeline_compress_batch_host(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int k, const uint8_t* in, const uint64_t* in_off, size_t count,
+                                  uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_len, int32_t* status, tdc_gpu_stats* stats) {
+    Ctx& c = ctx->c;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    out_off[0] = 0;
+    if (count == 0) return;
+    const size_t n = (size_t)in_off[count];
+    const bool lead_bwt = stages[0].kind == TDC_GPU_STAGE_BWT;
+    const int first = lead_bwt ? 1 : 0;
+    const bool plog = c.pipe_log != 0;
+    // the arena for the whole call, reserved before any work: the padded input, the offsets and verdicts, then the larger of what the
+    // bwt batch takes and of every intermediate at its worst case with its stage's scratch, and the output image
+    u64 need = n + 16 * (u64)count + 64 * (u64)count + 8192, byte_stages = 0, len = std::min<u64>(n, (u64)count * BATCH_TEXT_CAP);
+    for (int i = first; i < k; ++i) {
+        const u64 o = stage_bound(stages[i], len) + (stages[i].kind == TDC_GPU_STAGE_HUFF ? 1024 * (u64)count : 0);    // (a header per text)
+        byte_stages += batch_stage_scratch(len, count) + o + 16 * (u64)count + 4096;
+        len = std::min<u64>(o, STAGE_MAX_BYTES);
+    }
+    byte_stages += len + 48 * (u64)count + (n + 4096) + batch_stage_scratch(0, count);    // the output image, its offsets; the plain input on its way in
+    need += std::max<u64>(byte_stages, lead_bwt ? bwtb_forward_arena(n, count) + 4096 : 0);
+    reserve_arena(c, need);
+    const auto t_start = std::chrono::steady_clock::now();
+    auto t_last = t_start;
+    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    float ms[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    auto tick = [&](int i) {                                  // (synchronises: only with the diagnostic option)
+        if (!plog) return;
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        ms[i] = since(t_last);
+        t_last = std::chrono::steady_clock::now();
+    };
+    hipStream_t s = c.stream;
+    tdc_gpu_stats local = {};
+    tdc_gpu_stats* st = stats ? stats : &local;
+    // layout 0: the accepted texts at multiples of 16, a refused text with length 0
+    BatchLay cur;
+    cur.off = c.arena.get<u64>(count + 1);
+    cur.len = c.arena.get<u64>(count);
+    u64* d_inoff = c.arena.get<u64>(count + 1);
+    int* d_status = c.arena.get<int>(count);
+    std::vector<u64> h_off(count + 1), h_len(count);
+    BwtbKeep keep;
+    if (lead_bwt) {
+        // (the padded buffer is taken first: the bwt batch's scratch goes back before the byte stages take theirs)
+        u64 pad = 0;
+        for (size_t t = 0; t < count; ++t) pad += align_up((size_t)std::min<u64>(in_off[t + 1] - in_off[t], BATCH_TEXT_CAP), 16);
+        cur.d = c.arena.get<u8>(pad + 64);
+    } else {
+        for (size_t t = 0; t < count; ++t) status[t] = in_off[t + 1] - in_off[t] > BATCH_TEXT_CAP ? TDC_GPU_ERR_TOO_LARGE : TDC_GPU_OK;
+    }
+    const size_t mark = lead_bwt ? c.arena.mark() : 0;
+    if (lead_bwt) bwtb_forward(ctx, in, in_off, count, nullptr, 0, false, nullptr, status, st, &keep);
+    for (size_t t = 0; t < count; ++t) {
+        h_len[t] = status[t] == 0 ? in_off[t + 1] - in_off[t] : 0;
+        h_off[t] = cur.padded;
+        cur.padded += align_up((size_t)h_len[t], 16);
+        cur.total += h_len[t];
+    }
+    h_off[count] = cur.padded;
+    if (!lead_bwt) cur.d = c.arena.get<u8>(cur.padded + 64);
+    const size_t mark2 = lead_bwt ? mark : c.arena.mark();
+    HIP_TRY(hipMemcpyAsync(cur.off, h_off.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(cur.len, h_len.data(), count * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_inoff, in_off, (count + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_status, status, count * sizeof(int), hipMemcpyHostToDevice, s));
+    const u8* d_plain = lead_bwt ? keep.d_out : upload_plain(c, in, n);
+    if (cur.total) batch_relayout(c, d_plain, d_inoff, cur.d, cur.off, cur.len, count);
+    HIP_TRY(hipStreamSynchronize(s));                         // (the host arrays above; the plain input goes back to the arena)
+    c.arena.release(mark2);
+    if (!lead_bwt) st->ms_h2d = since(t_start);
+    u64 lens[TDC_GPU_PIPELINE_MAX_STAGES] = {0};
+    if (lead_bwt) { lens[0] = cur.total; tick(0); }
+    // the sizes, as soon as the last stage knows them: the caller's arrays are complete before its buffer is looked at
+    u64 used = 0;
+    const BatchSizesHook sizes = [&](const u64* d_len) {
+        std::vector<u64> hl(count);
+        c.read_n(d_len, hl.data(), count);
+        for (size_t t = 0; t < count; ++t) {
+            out_off[t] = used;
+            out_len[t] = status[t] == 0 ? hl[t] : 0;
+            used += align_up((size_t)out_len[t], 8);
+        }
+        out_off[count] = used;
+        if (!out || out_cap < used) throw ArgError{TDC_GPU_ERR_OOM, "pipeline batch: output buffer too small (out_off[count] holds the required size)"};
+    };
+    const BatchSizesHook none;
+    BatchHuffInfo hinfo;
+    int huff_stage = -1;
+    if (first == k) sizes(cur.len);
+    for (int i = first; i < k; ++i) {
+        const BatchSizesHook& hook = i + 1 == k ? sizes : none;
+        try {
+            switch (stages[i].kind) {
+                case TDC_GPU_STAGE_RLE: cur = rle_encode_batch(c, cur, count, stages[i].param, hook); break;
+                case TDC_GPU_STAGE_MTF: cur = mtf_encode_batch(c, cur, count, hook); break;
+                default: cur = huff_literals_batch(c, cur, count, d_status, status, (u32)c.pipe_batch_threads, &hinfo, hook); huff_stage = i; break;
+            }
+        } catch (const StageTooLarge&) {
+            throw ArgError{TDC_GPU_ERR_TOO_LARGE, "pipeline batch: a stage's output would pass 2^32 - 2 bytes over the batch"};
+        }
+        lens[i] = cur.total;
+        tick(i);
+    }
+    // the streams back to back at multiples of 8, one download
+    const auto t_down = std::chrono::steady_clock::now();
+    if (used) {
+        std::vector<u64> h_ooff(out_off, out_off + count + 1);
+        u64* d_ooff = c.arena.get<u64>(count + 1);
+        u8* d_img = c.arena.get<u8>(used + 64);
+        HIP_TRY(hipMemcpyAsync(d_ooff, h_ooff.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(d_img, 0, used, s));
+        batch_relayout(c, cur.d, cur.off, d_img, d_ooff, cur.len, count);
+        HIP_TRY(hipMemcpyAsync(out, d_img, used, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    st->ms_d2h = since(t_down);
+    st->n = n; st->out_len = used; st->pipe_stages = (uint32_t)k;
+    for (int i = 0; i < k; ++i) { st->pipe_len[i] = lens[i]; st->pipe_ms[i] = ms[i]; }
+    st->arena_bytes = c.arena.high;
+    st->ms_total = since(t_start);
+    if (plog) {
+        u64 prev = n;
+        for (int i = 0; i < k; ++i) {
+            fprintf(stderr, "pipe:     %-14s %12llu -> %12llu bytes %9.2f ms\n", stage_name(stages[i].kind), (unsigned long long)prev, (unsigned long long)lens[i], ms[i]);
+            if (i == huff_stage) fprintf(stderr, "pipe:     huff tables    %12llu tables on %u host threads %9.2f ms (inside encode(huff))\n", (unsigned long long)count, hinfo.threads, hinfo.ms_tables);
+            prev = lens[i];
+        }
+        fprintf(stderr, "pipe:     batch of %llu texts, total incl. download %9.2f ms\n", (unsigned long long)count, st->ms_total);
+    }
 }
 
 
@@ -475,6 +625,25 @@ int tdc_gpu_pipeline_compress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int
 int tdc_gpu_pipeline_compress_into(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t n, uint8_t* out,
                                    size_t out_cap, size_t* out_len, tdc_gpu_stats* stats) {
     return guarded(ctx, [&] { pipeline_compress_host(ctx, stages, nstages, in, n, sink_into(out, out_cap, out_len), stats); });
+}
+
+size_t tdc_gpu_pipeline_batch_bound(const tdc_gpu_stage* stages, int nstages, const uint64_t* in_off, size_t count) {
+    if (!in_off || in_off[0] != 0 || !pipeline_valid(stages, nstages) || count > 0x7FFFFFFFull) return 0;
+    for (int i = 0; i < nstages; ++i) if (stages[i].kind == TDC_GPU_STAGE_SLE) return 0;
+    size_t sum = 0;
+    for (size_t t = 0; t < count; ++t) {
+        if (in_off[t + 1] < in_off[t]) return 0;
+        const u64 nk = in_off[t + 1] - in_off[t];
+        if (nk <= BATCH_TEXT_CAP) sum += align_up(tdc_gpu_pipeline_bound(stages, nstages, (size_t)nk), 8);
+    }
+    return in_off[count] > STAGE_MAX_BYTES ? 0 : sum;
+}
+
+int tdc_gpu_pipeline_compress_batch(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, const uint64_t* in_off, size_t count,
+                                    uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_len, int32_t* status, tdc_gpu_stats* stats) {
+    try { pipeline_batch_check(stages, nstages, in, in_off, count, out_off, out_len, status); }       // (before the context: no device needed)
+    catch (const ArgError& e) { if (ctx) ctx->last_error = e.msg; return e.code; }
+    return guarded(ctx, [&] { pipeline_compress_batch_host(ctx, stages, nstages, in, in_off, count, out, out_cap, out_off, out_len, status, stats); });
 }
 
 int tdc_gpu_pipeline_decompress(tdc_gpu_ctx* ctx, const tdc_gpu_stage* stages, int nstages, const uint8_t* in, size_t len, uint8_t** out,

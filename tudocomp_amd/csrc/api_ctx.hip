@@ -140,7 +140,8 @@ constexpr size_t NOPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
 // tests/test_gpu_repair_decode.py walk them.  lz_batch_hash_bits (the batch parse's table under long probe runs) is walked by
 // tests/test_gpu_lz_batch.py; repair_batch_rounds and repair_batch_table (the batch grammar's launches and its table) by
 // tests/test_gpu_repair_batch.py; bwt_batch_sample and bwt_batch_steps (the batch inverse's list heads and walk launches) by
-// tests/test_gpu_bwt_batch.py.
+// tests/test_gpu_bwt_batch.py; pipe_batch_threads (the host threads of the batch pipeline's Huffman table build: the same tables on any
+// number) by tests/test_gpu_pipeline_batch.py.
 const OptionDef FOLD_OPTIONS[] = {
     { "fused_cand",       [](Ctx& c, long v) { c.fused_cand = v != 0; } },
     { "sel_tile_counts",  [](Ctx& c, long v) { c.sel_tile_counts = v != 0; } },
@@ -154,6 +155,7 @@ const OptionDef FOLD_OPTIONS[] = {
     { "repair_batch_table",[](Ctx& c, long v) { c.repair_batch_table = v != 0; } },
     { "bwt_batch_sample", [](Ctx& c, long v) { c.bwt_batch_sample = clampi(v, 0, 1 << 24); } },
     { "bwt_batch_steps",  [](Ctx& c, long v) { c.bwt_batch_steps = clampi(v, 0, 1 << 30); } },
+    { "pipe_batch_threads",[](Ctx& c, long v) { c.pipe_batch_threads = clampi(v, 0, 16); } },
 };
 constexpr size_t NFOLD = sizeof(FOLD_OPTIONS) / sizeof(FOLD_OPTIONS[0]);
 const OptionDef* find_option(const char* name) {

@@ -294,14 +294,15 @@ void bwtb_download(Ctx& c, const T* d, T* host, const uint64_t* off, size_t coun
     for (const auto& r : runs) memcpy(host + r.first, stage.data() + (r.first - lo), (size_t)(r.second - r.first) * sizeof(T));
 }
 
-// what the forward call takes from the arena for n bytes in count texts (DESIGN.md section 5.2 "Batches" states it)
-size_t bwtb_forward_arena(size_t n, size_t count) { return 64 * n + 64 * count + ((size_t)64 << 20); }
 // ... and the inverse (sample / steps at the library's choice or smaller lists: more heads)
 size_t bwtb_inverse_arena(size_t n, size_t count, size_t cap) { return 40 * n + 32 * count + 16 * cap + ((size_t)64 << 20); }
 
 }  // namespace
 
-// ---- what the entry points call (api.hpp; api_compress.hip, api_decompress.hip) --------------------------------------------------------
+// ---- what the entry points call (api.hpp; api_compress.hip, api_decompress.hip, api_chain.hip) ------------------------------------------
+// what the forward call takes from the arena for n bytes in count texts (DESIGN.md section 5.2 "Batches" states it)
+size_t bwtb_forward_arena(size_t n, size_t count) { return 64 * n + 64 * count + ((size_t)64 << 20); }
+
 // the refusals decided from the arguments alone; throws ArgError
 void bwtb_check(const uint8_t* in, const uint64_t* off, size_t count, const void* out, size_t out_cap, size_t elem, const int32_t* status, u64 total_max) {
     if (!off || !status) throw ArgError{TDC_GPU_ERR_ARG, "bwt batch: NULL argument"};
@@ -325,9 +326,10 @@ static int bwtb_host_status(const uint8_t* in, const uint64_t* off, size_t k) {
     return in[off[k + 1] - 1] != 0 ? TDC_GPU_ERR_NO_SENTINEL : TDC_GPU_OK;
 }
 
-// out (nullable): the transforms; sa_out (nullable): the suffix arrays
+// out (nullable): the transforms; sa_out (nullable): the suffix arrays; keep (nullable): neither -- the transforms stay in the arena, which
+// the caller has reserved
 void bwtb_forward(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size_t count, uint8_t* out, size_t out_cap, bool want_out, uint32_t* sa_out,
-                  int32_t* status, tdc_gpu_stats* stats) {
+                  int32_t* status, tdc_gpu_stats* stats, BwtbKeep* keep) {
     Ctx& c = ctx->c;
     if (stats) memset(stats, 0, sizeof(*stats));
     const size_t n = (size_t)off[count];
@@ -337,9 +339,9 @@ void bwtb_forward(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size
         if (!status[k]) longest = std::max<u64>(longest, off[k + 1] - off[k]);
     }
     if (want_out && n && (!out || out_cap < n)) throw ArgError{TDC_GPU_ERR_OOM, "bwt batch: output buffer too small (off[count] bytes are needed)"};
-    if (!want_out && n && !sa_out) throw ArgError{TDC_GPU_ERR_ARG, "bwt batch: NULL argument"};
+    if (!want_out && n && !sa_out && !keep) throw ArgError{TDC_GPU_ERR_ARG, "bwt batch: NULL argument"};
     if (count == 0 || n == 0) return;
-    reserve_arena(c, bwtb_forward_arena(n, count));
+    if (!keep) reserve_arena(c, bwtb_forward_arena(n, count));
     hipStream_t s = c.stream;
     Events ev(c);
     const int e0 = ev.tick();
@@ -418,6 +420,7 @@ void bwtb_forward(tdc_gpu_ctx* ctx, const uint8_t* in, const uint64_t* off, size
     for (size_t k = 0; k < count; ++k) ok[k] = status[k] == 0;
     if (want_out) bwtb_download(c, d_out, out, off, count, ok);
     if (sa_out) bwtb_download(c, sa, sa_out, off, count, ok);
+    if (keep) keep->d_out = d_out;
     const int e4 = ev.tick();
     if (stats) {
         stats->n = n; stats->out_len = n; stats->arena_bytes = c.arena.high;

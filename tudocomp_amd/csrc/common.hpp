@@ -217,6 +217,7 @@ struct Ctx {
     int repair_batch_rounds = 1024; // repair batches: most rounds per text and launch; the host relaunches while a text is unfinished (one read-back per launch)
     int repair_batch_table = 0;    // repair batches: 0 = the digram table of a text has 4 slots per text byte, 1 = 2 (small texts reach the in-kernel rebuild; tests)
     int bwt_batch_sample = 0, bwt_batch_steps = 0;   // bwt batch decoder: expected rows per list and most steps of a walk per launch (0: BWT_SAMPLE, BWT_STEPS_PER_SAMPLE x sample; small values: tests)
+    int pipe_batch_threads = 0;    // batch pipeline, encode(huff): host threads that build the tables (0: min(16, hardware threads); 1 .. 16 forced; measurements)
     int dec_log = 0, bwt_log = 0, pipe_log = 0, level_log = 0, wsort_log = 0, eager_dump = 0, small_prof = 0, arena_log = 0;   // diagnostics on stderr
 
     // overlapped D2H of the compressed stream (end-to-end entry point with a caller buffer): while the pack kernel works on the

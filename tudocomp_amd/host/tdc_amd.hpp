@@ -919,6 +919,37 @@ public:
         output.write(out, out_len);
         tdc_gpu_free(out);
     }
+    // every text on its own in one device call (tdc_gpu_pipeline_compress_batch): streams[k] is what compress() writes for texts[k] --
+    // under a leading bwt each escaped and terminated like a view; where status[k] is not TDC_GPU_OK (a text or view beyond the cap of
+    // one text in a batch) it is empty.  The buffer is sized by the call's own sizes pass.  A chain with encode(sle) has no batch form.
+    void compress_batch(const std::vector<bytes>& texts, std::vector<bytes>& streams, std::vector<int32_t>& status) {
+        if (!m_ctx) m_ctx = std::make_shared<GpuContext>(m_device);
+        const size_t count = texts.size();
+        const bool lead = m_stages[0].kind == TDC_GPU_STAGE_BWT;
+        bytes in, piece;
+        std::vector<uint64_t> in_off(count + 1, 0), out_off(count + 1, 0), out_len(count ? count : 1, 0);
+        for (size_t k = 0; k < count; ++k) {
+            if (lead) {
+                piece.resize(2 * texts[k].size() + 1);
+                piece.resize(tdc_escape(texts[k].data(), texts[k].size(), piece.data()));
+                in.insert(in.end(), piece.begin(), piece.end());
+            } else in.insert(in.end(), texts[k].begin(), texts[k].end());
+            in_off[k + 1] = in.size();
+        }
+        if (in.empty()) in.resize(1);
+        status.assign(count ? count : 1, 0);
+        const int k = (int)m_stages.size();
+        int rc = tdc_gpu_pipeline_compress_batch(m_ctx->h, m_stages.data(), k, in.data(), in_off.data(), count, nullptr, 0, out_off.data(), out_len.data(),
+                                                 status.data(), nullptr);                                              // the sizes
+        bytes out((size_t)out_off[count] ? (size_t)out_off[count] : 1);
+        if (rc == TDC_GPU_ERR_OOM || rc == TDC_GPU_OK)
+            rc = tdc_gpu_pipeline_compress_batch(m_ctx->h, m_stages.data(), k, in.data(), in_off.data(), count, out.data(), out.size(), out_off.data(),
+                                                 out_len.data(), status.data(), &last_stats);
+        if (rc) throw std::runtime_error(std::string(tdc_gpu_strerror(rc)) + ": " + tdc_gpu_last_error(m_ctx->h));
+        status.resize(count);
+        streams.clear();
+        for (size_t t = 0; t < count; ++t) streams.emplace_back(out.begin() + (size_t)out_off[t], out.begin() + (size_t)(out_off[t] + out_len[t]));
+    }
     // without a device (no context can be created) the byte stages are still decodable: the host loops, which need none
     void decompress_host(Input& input, Output& output) {
         bytes a = input.raw(), b;
